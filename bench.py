@@ -18,14 +18,18 @@ value = constraints/s = n * proofs / max-over-ranks time.
     split over the ranks by bucket range (plk_prover_shard_buckets, round 6) or, where the
     SRS does not allow that split, by SRS slice (plk_prover_shard): one RCCL all-gather of
     partial points per commit group, host fold — strong scaling of proof latency.
-After the timed region the prove line also carries (unless --no-extras) `msm_shard`: one 2^k
+A plain run sets up, warms up, times the steps, writes the last step's outputs if
+--dump-outputs DIR is given and prints the line. Everything else is behind --full: the
+dominant kernel's roofline (one more proof with the GPU to itself), every lane's last proof
+re-proved alone and byte-compared, the CPU baseline, the oracle checks of the ntt / msm
+modes, and (unless --no-extras) `msm_shard`: one 2^k
 MSM split over ALL ranks by bucket range (RCCL all-gather + host fold, checked against the
 unsplit commit; at world 1 the lone MSM against the oracle) — the north star's MSM scaling
 curve, one point per run — and `n_2_16`: the metric's second size, a short 2^16 prove run.
 Every line carries `build_id` (plk_build_info, checked against this tree before anything runs).
 `--gpus N` without a launcher starts N ranks itself (torch.distributed.run, 127.0.0.1).
 Other modes: hotpath (only the NTT/MSM calls of one proof), ntt / msm (BASELINE configs[1] /
-[2], checked bit-exact against the oracle after the timed loop).
+[2], with --full checked bit-exact against the oracle after the timed loop).
 """
 from __future__ import annotations
 
@@ -104,7 +108,21 @@ def parse():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--log-n", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything beside the "
+                         "headline figure: the dominant kernel's roofline (a solo proof of its "
+                         "own), every lane's last proof re-proved alone and byte-compared, the "
+                         "extras (msm_shard, n_2_16), the oracle / unsplit-commit comparisons of "
+                         "the ntt / msm modes and the CPU baseline. Without it a run sets up, "
+                         "warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned to its "
+                         "caller as DIR/<name>.npy (float32 holding the 16-bit pieces of every "
+                         "word, exactly; prove: every lane's proof bytes; at most 64 MB in all, "
+                         "larger arrays as a fixed seeded sample of rows). Inputs are seeded: the "
+                         "same arguments give the same files")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="CPU baseline threads; 0 = OMP_NUM_THREADS if set (the GPU box's CPU "
                          "share per GPU), else every core in this process's affinity mask")
@@ -157,6 +175,41 @@ def rand_fr_dev(torch, n: int, seed: int, device):
     sys.path.insert(0, str(ROOT / "tests"))
     from oracle_lib import random_fr  # sampler only (numpy); no oracle arithmetic
     return torch.from_numpy(random_fr(n, seed).view(np.int64)).to(device)
+
+
+DUMP_BUDGET = 60_000_000  # bytes of .npy data one run may write (under 64 MB with the headers)
+DUMP_SAMPLE_SEED = 0xD0C5
+
+
+def dump_outputs(out_dir, arrays: dict, rank: int = 0, world: int = 1) -> dict:
+    """--dump-outputs: write each array (uint8 bytes or uint64 words, one row per element) as
+    <out_dir>/<name>.npy in float32, exactly: a byte as itself, a word as its four 16-bit
+    pieces, least significant first. The byte budget is shared evenly between the arrays (and
+    the ranks, whose files carry `_rank<r>` at world > 1); an array over its share is written
+    as a sample of its rows (fixed seed, ascending order: the same rows on every run)."""
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    share = DUMP_BUDGET // (max(1, len(arrays)) * max(1, world))
+    written = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        rows = a.reshape(a.shape[0] if a.ndim > 1 else 1, -1)
+        pieces = rows if rows.dtype == np.uint8 else rows.view(np.uint16)
+        keep = max(1, share // (4 * pieces.shape[1]))
+        if pieces.shape[0] > keep:
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(
+                pieces.shape[0], keep, replace=False))
+            pieces = pieces[idx]
+        f = d / (f"{name}.npy" if world == 1 else f"{name}_rank{rank}.npy")
+        np.save(f, pieces.astype(np.float32))
+        written[f.name] = list(pieces.shape)
+    return written
+
+
+def proof_outputs(lanes) -> dict:
+    """What the last timed step of the prove mode returned: every lane's proof (the plk_proof
+    struct's bytes, one row per lane, lane order)."""
+    return {"proofs": np.stack([np.frombuffer(ln.last[1], dtype=np.uint8) for ln in lanes])}
 
 
 class HotPath:
@@ -912,20 +965,26 @@ def run_full(args, plk, torch, dist, world, rank, device, k, n, shard):
         elapsed = max_over_ranks(torch, dist, elapsed, device)
     steps = args.steps
     lanes_all, lanes, L = lanes, active, L_run
-    # k_accumulate inside the workload (all lanes' launches; they share the chip) ...
+    if args.dump_outputs:  # the last timed step's proofs, before any lane proves again
+        dump_outputs(args.dump_outputs, proof_outputs(lanes), rank, world)
     acc_ms = launches = adds = points = 0
-    for ln in lanes:
-        m_, l_, a_, p_ = ln.lane.msm_stats(reset=True)
-        acc_ms, launches, adds, points = acc_ms + m_, launches + l_, adds + a_, points + p_
-    # ... and with the GPU to itself: one more proof on lane 0 after the timed region. The
-    # solo durations are the kernel's own (the in-workload ones overlap other lanes' kernels)
-    run(1, False, [lanes[0]])
-    torch.cuda.synchronize()
-    s_ms, s_l, s_a, s_p = lanes[0].lane.msm_stats(reset=True)
+    s_ms = s_l = s_a = s_p = 0
+    checked, mismatched = 0, []
+    if args.full:
+        # k_accumulate inside the workload (all lanes' launches; they share the chip) ...
+        for ln in lanes:
+            m_, l_, a_, p_ = ln.lane.msm_stats(reset=True)
+            acc_ms, launches, adds, points = acc_ms + m_, launches + l_, adds + a_, points + p_
+        # ... and with the GPU to itself: one more proof on lane 0 after the timed region. The
+        # solo durations are the kernel's own (the in-workload ones overlap other lanes' kernels)
+        run(1, False, [lanes[0]])
+        torch.cuda.synchronize()
+        s_ms, s_l, s_a, s_p = lanes[0].lane.msm_stats(reset=True)
     cbits = base.pp.last_msm_stats()[2]
-    # every lane's last timed proof, re-proved alone on lane 0 and compared byte for byte
-    # (under --shard-msm every rank re-proves the same seeds in the same order)
-    checked, mismatched = recheck_proofs(lanes, lanes[0])
+    if args.full:
+        # every lane's last timed proof, re-proved alone on lane 0 and compared byte for byte
+        # (under --shard-msm every rank re-proves the same seeds in the same order)
+        checked, mismatched = recheck_proofs(lanes, lanes[0])
     proofs = L if shard else L * world
     transforms = ("13 transforms (6 idft(n); 6 coset_dft and 1 coset_idft over the 6n quotient "
                   "domain, each as 3 coset blocks of 2n) + 11 MSMs")
@@ -969,21 +1028,24 @@ def run_full(args, plk, torch, dist, world, rank, device, k, n, shard):
             "synthesis_host_overlapped": 1e3 * sum(sum(ln.synth_s) for ln in lanes) / (steps * L),
             "prove_latency": 1e3 * sum(sum(ln.prove_s) for ln in lanes) / (steps * L),
         },
-        "proofs_checked": checked - len(mismatched),
-        "proofs_check": ("GPU against GPU: each lane's last timed proof re-proved alone on one "
-                         "lane after the timed region, byte-identical (catches races between "
-                         "concurrent lanes). The oracle check of this configuration (12 lanes "
-                         "at 2^20 against the committed C-oracle proof) is the -m gpu test "
-                         "tests/test_prover_lanes.py::test_twelve_lanes_2_20_concurrent_byte_exact"),
         "host_cores": {**hc, "lanes_requested": len(lanes_all), "lanes_run": L,
                        "note": "lanes x measured synthesis s / step s (warmup) per rank, against "
                                "that rank's own CPU share (cpu_share); ratio = the largest "
                                "need / share over the ranks; lanes are lowered only with "
                                "--fit-lanes"},
+        "full": bool(args.full),
     }
+    if args.full:
+        result["proofs_checked"] = checked - len(mismatched)
+        result["proofs_check"] = (
+            "GPU against GPU: each lane's last timed proof re-proved alone on one lane after "
+            "the timed region, byte-identical (catches races between concurrent lanes). The "
+            "oracle check of this configuration (12 lanes at 2^20 against the committed "
+            "C-oracle proof) is the -m gpu test "
+            "tests/test_prover_lanes.py::test_twelve_lanes_2_20_concurrent_byte_exact")
     # roofline of the dominant kernel (k_accumulate, ~60 % of a proof's GPU time) from its
     # solo launches; the in-workload averages beside them
-    if s_l and s_ms > 0:
+    if args.full and s_l and s_ms > 0:
         solo = acc_roofline(s_ms, s_l, s_a, s_p, "one proof with no other lane running, "
                             "dispatch-stamped events (outside the timed region)")
         inw = (acc_roofline(acc_ms, launches, adds, points, "all lanes inside the timed region; "
@@ -1032,7 +1094,7 @@ def run_full(args, plk, torch, dist, world, rank, device, k, n, shard):
             emit(result)
         raise SystemExit(f"bench.py: {len(mismatched)} of {checked} concurrent proofs differ "
                          f"from the same proof made alone (seeds {mismatched})")
-    if not args.no_extras and not shard:
+    if args.full and not args.no_extras and not shard:
         # after the timed region: the north star's MSM curve point (one 2^k MSM over all ranks)
         # and the metric's second size
         result["msm_shard"] = msm_shard_point(plk, torch, dist, world, rank, device, base.pp, k,
@@ -1044,11 +1106,11 @@ def run_full(args, plk, torch, dist, world, rank, device, k, n, shard):
             raise SystemExit("bench.py: the split MSM differs from the unsplit commit")
         if k != 16:
             result["n_2_16"] = run_second_size(args, plk, torch, dist, world, rank, device, 16)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline_full(
             k, base.pp, cpu_threads(args), gpu_value=result["value"],
             gpu_value_16=(result.get("n_2_16") or {}).get("value") if k != 16 else result["value"])
-    elif rank == 0 and world > 1:
+    elif args.full and rank == 0 and world > 1:
         result["cpu_baseline"] = stored_cpu_baseline(k, world, result["value"])
     if rank == 0:
         emit(result)
@@ -1244,8 +1306,13 @@ def run_kernel_mode(args, plk, torch, dist, world, rank, device, k, n):
                                    if (args.shard_msm and args.mode == "msm") else
                                    f"replicas x{world}")},
         "roofline": roof,
+        "full": bool(args.full),
     }
-    if args.mode == "msm" and args.shard_msm and world > 1:
+    if args.dump_outputs:  # the last timed step's results
+        out = ({"dft": y.cpu().numpy().view(np.uint64), "idft": z.cpu().numpy().view(np.uint64)}
+               if args.mode == "ntt" else {"commitment": coms[-1].words})
+        dump_outputs(args.dump_outputs, out, rank, world)
+    if args.full and args.mode == "msm" and args.shard_msm and world > 1:
         # the folded commitment against an unsplit commit of the same scalars on a whole SRS
         # (buckets: every rank's own; points: one built for the check), on every rank
         full = spp.local if spp.mode == "buckets" else plk.PlonkParams.setup(k, tau, ctx)
@@ -1259,7 +1326,7 @@ def run_kernel_mode(args, plk, torch, dist, world, rank, device, k, n):
             if rank == 0:
                 emit(result)
             raise SystemExit("bench.py: the split MSM's fold differs from the unsplit commit")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         threads = cpu_threads(args)
         sys.path.insert(0, str(ROOT / "tests"))
         import oracle_lib
@@ -1382,7 +1449,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        hp.step(timed=True)
+        last_coms = hp.step(timed=True)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -1436,6 +1503,7 @@ def main():
             "ntt_n_x11": t_ntt_n, "ntt_8n_x8": t_ntt_8n, "msm_accumulate_4_batches": t_acc,
             "other": ms_per_step - t_ntt_n - t_ntt_8n - t_acc,
         },
+        "full": bool(args.full),
     }
     if kname == "k_ntt_pass":  # the binding (Fr-multiply issue) roofline at top level
         k8 = k + 3
@@ -1457,7 +1525,10 @@ def main():
                      "point_adds_per_s": adds / (launch_ms * 1e-3),
                      "note": "integer-VALU-bound (no MFMA); HBM is the secondary roofline"})
         result["roofline"] = roof
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.dump_outputs:  # the last timed step's 11 commitments
+        dump_outputs(args.dump_outputs,
+                     {"commitments": np.stack([c.words for c in last_coms])}, rank, world)
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(k, hp.pp, cpu_threads(args))
     if rank == 0:
         emit(result)

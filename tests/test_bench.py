@@ -44,7 +44,8 @@ def test_cli_lists_modes():
     p = subprocess.run([sys.executable, "bench.py", "--help"], cwd=ROOT, capture_output=True,
                        text=True, timeout=60)
     assert p.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup", "--mode", "--lanes", "--dist-backend"):
+    for flag in ("--gpus", "--steps", "--warmup", "--mode", "--lanes", "--dist-backend", "--full",
+                 "--dump-outputs"):
         assert flag in p.stdout
     for mode in ("prove", "hotpath", "ntt", "msm"):
         assert mode in p.stdout
@@ -53,7 +54,7 @@ def test_cli_lists_modes():
 @pytest.mark.gpu
 @pytest.mark.parametrize("mode", ["ntt", "msm"])
 def test_kernel_mode_line_is_bit_exact(mode):
-    d = run_bench("--mode", mode, "--log-n", "12", "--steps", "3", "--warmup", "1",
+    d = run_bench("--full", "--mode", mode, "--log-n", "12", "--steps", "3", "--warmup", "1",
                   "--cpu-threads", "4")
     check_contract(d, 3, 1)
     assert d["unit"] == "points/s" and d["config"]["log_n"] == 12
@@ -66,12 +67,82 @@ def test_kernel_mode_line_is_bit_exact(mode):
 
 @pytest.mark.gpu
 def test_prove_mode_line():
-    d = run_bench("--log-n", "12", "--steps", "2", "--warmup", "1", "--lanes", "2",
+    d = run_bench("--full", "--log-n", "12", "--steps", "2", "--warmup", "1", "--lanes", "2",
                   "--no-cpu-baseline", "--no-extras")
     check_contract(d, 2, 1)
     assert d["unit"] == "constraints/s" and d["scaling"] == "weak"
     # value counts every lane's proof: n * steps * lanes / time
     assert d["value"] == pytest.approx(4096 * 2 * 2 / (d["ms_per_step"] * 2e-3), rel=1e-6)
+
+
+PLAIN = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step",
+         "higher_is_better", "dtype", "config", "build_id")
+FULL_ONLY = ("roofline", "proofs_checked", "msm_shard", "n_2_16", "cpu_baseline")
+
+
+@pytest.mark.gpu
+def test_plain_line_is_lean_and_dumps_its_last_proofs(plk, gpu_ctx, tmp_path):
+    """A plain run prints the headline line without anything that takes runs of its own, and
+    --dump-outputs writes the last timed step's proofs (float32, one row of struct bytes per
+    lane). The inputs are seeded, so the file is known in advance: lane l's last proof of 1
+    warmup + 3 timed steps is the bench circuit of seed 17 + 101 l + 4, proved here again."""
+    import numpy as np
+    sys.path.insert(0, str(ROOT))
+    import bench
+    d = run_bench("--log-n", "12", "--steps", "3", "--warmup", "1", "--lanes", "2",
+                  "--dump-outputs", str(tmp_path / "out"))
+    for k in PLAIN:
+        assert k in d, k
+    for k in FULL_ONLY:
+        assert k not in d, k
+    assert d["full"] is False and d["steps"] == 3 and d["warmup"] == 1
+    assert d["unit"] == "constraints/s" and d["higher_is_better"] is True
+    assert d["value"] == pytest.approx(4096 * 3 * 2 / (d["ms_per_step"] * 3e-3), rel=1e-6)
+    assert [p.name for p in (tmp_path / "out").iterdir()] == ["proofs.npy"]
+    got = np.load(tmp_path / "out" / "proofs.npy")
+    assert got.dtype == np.float32 and got.ndim == 2 and got.shape[0] == 2
+    base = bench.ProverBase(plk, 12, gpu_ctx)
+    lane = base.prover.lane()
+    try:
+        for l in range(2):
+            seed = 17 + 101 * l + 4
+            cs = bench.bench_circuit(base.Plonk, base.chain, seed)
+            want = np.frombuffer(lane.prove_composer(cs, seed)[0].raw_bytes(), dtype=np.uint8)
+            assert np.array_equal(got[l], want.astype(np.float32)), l
+    finally:
+        lane.close()
+
+
+def test_dump_outputs_exact_pieces_and_seeded_sample(tmp_path, monkeypatch):
+    """bench.dump_outputs: words as their four 16-bit pieces (exact in float32), bytes as
+    themselves, an array over its share of the budget as the same seeded rows every time."""
+    import numpy as np
+    sys.path.insert(0, str(ROOT))
+    import bench
+    w = np.array([[0xFFFF_0001_8000_7FFF, 1, 0, 2**64 - 1]] * 3, dtype=np.uint64)
+    w[1, 1] = 0xDEAD_BEEF_0BAD_F00D
+    by = np.arange(7, dtype=np.uint8).reshape(1, 7)
+    wrote = bench.dump_outputs(tmp_path / "x", {"words": w, "one": w[1], "bytes": by})
+    assert wrote == {"words.npy": [3, 16], "one.npy": [1, 16], "bytes.npy": [1, 7]}
+    got = np.load(tmp_path / "x" / "words.npy")
+    assert got.dtype == np.float32
+    assert np.array_equal(got.astype(np.uint16).view(np.uint64), w)
+    assert list(got[0, :4]) == [0x7FFF, 0x8000, 0x0001, 0xFFFF]
+    assert np.array_equal(np.load(tmp_path / "x" / "one.npy")[0], got[1])
+    assert np.array_equal(np.load(tmp_path / "x" / "bytes.npy"), by.astype(np.float32))
+    # over the budget: 2 arrays x 2 ranks share 4 KiB -> 1 KiB each = 16 rows of 16 float32
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 4096)
+    big = np.arange(4 * 100, dtype=np.uint64).reshape(100, 4)
+    for name in ("p", "q"):
+        wrote = bench.dump_outputs(tmp_path / name, {"big": big, "w": w}, rank=1, world=2)
+        assert wrote == {"big_rank1.npy": [16, 16], "w_rank1.npy": [3, 16]}
+    p, q = np.load(tmp_path / "p" / "big_rank1.npy"), np.load(tmp_path / "q" / "big_rank1.npy")
+    assert np.array_equal(p, q)
+    rows = p.astype(np.uint16).view(np.uint64)[:, 0] // 4
+    assert len(set(rows)) == 16 and list(rows) == sorted(rows)
+    assert np.array_equal(p.astype(np.uint16).view(np.uint64), big[rows.astype(int)])
+    total = sum(f.stat().st_size for f in (tmp_path / "p").iterdir())
+    assert total <= 4096 // 2 + 2 * 128  # this rank's half of the budget + the .npy headers
 
 
 def test_compiled_loop_mads():
@@ -115,7 +186,7 @@ def test_gpus_flag_must_match_launcher():
 
 @pytest.mark.gpu
 def test_prove_mode_line_has_solo_roofline():
-    d = run_bench("--log-n", "12", "--steps", "2", "--warmup", "1", "--lanes", "2",
+    d = run_bench("--full", "--log-n", "12", "--steps", "2", "--warmup", "1", "--lanes", "2",
                   "--no-cpu-baseline", "--no-extras")
     r = d["roofline"]
     assert r["kernel"] == "k_accumulate" and r["solo"]["launches"] == 4  # one proof
@@ -131,7 +202,7 @@ def test_prove_mode_line_has_solo_roofline():
 def test_gpus_2_shard_msm_launches_ranks_itself():
     """`bench.py --gpus 2 --shard-msm` without a launcher starts two ranks (here sharing the
     box's one GPU over gloo) and prints ONE full-proof line with n_gpus 2 (configs[4] form)."""
-    d = run_bench("--gpus", "2", "--shard-msm", "--dist-backend", "gloo", "--log-n", "12",
+    d = run_bench("--full", "--gpus", "2", "--shard-msm", "--dist-backend", "gloo", "--log-n", "12",
                   "--steps", "2", "--warmup", "1", "--lanes", "2", "--no-cpu-baseline",
                   timeout=300)
     check_contract(d, 2, 1, n_gpus=2)
@@ -144,7 +215,7 @@ def test_gpus_2_shard_msm_launches_ranks_itself():
 @pytest.mark.gpu
 def test_prove_mode_checks_its_proofs():
     """The prove line re-proves every lane's last timed proof alone and compares bytes."""
-    d = run_bench("--log-n", "12", "--steps", "2", "--warmup", "1", "--lanes", "3",
+    d = run_bench("--full", "--log-n", "12", "--steps", "2", "--warmup", "1", "--lanes", "3",
                   "--no-cpu-baseline", "--no-extras")
     assert d["proofs_checked"] == 3
     hc = d["host_cores"]
@@ -156,7 +227,7 @@ def test_prove_mode_checks_its_proofs():
 def test_shard_msm_world1_over_rccl():
     """`bench.py --shard-msm` at world 1 under nccl: the configs[4] form with its whole RCCL
     exchange on the one GPU (no launcher), one line, transport named."""
-    d = run_bench("--shard-msm", "--log-n", "12", "--steps", "2", "--warmup", "1", "--lanes",
+    d = run_bench("--full", "--shard-msm", "--log-n", "12", "--steps", "2", "--warmup", "1", "--lanes",
                   "2", "--no-cpu-baseline", timeout=200)
     check_contract(d, 2, 1)
     assert d["scaling"] == "strong" and "RCCL" in d["config"]["parallelism"]
@@ -220,7 +291,7 @@ def test_host_core_budget_per_rank_share_gloo_world2():
 def test_prove_line_world2_self_describing():
     """A multi-rank prove line (2 ranks sharing the card over gloo) carries every rank's
     roofline and the stored CPU baseline (bench.py stored_cpu_baseline), labelled as stored."""
-    d = run_bench("--gpus", "2", "--dist-backend", "gloo", "--log-n", "12", "--steps", "2",
+    d = run_bench("--full", "--gpus", "2", "--dist-backend", "gloo", "--log-n", "12", "--steps", "2",
                   "--warmup", "1", "--lanes", "2", "--no-cpu-baseline", "--no-extras", timeout=300)
     check_contract(d, 2, 1, n_gpus=2)
     cb = d["cpu_baseline"]
@@ -234,7 +305,7 @@ def test_prove_line_world2_self_describing():
 def test_msm_bucket_parts_line_is_bit_exact():
     """`--mode msm --bucket-parts 4`: the 2^16 MSM run as 4 bucket-range parts on one GPU (what
     each of 4 GPUs runs under --shard-msm), folded, checked against the oracle; per-part times."""
-    d = run_bench("--mode", "msm", "--log-n", "16", "--steps", "2", "--warmup", "1",
+    d = run_bench("--full", "--mode", "msm", "--log-n", "16", "--steps", "2", "--warmup", "1",
                   "--bucket-parts", "4", "--cpu-threads", "4")
     check_contract(d, 2, 1)
     assert d["bit_exact_vs_oracle"] is True
@@ -246,11 +317,11 @@ def test_msm_bucket_parts_line_is_bit_exact():
 def test_msm_split_over_ranks_lines():
     """`--mode msm --shard-msm`: ONE MSM per step split over the ranks by bucket range — at
     world 1 over RCCL (checked against the oracle) and on 2 gloo ranks sharing the card."""
-    d = run_bench("--mode", "msm", "--shard-msm", "--log-n", "16", "--steps", "2", "--warmup",
+    d = run_bench("--full", "--mode", "msm", "--shard-msm", "--log-n", "16", "--steps", "2", "--warmup",
                   "1", "--cpu-threads", "4")
     assert d["bit_exact_vs_oracle"] is True and d["scaling"] == "strong"
     assert d["config"]["parallelism"] == "msm-split x1 (buckets)"
-    d2 = run_bench("--gpus", "2", "--mode", "msm", "--shard-msm", "--dist-backend", "gloo",
+    d2 = run_bench("--full", "--gpus", "2", "--mode", "msm", "--shard-msm", "--dist-backend", "gloo",
                    "--log-n", "16", "--steps", "2", "--warmup", "1", timeout=300)
     assert d2["n_gpus"] == 2 and d2["scaling"] == "strong"
     assert d2["config"]["parallelism"] == "msm-split x2 (buckets)"
@@ -264,7 +335,7 @@ def test_msm_split_over_ranks_lines():
 def test_msm_split_points_over_ranks_line():
     """`--msm-split points` on 2 gloo ranks (round-5 advisor: each rank commits ITS span of the
     scalars against its SRS slice, not the whole vector), checked against an unsplit commit."""
-    d = run_bench("--gpus", "2", "--mode", "msm", "--shard-msm", "--msm-split", "points",
+    d = run_bench("--full", "--gpus", "2", "--mode", "msm", "--shard-msm", "--msm-split", "points",
                   "--dist-backend", "gloo", "--log-n", "16", "--steps", "2", "--warmup", "1",
                   timeout=300)
     assert d["n_gpus"] == 2 and d["config"]["parallelism"] == "msm-split x2 (points)"
@@ -353,7 +424,7 @@ def test_prove_line_extras_world1():
     """The default line's extras at world 1: msm_shard = the lone 2^k MSM (the curve's N = 1
     point) checked against the oracle; n_2_16 = the metric's second size, proofs re-checked;
     build_id = the library's source hash, equal to the tree's."""
-    d = run_bench("--log-n", "14", "--steps", "2", "--warmup", "1", "--lanes", "2",
+    d = run_bench("--full", "--log-n", "14", "--steps", "2", "--warmup", "1", "--lanes", "2",
                   "--no-cpu-baseline", timeout=300)
     m = d["msm_shard"]
     assert m["parts"] == 1 and m["bit_exact"] is True and "oracle" in m["check"]
@@ -367,7 +438,7 @@ def test_prove_line_extras_world1():
 def test_prove_line_msm_curve_world2():
     """At world 2 (two gloo ranks sharing the card) the line's msm_shard is ONE 2^16 MSM split
     by bucket range over both ranks, folded and checked against the unsplit commit."""
-    d = run_bench("--gpus", "2", "--dist-backend", "gloo", "--log-n", "16", "--steps", "2",
+    d = run_bench("--full", "--gpus", "2", "--dist-backend", "gloo", "--log-n", "16", "--steps", "2",
                   "--warmup", "1", "--lanes", "2", "--no-cpu-baseline", timeout=400)
     m = d["msm_shard"]
     assert m["parts"] == 2 and m["split"] == "bucket range" and m["bit_exact"] is True
@@ -378,7 +449,7 @@ def test_prove_line_msm_curve_world2():
 def test_gpus_2_shard_msm_bucket_split():
     """configs[4] with the bucket-range split (plk_prover_shard_buckets): 2^16 (c = 17, 2 parts
     of 2^15 buckets), two gloo ranks sharing the card, every lane's proof re-checked alone."""
-    d = run_bench("--gpus", "2", "--shard-msm", "--dist-backend", "gloo", "--log-n", "16",
+    d = run_bench("--full", "--gpus", "2", "--shard-msm", "--dist-backend", "gloo", "--log-n", "16",
                   "--steps", "2", "--warmup", "1", "--lanes", "2", "--no-cpu-baseline",
                   timeout=400)
     check_contract(d, 2, 1, n_gpus=2)

@@ -8,7 +8,7 @@ the per-experiment tools/gpu_r0*.sh scripts).
       [--env KEY=VALUE ...] [--tests tests/test_msm_gpu.py]
 
 For every repetition, every args set and every variant (in that nesting, so the variants of
-one setting run back to back) it runs `python bench.py <args> --warmup W --no-cpu-baseline`
+one setting run back to back) it runs `python bench.py <args> --warmup W --full --no-cpu-baseline`
 with PLK_LIB pointing at dusk-plonk_amd/<lib>, under its own timeout, and appends one JSON
 line: tag, args, value, ms_per_step, the roofline's point_adds_per_s / frac, proofs checked.
 --tests first runs the given -m gpu test files once per variant (parity before timing).
@@ -72,7 +72,7 @@ def main() -> int:
         for args in a.args:
             for tag, ve in variants:
                 cmd = [sys.executable, "bench.py", *args.split(), "--warmup", str(a.warmup),
-                       "--no-cpu-baseline", "--no-extras"]
+                       "--full", "--no-cpu-baseline", "--no-extras"]
                 r = subprocess.run(["timeout", "-k", "10", str(a.timeout), *cmd], cwd=ROOT,
                                    env={**base_env, **ve}, capture_output=True, text=True)
                 if r.returncode != 0:

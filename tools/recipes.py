@@ -94,7 +94,7 @@ def r_refresh(o, a):
     2^20 and 2^16 proof traces for the per-kernel breakdown."""
     tests(o, "tests", 1100)
     smoke(o)
-    bench(o, "bench_default", "--steps 20 --warmup 5", 600)
+    bench(o, "bench_default", "--full --steps 20 --warmup 5", 600)
     trace(o, "prof", "--no-cpu-baseline --no-extras")
     pmc(o, "pmc", "FETCH_SIZE;WRITE_SIZE", "--no-cpu-baseline --no-extras")
     tool(o, "pmc_summary.txt", "tools/pmc_summary.py", str(o / "pmc"), str(o / "pmc_traffic.json"))
@@ -118,7 +118,7 @@ def r_configs(o, a):
         d["units"] = (10 + 2) * (2 if m == "ntt" else 1)
         out.write_text(json.dumps(d, indent=1, sort_keys=True))
     for m, k in (("ntt", 20), ("msm", 20), ("ntt", 23), ("msm", 16)):
-        bench(o, "lines", f"--mode {m} --log-n {k} --steps 10 --warmup 2", 300, append=True)
+        bench(o, "lines", f"--mode {m} --log-n {k} --steps 10 --warmup 2 --full", 300, append=True)
     bench(o, "lines", "--mode msm --log-n 20 --steps 20 --warmup 3 --no-cpu-baseline --bucket-parts 8",
           300, append=True)
 
@@ -127,8 +127,8 @@ def r_sizes(o, a):
     """Constraints/s at 2^12 .. 2^20 (round 5's gpu_r05_l / gpu_size_sweep.sh), default lanes,
     every lane's last proof re-proved and byte-compared."""
     for k in a.sizes.split():
-        bench(o, "sizes", f"--log-n {k} --steps 10 --warmup 3 --no-cpu-baseline --no-extras", 400,
-              append=True)
+        bench(o, "sizes", f"--log-n {k} --steps 10 --warmup 3 --full --no-cpu-baseline --no-extras",
+              400, append=True)
 
 
 def r_parts(o, a):
@@ -177,7 +177,7 @@ def r_check(o, a):
              "tests/test_parallel.py::test_sharded_prover_bucket_split "
              "tests/test_parallel.py::test_sharded_prover_bucket_split_refused_small_srs "
              "tests/test_parallel.py::test_sharded_prover_2_20_bucket_split_equals_fixture", 900)
-    bench(o, "bench_default", "--steps 20 --warmup 5", 600)
+    bench(o, "bench_default", "--full --steps 20 --warmup 5", 600)
 
 
 def r_shardprobe(o, a):
