@@ -1,6 +1,9 @@
-// debug.hip — plk_debug_field_op: elementwise device field arithmetic for parity tests.
+// debug.hip — test hooks: elementwise device arithmetic on host arrays for the parity tests.
+// plk_debug_field_op: the packed field of ff.hpp; plk_debug_rx_op: the redundant-limb field of
+// ffr.hpp on raw limb rows; plk_debug_g1r_op: the XYZZ group law of g1r.hpp on raw limb rows.
 #include <hip/hip_runtime.h>
 
+#include "g1r.hpp"
 #include "internal.hpp"
 
 namespace plk {
@@ -40,8 +43,285 @@ int run(plk_ctx* ctx, int op, const uint64_t* a, const uint64_t* b, uint64_t* ou
   return PLK_OK;
 }
 
+// ---- plk_debug_rx_op: ffr.hpp on raw limb rows ------------------------------------------
+// One kernel instantiation per op (the op is a template argument: a run-time switch over
+// values of this size is merged through a scratch object, ntt.hip r4_math). Op codes as in
+// include/plk.h; 100 + CP: rx_sub_u<CP>, 200 + CP: rx_sub_n<CP>.
+enum : int {
+  kOpMul = 0, kOpSqr, kOpMulAdd, kOpMul2, kOpMul2Asm, kOpSqr2, kOpSqr2Asm, kOpMulAddMul2,
+  kOpMulAddMul2Asm, kOpMul3, kOpAdd, kOpSub, kOpSubLazy, kOpSub2N6, kOpSmall2, kOpSmall3,
+  kOpCanon, kOpIsZero, kOpIsZeroU, kOpUnpackPack, kOpSubU = 100, kOpSubN = 200
+};
+
+constexpr int rx_op_nin(int op) {
+  if (op >= kOpSubU) return 2;
+  switch (op) {
+    case kOpSqr: case kOpSmall2: case kOpSmall3: case kOpCanon: case kOpIsZero: case kOpIsZeroU:
+    case kOpUnpackPack: return 1;
+    case kOpMul: case kOpSqr2: case kOpSqr2Asm: case kOpAdd: case kOpSub: case kOpSubLazy: return 2;
+    case kOpSub2N6: return 3;
+    default: return 4;
+  }
+}
+constexpr int rx_op_nout(int op) {
+  switch (op) {
+    case kOpMul2: case kOpMul2Asm: case kOpSqr2: case kOpSqr2Asm: case kOpUnpackPack: return 2;
+    case kOpMulAddMul2: case kOpMulAddMul2Asm: case kOpMul3: return 3;
+    default: return 1;
+  }
+}
+
+template <class C>
+__device__ __forceinline__ Rx<C> ld_row(const uint32_t* __restrict__ p, uint64_t i) {
+  Rx<C> r;
+#pragma unroll
+  for (int k = 0; k < RxShape<C>::L; ++k) r.v[k] = p[i * RxShape<C>::L + k];
+  return r;
+}
+template <class C>
+__device__ __forceinline__ void st_row(uint32_t* __restrict__ p, uint64_t i, const Rx<C>& r) {
+#pragma unroll
+  for (int k = 0; k < RxShape<C>::L; ++k) p[i * RxShape<C>::L + k] = r.v[k];
+}
+template <class C>
+__device__ __forceinline__ Rx<C> rx_flag(bool f) {
+  Rx<C> r = rx_zero<C>();
+  r.v[0] = f ? 1u : 0u;
+  return r;
+}
+
+template <class C, int OP>
+__global__ void __launch_bounds__(256)
+    k_rx_op(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b,
+            const uint32_t* __restrict__ c, const uint32_t* __restrict__ d,
+            uint32_t* __restrict__ out, uint64_t n) {
+  constexpr int NIN = rx_op_nin(OP), NOUT = rx_op_nout(OP);
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const Rx<C> x0 = ld_row<C>(a, i);
+  const Rx<C> x1 = NIN > 1 ? ld_row<C>(b, i) : rx_zero<C>();
+  const Rx<C> x2 = NIN > 2 ? ld_row<C>(c, i) : rx_zero<C>();
+  const Rx<C> x3 = NIN > 3 ? ld_row<C>(d, i) : rx_zero<C>();
+  Rx<C> o0 = rx_zero<C>(), o1 = rx_zero<C>(), o2 = rx_zero<C>();
+  if constexpr (OP == kOpMul) o0 = rx_mul(x0, x1);
+  else if constexpr (OP == kOpSqr) o0 = rx_sqr(x0);
+  else if constexpr (OP == kOpMulAdd) o0 = rx_mul_add(x0, x1, x2, x3);
+  else if constexpr (OP == kOpMul2) rx_mul2<C, false>(x0, x1, x2, x3, o0, o1);
+  else if constexpr (OP == kOpMul2Asm) rx_mul2<C, true>(x0, x1, x2, x3, o0, o1);
+  else if constexpr (OP == kOpSqr2) rx_sqr2<C, false>(x0, x1, o0, o1);
+  else if constexpr (OP == kOpSqr2Asm) rx_sqr2<C, true>(x0, x1, o0, o1);
+  else if constexpr (OP == kOpMulAddMul2) rx_mul_add_mul2<C, false>(x0, x1, x2, x3, x0, x3, x2, x1, o0, o1, o2);
+  else if constexpr (OP == kOpMulAddMul2Asm) rx_mul_add_mul2<C, true>(x0, x1, x2, x3, x0, x3, x2, x1, o0, o1, o2);
+  else if constexpr (OP == kOpMul3) rx_mul3<C>(x0, x1, x2, x3, x3, x0, o0, o1, o2);
+  else if constexpr (OP == kOpAdd) o0 = rx_add(x0, x1);
+  else if constexpr (OP == kOpSub) o0 = rx_sub(x0, x1);
+  else if constexpr (OP == kOpSubLazy) o0 = rx_sub_lazy(x0, x1);
+  else if constexpr (OP == kOpSub2N6) o0 = rx_sub2_n<C, 6>(x0, x1, x2);
+  else if constexpr (OP == kOpSmall2) o0 = rx_small_mul_n<C, 2>(x0);
+  else if constexpr (OP == kOpSmall3) o0 = rx_small_mul_n<C, 3>(x0);
+  else if constexpr (OP == kOpCanon) o0 = rx_canon(x0);
+  else if constexpr (OP == kOpIsZero) o0 = rx_flag<C>(rx_is_zero(x0));
+  else if constexpr (OP == kOpIsZeroU) o0 = rx_flag<C>(rx_is_zero_u(x0));
+  else if constexpr (OP == kOpUnpackPack) {
+    Fe<C> w;
+#pragma unroll
+    for (int k = 0; k < C::N; ++k) w.v[k] = x0.v[k];
+    o0 = rx_unpack(w);
+    w = rx_pack(o0);
+#pragma unroll
+    for (int k = 0; k < C::N; ++k) o1.v[k] = w.v[k];
+  } else if constexpr (OP >= kOpSubN) o0 = rx_sub_n<C, OP - kOpSubN>(x0, x1);
+  else o0 = rx_sub_u<C, OP - kOpSubU>(x0, x1);
+  st_row<C>(out, i * NOUT, o0);
+  if constexpr (NOUT > 1) st_row<C>(out, i * NOUT + 1, o1);
+  if constexpr (NOUT > 2) st_row<C>(out, i * NOUT + 2, o2);
+}
+
+using RxKernel = void (*)(const uint32_t*, const uint32_t*, const uint32_t*, const uint32_t*,
+                          uint32_t*, uint64_t);
+#define PLK_RX_CASE(C, OP) \
+  case OP: return k_rx_op<C, OP>;
+#define PLK_RX_COMMON(C)                                                                       \
+  PLK_RX_CASE(C, kOpMul) PLK_RX_CASE(C, kOpSqr) PLK_RX_CASE(C, kOpMulAdd) PLK_RX_CASE(C, kOpMul2) \
+  PLK_RX_CASE(C, kOpMul2Asm) PLK_RX_CASE(C, kOpSqr2) PLK_RX_CASE(C, kOpMulAddMul2)             \
+  PLK_RX_CASE(C, kOpMul3) PLK_RX_CASE(C, kOpAdd) PLK_RX_CASE(C, kOpSub) PLK_RX_CASE(C, kOpSubLazy) \
+  PLK_RX_CASE(C, kOpSub2N6) PLK_RX_CASE(C, kOpSmall2) PLK_RX_CASE(C, kOpSmall3)                \
+  PLK_RX_CASE(C, kOpCanon) PLK_RX_CASE(C, kOpIsZero) PLK_RX_CASE(C, kOpIsZeroU)                \
+  PLK_RX_CASE(C, kOpUnpackPack) PLK_RX_CASE(C, kOpSubU + 3) PLK_RX_CASE(C, kOpSubU + 5)        \
+  PLK_RX_CASE(C, kOpSubU + 6) PLK_RX_CASE(C, kOpSubN + 3) PLK_RX_CASE(C, kOpSubN + 5)          \
+  PLK_RX_CASE(C, kOpSubN + 6)
+RxKernel rx_kernel(int field, int op) {
+  if (field == 0) {
+    switch (op) {
+      PLK_RX_COMMON(FrCfg)
+      default: return nullptr;
+    }
+  }
+  switch (op) {
+    PLK_RX_COMMON(FpCfg)
+    PLK_RX_CASE(FpCfg, kOpSqr2Asm) PLK_RX_CASE(FpCfg, kOpMulAddMul2Asm)
+    PLK_RX_CASE(FpCfg, kOpSubU + 4) PLK_RX_CASE(FpCfg, kOpSubU + 10)
+    PLK_RX_CASE(FpCfg, kOpSubN + 4) PLK_RX_CASE(FpCfg, kOpSubN + 10)
+    default: return nullptr;
+  }
+}
+#undef PLK_RX_COMMON
+#undef PLK_RX_CASE
+
+// ---- plk_debug_g1r_op: g1r.hpp on raw XYZZ limb rows -------------------------------------
+enum : int {
+  kG1Madd000 = 0, kG1Madd100, kG1Madd110, kG1Madd111, kG1MaddLazy, kG1AddLazy, kG1AddQuad,
+  kG1DblLazy, kG1LazyFinish, kG1Add, kG1AddAffine, kG1Dbl, kG1DblAffine, kG1OpCount
+};
+constexpr int kG1Row = 4 * RxShape<FpCfg>::L;
+constexpr bool g1_op_needs_q(int op) {
+  return !(op == kG1DblLazy || op == kG1LazyFinish || op == kG1Dbl || op == kG1DblAffine);
+}
+
+__device__ __forceinline__ G1R ld_g1row(const uint32_t* __restrict__ p, uint64_t i) {
+  G1R r;
+  r.X = ld_row<FpCfg>(p, 4 * i);
+  r.Y = ld_row<FpCfg>(p, 4 * i + 1);
+  r.ZZ = ld_row<FpCfg>(p, 4 * i + 2);
+  r.ZZZ = ld_row<FpCfg>(p, 4 * i + 3);
+  return r;
+}
+
+// k_accumulate's sequence around the straight-line mixed addition (msm_acc.hip)
+template <bool GROUPED, bool ASM, bool PAIRS>
+__device__ __forceinline__ G1R madd_as_accumulate(const G1R& acc, const G1R& q, bool neg) {
+  RFp y = q.Y;
+  if (neg) y = rx_neg_lazy(y);
+  const bool was_inf = g1r_is_inf(acc);
+  G1R r = g1r_madd_lazy_sl<GROUPED, ASM, PAIRS>(acc, q.X, y);
+  if (rx_is_zero(r.ZZ)) {
+    RFp yr = q.Y;
+    if (neg) yr = rx_neg(yr);
+    r = g1r_madd_lazy_fix(was_inf, r, q.X, yr);
+  }
+  return r;
+}
+
+template <int OP>
+__global__ void __launch_bounds__(256)
+    k_g1r_op(const uint32_t* __restrict__ p, const uint32_t* __restrict__ q,
+             const uint32_t* __restrict__ flags, uint32_t* __restrict__ out, uint64_t n) {
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t i = OP == kG1AddQuad ? t >> 2 : t;  // a quad shares one row: uniform per quad
+  if (i >= n) return;
+  const G1R a = ld_g1row(p, i);
+  G1R b = g1_op_needs_q(OP) ? ld_g1row(q, i) : a;
+  const bool neg = g1_op_needs_q(OP) && flags && (flags[i] & 1u);
+  G1R r;
+  if constexpr (OP == kG1Madd000) r = madd_as_accumulate<false, false, false>(a, b, neg);
+  else if constexpr (OP == kG1Madd100) r = madd_as_accumulate<true, false, false>(a, b, neg);
+  else if constexpr (OP == kG1Madd110) r = madd_as_accumulate<true, true, false>(a, b, neg);
+  else if constexpr (OP == kG1Madd111) r = madd_as_accumulate<true, true, true>(a, b, neg);
+  else if constexpr (OP == kG1MaddLazy) r = g1r_madd_lazy(a, b.X, neg ? rx_neg_lazy(b.Y) : b.Y);
+  else if constexpr (OP == kG1AddLazy || OP == kG1AddQuad) {
+    if (neg) b.Y = rx_neg_lazy(b.Y);  // 4p - Y, normalised
+    if constexpr (OP == kG1AddLazy) r = g1r_add_lazy(a, b);
+    else r = g1r_add_quad(a, b, threadIdx.x & 3u);
+  } else if constexpr (OP == kG1DblLazy) r = g1r_dbl_lazy(a);
+  else if constexpr (OP == kG1LazyFinish) r = g1r_lazy_finish(a);
+  else if constexpr (OP == kG1Add) r = g1r_add(a, neg ? g1r_neg(b) : b);
+  else if constexpr (OP == kG1AddAffine) r = g1r_add_affine(a, b.X, neg ? rx_neg(b.Y) : b.Y);
+  else if constexpr (OP == kG1Dbl) r = g1r_dbl(a);
+  else r = g1r_dbl_affine(a.X, a.Y);
+  st_row<FpCfg>(out, 4 * t, r.X);
+  st_row<FpCfg>(out, 4 * t + 1, r.Y);
+  st_row<FpCfg>(out, 4 * t + 2, r.ZZ);
+  st_row<FpCfg>(out, 4 * t + 3, r.ZZZ);
+}
+
+using G1Kernel = void (*)(const uint32_t*, const uint32_t*, const uint32_t*, uint32_t*, uint64_t);
+G1Kernel g1r_kernel(int op) {
+  switch (op) {
+#define PLK_G1_CASE(OP) \
+  case OP: return k_g1r_op<OP>;
+    PLK_G1_CASE(kG1Madd000) PLK_G1_CASE(kG1Madd100) PLK_G1_CASE(kG1Madd110)
+    PLK_G1_CASE(kG1Madd111) PLK_G1_CASE(kG1MaddLazy) PLK_G1_CASE(kG1AddLazy)
+    PLK_G1_CASE(kG1AddQuad) PLK_G1_CASE(kG1DblLazy) PLK_G1_CASE(kG1LazyFinish)
+    PLK_G1_CASE(kG1Add) PLK_G1_CASE(kG1AddAffine) PLK_G1_CASE(kG1Dbl) PLK_G1_CASE(kG1DblAffine)
+#undef PLK_G1_CASE
+    default: return nullptr;
+  }
+}
+
+// host arrays of uint32 rows in, one launch of `threads` threads, rows out
+struct RowArg {
+  const uint32_t* host;
+  size_t bytes;
+};
+template <class K, size_t NA>
+int run_rows(plk_ctx* ctx, K kern, const RowArg (&in)[NA], uint32_t* out, size_t out_bytes,
+             uint64_t threads, uint64_t n) {
+  DevBuf din[NA], dout;
+  int st;
+  hipStream_t s = ctx->stream;
+  for (size_t k = 0; k < NA; ++k) {
+    if (!in[k].host) continue;
+    if ((st = din[k].alloc(in[k].bytes))) return st;
+    PLK_HIP_TRY(hipMemcpyAsync(din[k].ptr, in[k].host, in[k].bytes, hipMemcpyHostToDevice, s));
+  }
+  if ((st = dout.alloc(out_bytes))) return st;
+  const dim3 grid((unsigned)((threads + 255) / 256)), block(256);
+  const uint32_t* dp[NA];
+  for (size_t k = 0; k < NA; ++k) dp[k] = static_cast<const uint32_t*>(din[k].ptr);
+  uint32_t* const dres = static_cast<uint32_t*>(dout.ptr);
+  if constexpr (NA == 4)
+    hipLaunchKernelGGL(kern, grid, block, 0, s, dp[0], dp[1], dp[2], dp[3], dres, n);
+  else
+    hipLaunchKernelGGL(kern, grid, block, 0, s, dp[0], dp[1], dp[2], dres, n);
+  PLK_HIP_TRY(hipGetLastError());
+  PLK_HIP_TRY(hipMemcpyAsync(out, dout.ptr, out_bytes, hipMemcpyDeviceToHost, s));
+  PLK_HIP_TRY(stream_wait(s));
+  return PLK_OK;
+}
+
 }  // namespace
 }  // namespace plk
+
+extern "C" int plk_debug_rx_op(plk_ctx* ctx, int field, int op, const uint32_t* a,
+                               const uint32_t* b, const uint32_t* c, const uint32_t* d,
+                               uint32_t* out, size_t n) {
+  try {
+    if (!ctx || !out || (field != 0 && field != 1)) return PLK_E_ARG;
+    const plk::RxKernel kern = plk::rx_kernel(field, op);
+    if (!kern) return PLK_E_ARG;
+    const uint32_t* rows[4] = {a, b, c, d};
+    const int nin = plk::rx_op_nin(op);
+    for (int k = 0; k < nin; ++k)
+      if (!rows[k]) return PLK_E_ARG;
+    if (n == 0) return PLK_OK;
+    const size_t row = (field == 0 ? 9 : 13) * sizeof(uint32_t);
+    plk::RowArg in[4];
+    for (int k = 0; k < 4; ++k) in[k] = {k < nin ? rows[k] : nullptr, n * row};
+    plk::DeviceGuard g(ctx->device);
+    return plk::run_rows(ctx, kern, in, out, n * row * plk::rx_op_nout(op), n, n);
+  } catch (...) {
+    return PLK_E_DEVICE;
+  }
+}
+
+extern "C" int plk_debug_g1r_op(plk_ctx* ctx, int op, const uint32_t* p, const uint32_t* q,
+                                const uint32_t* flags, uint32_t* out, size_t n) {
+  try {
+    if (!ctx || !p || !out) return PLK_E_ARG;
+    const plk::G1Kernel kern = plk::g1r_kernel(op);
+    if (!kern || (plk::g1_op_needs_q(op) && !q)) return PLK_E_ARG;
+    if (n == 0) return PLK_OK;
+    const size_t row = plk::kG1Row * sizeof(uint32_t);
+    const uint64_t threads = op == plk::kG1AddQuad ? 4 * (uint64_t)n : n;
+    const plk::RowArg in[3] = {{p, n * row},
+                               {plk::g1_op_needs_q(op) ? q : nullptr, n * row},
+                               {flags, n * sizeof(uint32_t)}};
+    plk::DeviceGuard g(ctx->device);
+    return plk::run_rows(ctx, kern, in, out, threads * row, threads, n);
+  } catch (...) {
+    return PLK_E_DEVICE;
+  }
+}
 
 extern "C" int plk_debug_field_op(plk_ctx* ctx, int field, int op, const uint64_t* a,
                                   const uint64_t* b, uint64_t* out, size_t n) {

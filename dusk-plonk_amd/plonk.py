@@ -39,7 +39,8 @@ ABI_SYMBOLS = (
     "plk_domain_info", "plk_domain_elements", "plk_domain_vanishing_over_coset", "plk_ntt",
     "plk_ntt_dev", "plk_ntt_batch_dev", "plk_srs_setup", "plk_srs_load", "plk_srs_destroy",
     "plk_srs_len", "plk_srs_points", "plk_msm", "plk_commit", "plk_commit_dev",
-    "plk_srs_last_msm_stats", "plk_debug_field_op", "plk_commit_batch_dev",
+    "plk_srs_last_msm_stats", "plk_debug_field_op", "plk_debug_rx_op", "plk_debug_g1r_op",
+    "plk_commit_batch_dev",
     "plk_commit_batch_dev_part",
     "plk_srs_setup_range", "plk_g1_sum", "plk_msm_sharded", "plk_srs_msm_stats_reset",
     "plk_srs_cum_msm_stats", "plk_ntt_stream", "plk_aggregate_witness",
@@ -115,6 +116,8 @@ def _lib():
             "plk_srs_last_msm_stats": (i32, [vp, C.POINTER(C.c_float), C.POINTER(u64),
                                              C.POINTER(u32)]),
             "plk_debug_field_op": (i32, [vp, i32, i32, vp, vp, vp, sz]),
+            "plk_debug_rx_op": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, sz]),
+            "plk_debug_g1r_op": (i32, [vp, i32, vp, vp, vp, vp, sz]),
             "plk_commit_batch_dev": (i32, [vp, vp, vp, sz, vp, vp, vp]),
             "plk_commit_batch_dev_part": (i32, [vp, vp, vp, sz, u32, u32, vp, vp, vp]),
             "plk_srs_setup_range": (i32, [vp, vp, u64, sz, vp, pp]),
@@ -224,6 +227,54 @@ class Context:
         _check(_lib().plk_debug_field_op(self.handle, 0 if field == "fr" else 1, code, _ptr(a),
                                          None if bb is None else _ptr(bb), _ptr(out), a.shape[0]),
                "plk_debug_field_op")
+        return out
+
+    # op -> (code, operand rows, output rows) of plk_debug_rx_op (include/plk.h)
+    RX_OPS = {"mul": (0, 2, 1), "sqr": (1, 1, 1), "mul_add": (2, 4, 1), "mul2": (3, 4, 2),
+              "mul2_asm": (4, 4, 2), "sqr2": (5, 2, 2), "sqr2_asm": (6, 2, 2),
+              "mul_add_mul2": (7, 4, 3), "mul_add_mul2_asm": (8, 4, 3), "mul3": (9, 4, 3),
+              "add": (10, 2, 1), "sub": (11, 2, 1), "sub_lazy": (12, 2, 1), "sub2_n6": (13, 3, 1),
+              "small_mul2": (14, 1, 1), "small_mul3": (15, 1, 1), "canon": (16, 1, 1),
+              "is_zero": (17, 1, 1), "is_zero_u": (18, 1, 1), "unpack_pack": (19, 1, 2),
+              "sub_u": (100, 2, 1), "sub_n": (200, 2, 1)}
+    G1R_OPS = {"madd_000": 0, "madd_100": 1, "madd_110": 2, "madd_111": 3, "madd_lazy": 4,
+               "add_lazy": 5, "add_quad": 6, "dbl_lazy": 7, "lazy_finish": 8, "add": 9,
+               "add_affine": 10, "dbl": 11, "dbl_affine": 12}
+
+    def rx_op(self, field: str, op: str, *rows, cp: int = 0) -> np.ndarray:
+        """The redundant-limb field (csrc/ffr.hpp) on raw uint32 limb rows (test support):
+        field 'fr' (9 limbs) | 'fp' (13), op a key of RX_OPS ('sub_u' / 'sub_n' take cp);
+        returns [n, outputs, limbs]."""
+        L = 9 if field == "fr" else 13
+        code, nin, nout = self.RX_OPS[op]
+        if len(rows) != nin:
+            raise ValueError(f"rx_op {op} takes {nin} operand arrays")
+        ops = [np.ascontiguousarray(np.asarray(r, dtype=np.uint32).reshape(-1, L)) for r in rows]
+        n = ops[0].shape[0]
+        if any(o.shape[0] != n for o in ops):
+            raise ValueError("rx_op operands differ in length")
+        out = np.zeros((n, nout, L), dtype=np.uint32)
+        ptrs = [_ptr(o) for o in ops] + [None] * (4 - nin)
+        _check(_lib().plk_debug_rx_op(self.handle, 0 if field == "fr" else 1, code + cp, *ptrs,
+                                      _ptr(out), n), "plk_debug_rx_op")
+        return out
+
+    def g1r_op(self, op: str, p, q=None, flags=None) -> np.ndarray:
+        """The XYZZ group law (csrc/g1r.hpp) on raw rows of 4 x 13 uint32 limbs (test support):
+        op a key of G1R_OPS; returns [n, 4, 13], for 'add_quad' [n, 4 lanes, 4, 13]."""
+        p = np.ascontiguousarray(np.asarray(p, dtype=np.uint32).reshape(-1, 4, 13))
+        n = p.shape[0]
+        if q is not None:
+            q = np.ascontiguousarray(np.asarray(q, dtype=np.uint32).reshape(-1, 4, 13))
+        if flags is not None:
+            flags = np.ascontiguousarray(np.asarray(flags, dtype=np.uint32).reshape(-1))
+        if any(x is not None and x.shape[0] != n for x in (q, flags)):
+            raise ValueError("g1r_op operands differ in length")
+        out = np.zeros((n, 4, 4, 13) if op == "add_quad" else (n, 4, 13), dtype=np.uint32)
+        _check(_lib().plk_debug_g1r_op(self.handle, self.G1R_OPS[op], _ptr(p),
+                                       None if q is None else _ptr(q),
+                                       None if flags is None else _ptr(flags), _ptr(out), n),
+               "plk_debug_g1r_op")
         return out
 
     def domain(self, k: int) -> C.c_void_p:

@@ -355,6 +355,40 @@ int plk_proof_decode(const uint8_t* in, size_t len, plk_proof* proof);
  * op 0 = a*b, 1 = a+b, 2 = a-b, 3 = a^2, 4 = a^-1 (Montgomery form in and out). */
 int plk_debug_field_op(plk_ctx* ctx, int field, int op, const uint64_t* a, const uint64_t* b,
                        uint64_t* out, size_t n);
+/* The redundant-limb field of the hot loops (csrc/ffr.hpp) on raw limb rows: field 0 = Fr
+ * (L = 9 limbs of 29 bits), 1 = Fp (L = 13 limbs of 30 bits). Operands a, b, c, d are n rows of L
+ * uint32 limbs each; a thread copies its rows into Rx values unchanged (nothing is unpacked,
+ * reduced or normalised) and writes each result's limbs back raw: out holds n x (outputs of the
+ * op) rows, row i * outputs + j = output j of input row i. Operands an op does not read may be
+ * NULL. Ops (outputs; (A) marks the form with its columns as inline-asm statements):
+ *    0 rx_mul a b                  1 rx_sqr a                 2 rx_mul_add a b + c d
+ *    3 rx_mul2 (a b, c d)          4 rx_mul2 (A)              5 rx_sqr2 (a^2, b^2)
+ *    6 rx_sqr2 (A), Fp only        7 rx_mul_add_mul2 (a b + c d, a d, c b)
+ *    8 rx_mul_add_mul2 (A), Fp only                           9 rx_mul3 (a b, c d, d a)
+ *   10 rx_add a + b               11 rx_sub a - b            12 rx_sub_lazy a - b
+ *   13 rx_sub2_n<6> a + 6p - b - 2c                          14, 15 rx_small_mul_n<2>, <3> a
+ *   16 rx_canon a                 17 rx_is_zero a            18 rx_is_zero_u a
+ *   19 (rx_unpack a, rx_pack of that): a's first 8 (Fr) / 12 (Fp) words are a packed value;
+ *      output 0 its limbs, output 1 the words packed back (the rest of the row 0)
+ *   100 + CP rx_sub_u<CP> a + CP p - b, 200 + CP rx_sub_n<CP>: CP in 3, 5, 6 and for Fp 4, 10
+ * The two tests write 0 / 1 into limb 0 of an otherwise zero row. Other codes: PLK_E_ARG. */
+int plk_debug_rx_op(plk_ctx* ctx, int field, int op, const uint32_t* a, const uint32_t* b,
+                    const uint32_t* c, const uint32_t* d, uint32_t* out, size_t n);
+/* The XYZZ group law over that field (csrc/g1r.hpp) on raw limb rows: p, q and out are rows of
+ * 4 x 13 limbs (X, Y, ZZ, ZZZ; R' = 2^390 domain), an affine q uses X and Y only. Bit 0 of
+ * flags[i] (flags may be NULL) negates q: the lazy 4p - Y (rx_neg_lazy) for the lazy ops,
+ * rx_neg for the others. Ops:
+ *    0..3 g1r_madd_lazy_sl<GROUPED, ASM, PAIRS> as (0,0,0), (1,0,0), (1,1,0), (1,1,1), in the
+ *         sequence of k_accumulate: the flag's rx_neg_lazy, the straight-line addition, and on a
+ *         zero ZZ g1r_madd_lazy_fix with the canonical (negated) point
+ *    4 g1r_madd_lazy      5 g1r_add_lazy
+ *    6 g1r_add_quad: every row runs on the four lanes of a quad and out holds 4 n rows, row
+ *      4 i + l = lane l's result
+ *    7 g1r_dbl_lazy p     8 g1r_lazy_finish p        9 g1r_add        10 g1r_add_affine
+ *   11 g1r_dbl p         12 g1r_dbl_affine of (p.X, p.Y)
+ * q may be NULL for the ops of p alone. */
+int plk_debug_g1r_op(plk_ctx* ctx, int op, const uint32_t* p, const uint32_t* q,
+                     const uint32_t* flags, uint32_t* out, size_t n);
 
 #ifdef __cplusplus
 }
