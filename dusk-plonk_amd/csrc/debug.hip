@@ -1,10 +1,12 @@
 // debug.hip — test hooks: elementwise device arithmetic on host arrays for the parity tests.
 // plk_debug_field_op: the packed field of ff.hpp; plk_debug_rx_op: the redundant-limb field of
-// ffr.hpp on raw limb rows; plk_debug_g1r_op: the XYZZ group law of g1r.hpp on raw limb rows.
+// ffr.hpp on raw limb rows; plk_debug_g1r_op: the XYZZ group law of g1r.hpp on raw limb rows;
+// plk_debug_block_eval: the prover's forward block transform onto a key's quotient domain.
 #include <hip/hip_runtime.h>
 
 #include "g1r.hpp"
 #include "internal.hpp"
+#include "prover.hpp"
 
 namespace plk {
 namespace {
@@ -331,6 +333,39 @@ extern "C" int plk_debug_field_op(plk_ctx* ctx, int field, int op, const uint64_
     plk::DeviceGuard g(ctx->device);
     return field == 0 ? plk::run<plk::FrCfg>(ctx, op, a, b, out, n)
                       : plk::run<plk::FpCfg>(ctx, op, a, b, out, n);
+  } catch (...) {
+    return PLK_E_DEVICE;
+  }
+}
+
+// the same call the prover makes for z, the wires and the key's tables (prover.hip coset_fwd)
+extern "C" int plk_debug_block_eval(plk_key* key, const uint64_t* coef, size_t len, uint64_t* out,
+                                    size_t out_cap, int* blocks_out) {
+  using plk::last_hip_error;
+  try {
+    if (!key) return PLK_E_ARG;
+    if (blocks_out) *blocks_out = key->qb;
+    if (!out) return PLK_OK;
+    const uint64_t n = key->n, total = (uint64_t)key->qb * n;
+    if (!coef || len == 0 || len > n + 8 || out_cap < total) return PLK_E_ARG;
+    plk::DeviceGuard g(key->ctx->device);
+    hipStream_t s = key->ctx->stream;
+    plk::DevBuf din, dout;
+    int st;
+    if ((st = din.alloc(len * sizeof(plk::Fr))) || (st = dout.alloc(total * sizeof(plk::Fr))))
+      return st;
+    PLK_HIP_TRY(hipMemcpyAsync(din.ptr, coef, len * sizeof(plk::Fr), hipMemcpyHostToDevice, s));
+    plk::NttBatch b;
+    b.in_stride = 0;
+    b.out_stride = n;
+    b.pre = key->coset_s.as<plk::Fr>();
+    b.pre_stride = n + 8;
+    if ((st = plk::ntt_run_batch(key->dom, din.as<plk::Fr>(), dout.as<plk::Fr>(), len, 1, 1,
+                                 nullptr, s, (uint32_t)key->qb, b)))
+      return st;
+    PLK_HIP_TRY(hipMemcpyAsync(out, dout.ptr, total * sizeof(plk::Fr), hipMemcpyDeviceToHost, s));
+    PLK_HIP_TRY(plk::stream_wait(s));
+    return PLK_OK;
   } catch (...) {
     return PLK_E_DEVICE;
   }

@@ -294,7 +294,10 @@ __device__ __forceinline__ void quad_transpose(RFr& a0, RFr& a1, RFr& a2, RFr& a
   }
 }
 
-// One Stockham pass. PRE: 0 none, 1 multiply input e by pre[e] (coset g^e).
+// One Stockham pass. PRE: 0 none, 1 multiply input e by pre[e] (coset g^e), 2 the same for an
+// input longer than the transform (n < len_in <= n + 8, first pass only): on the coset s H_n
+// X^n = s^n, so the pre-scaled coefficient n + j (pre[n + j] = s^(n + j)) is added to the
+// pre-scaled coefficient j — the whole polynomial evaluated on the coset, its buffer untouched.
 // POST: 0 none, 1 multiply by post_scalar, 2 multiply output e by post[e].
 // Data buffers are R-domain (canonical in and out); tw / pre / post / post_scalar are
 // R'-domain (ffr.hpp), so every product data x table stays in the R domain.
@@ -328,7 +331,7 @@ __global__ void __launch_bounds__(256, PLK_NTT_MINW) k_ntt_pass(const Fr* __rest
     const uint32_t yi = str.group_in ? y % str.group_in : y, gi = str.group_in ? y / str.group_in : 0;
     in += (size_t)yi * str.in + (size_t)gi * str.in_group;
     out += (size_t)y * str.out;
-    if (PRE == 1) pre += (size_t)yi * str.pre;
+    if (PRE >= 1) pre += (size_t)yi * str.pre;
     if (POST == 2) post += (size_t)(str.group_post ? y % str.group_post : y) * str.post;
   }
 
@@ -353,11 +356,11 @@ __global__ void __launch_bounds__(256, PLK_NTT_MINW) k_ntt_pass(const Fr* __rest
       const size_t g = (size_t)(i0 + (e & (T - 1))) + ((size_t)(e >> lt) << nr_log);
       const size_t gc = g < len_in ? g : 0;
       raw[c] = ld_fr(&in[gc]);
-      if (PRE == 1) aux[c] = ld_fr(&pre[gc]);
+      if (PRE >= 1) aux[c] = ld_fr(&pre[gc]);
     }
     // inter-pass twiddle w_{Rp}^{jk} from the pass table laid out [j][k] (coalesced in k);
     // every (j, k) is in the table and every entry is multiplied below (see there)
-    if (PRE != 1 && lp != 0) {
+    if (PRE == 0 && lp != 0) {
 #pragma unroll
       for (uint32_t c = 0; c < kLoadIt; ++c) {
         const uint32_t e = min(tid + c * bd, E - 1);
@@ -414,13 +417,17 @@ __global__ void __launch_bounds__(256, PLK_NTT_MINW) k_ntt_pass(const Fr* __rest
       RFr v = rx_zero<FrCfg>();
       if (g < len_in) {
         v = rx_unpack(raw[c]);
-        if (PRE == 1) v = rx_mul(v, rx_unpack(aux[c]));
+        if (PRE >= 1) v = rx_mul(v, rx_unpack(aux[c]));
+        if (PRE == 2) {  // the few coefficients past n fold onto the first rows (see above)
+          const size_t g2 = g + ((size_t)1 << log_n);
+          if (g2 < len_in) v = rx_add(v, rx_mul(ld_rfr(&in[g2]), ld_rfr(&pre[g2])));
+        }
       }
       // inter-pass twiddle: the multiply MUST stay unconditional. A plain idft's last pass
       // reads pass_tw_inv_last, whose entries carry n^-1 (round 5: the idft scaling rides on
       // this table), so its j = 0 / k = 0 entries are n^-1, not one; skipping the "identity"
       // entries would drop the scaling on those rows (test_idft_multipass_identity_rows)
-      if (PRE != 1 && lp != 0) v = rx_mul(v, rx_unpack(aux[c]));
+      if (PRE == 0 && lp != 0) v = rx_mul(v, rx_unpack(aux[c]));
       return v;
     };
     {
@@ -708,7 +715,11 @@ int ntt_run(plk_domain* d, const Fr* in, Fr* out, size_t len_in, int dir, int co
 int ntt_run_batch(plk_domain* d, const Fr* in, Fr* out, size_t len_in, int dir, int coset,
                   Fr* scratch, hipStream_t stream, uint32_t count, const NttBatch& bt) {
   const uint64_t n = d->n;
-  if (len_in > n || count == 0) return PLK_E_ARG;
+  if (count == 0) return PLK_E_ARG;
+  // a polynomial of up to n + 8 coefficients on a coset given by a `pre` table of that many
+  // rows: folded in the first pass' loads (k_ntt_pass PRE = 2)
+  const bool fold = len_in > n;
+  if (fold && !(bt.pre && dir > 0 && coset && len_in <= n + 8 && n > 1)) return PLK_E_ARG;
   const Fr* pre_table = bt.pre;
   if (n == 1) {  // size-1 transform: x * pre[0] (forward coset) or x * post[0]; else identity
     if (bt.pre || bt.post) return PLK_E_ARG;  // not needed by any caller
@@ -753,7 +764,7 @@ int ntt_run_batch(plk_domain* d, const Fr* in, Fr* out, size_t len_in, int dir, 
     if (bd < 64) bd = 64;
     if (bd > 256) bd = 256;
     const uint32_t blocks = (uint32_t)(n >> (ps.lr + ps.lt));
-    const int pre = (first && dir > 0 && coset) ? 1 : 0;
+    const int pre = (first && dir > 0 && coset) ? (fold ? 2 : 1) : 0;
     // a plain idft's n^-1 comes with the last pass' inter-pass twiddles (pass_tw_inv_last) when
     // the plan has more than one pass: one product per element fewer in that pass
     const bool scaled_tw = last && !first && dir < 0 && !coset;
@@ -800,6 +811,7 @@ int ntt_run_batch(plk_domain* d, const Fr* in, Fr* out, size_t len_in, int dir, 
       else PLK_LAUNCH(0, 0, 1);
     } else if (pre == 0 && post == 0) PLK_LAUNCH(0, 0, 0);
     else if (pre == 1 && post == 0) PLK_LAUNCH(1, 0, 0);
+    else if (pre == 2) PLK_LAUNCH(2, 0, 0);
     else if (pre == 0 && post == 1) PLK_LAUNCH(0, 1, 0);
     else if (pre == 0 && post == 2) PLK_LAUNCH(0, 2, 0);
     else if (pre == 1 && post == 1) PLK_LAUNCH(1, 1, 0);

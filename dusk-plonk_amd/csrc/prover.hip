@@ -414,16 +414,6 @@ int prover_commit(plk_prover* P, const std::vector<const Fr*>& ptrs,
   return key_commit(P->key, *P->ws, ptrs, lens, outs, statuses, P->stream, cap);
 }
 
-// a primitive cube root of unity in Fr: 7^((r-1)/3) = 0xac45a4010001a40200000000ffffffff
-// (Montgomery form)
-Fr cube_root_of_unity() {
-  static const uint32_t w[8] = {0xffffffffu, 0x00000000u, 0x0001a402u, 0xac45a401u,
-                                0u, 0u, 0u, 0u};
-  Fr x;
-  for (int i = 0; i < 8; ++i) x.v[i] = w[i];
-  return fe_to_mont(x);
-}
-
 // JubJub twisted-Edwards d = -10240/10241 mod r
 // (0x2a9318e74bfa2b48f5fd9207e6bd7fd4292d7f6d37579d2601065fd6d6343eb1), Montgomery form
 Fr edwards_d() {
@@ -766,8 +756,8 @@ int plk_key_compile(plk_srs* srs, const plk_composer* cs, const char* label, plk
       if (!fe_is_zero(g.q[QVAR])) key->has_var = true;
     }
     TRY(plk_domain_get(ctx, k, &key->dom));
-    TRY(plk_domain_get(ctx, k + 1, &key->domq));
-    const uint64_t n2 = 2 * n, nq = kQBlocks * n2;
+    const int QB = key->qb = q_blocks(n);
+    const uint64_t nq = (uint64_t)QB * n;  // quotient domain (prover.hpp)
 
     // 1. selectors padded to n (key.rs:89-119) -> idft (key.rs:121-131)
     std::vector<Fr> host(11 * n, fe_zero<FrCfg>());
@@ -825,49 +815,62 @@ int plk_key_compile(plk_srs* srs, const plk_composer* cs, const char* label, plk
     for (int i = 11; i < 15; ++i)
       if (sts[i] != PLK_OK) return sts[i];
 
-    // 4. quotient-domain evaluations (key.rs:220-245 over g H_8n there; g H_6n here, see
-    // prover.hpp) and v_h over it (key.rs:291)
+    // 4. quotient-domain evaluations (key.rs:220-245 over g H_8n there; its cosets
+    // g w_8n^m H_n, m < QB, here, see prover.hpp) and v_h over them (key.rs:291)
     {
-      const Fr gq = key->domq->g, one = fe_one<FrCfg>();
-      const Fr w3 = cube_root_of_unity();
-      const uint64_t rowc = n + 8;  // coset table row: the transforms read <= n + 3 inputs
-      TRY(key->coset_s.alloc(kQBlocks * rowc * sizeof(Fr)));
-      TRY(key->coset_w.alloc(kQBlocks * rowc * sizeof(Fr)));
-      TRY(key->coset_pi.alloc(kQBlocks * rowc * sizeof(Fr)));
-      TRY(key->icoset_q.alloc(kQBlocks * n2 * sizeof(Fr)));
-      const Fr c32 = fr_u64(32), inv3 = fe_inv(fr_u64(3));
+      const Fr gq = key->dom->g, one = fe_one<FrCfg>();
+      Fr w8n;
+      fr_root_of_unity(k + 3, w8n);
+      const uint64_t rowc = n + 8;  // coset table row: the transforms read <= n + 8 inputs
+      TRY(key->coset_s.alloc(QB * rowc * sizeof(Fr)));
+      TRY(key->coset_w.alloc(QB * rowc * sizeof(Fr)));
+      TRY(key->coset_pi.alloc(QB * rowc * sizeof(Fr)));
+      TRY(key->icoset_q.alloc(QB * n * sizeof(Fr)));
+      const Fr c32 = fr_u64(32);
       Fr sm = gq;
-      for (int mb = 0; mb < kQBlocks; ++mb) {
+      for (int mb = 0; mb < QB; ++mb) {
         key->s_m[mb] = sm;
         TRY(ntt_power_table(key->coset_s.as<Fr>() + mb * rowc, sm, one, rowc, true, s));
         TRY(ntt_power_table(key->coset_w.as<Fr>() + mb * rowc, sm, c32, rowc, true, s));
         TRY(ntt_power_table(key->coset_pi.as<Fr>() + mb * rowc, sm, fe_inv(c32), rowc, true, s));
-        TRY(ntt_power_table(key->icoset_q.as<Fr>() + mb * n2, fe_inv(sm),
-                            fe_mul(key->domq->n_inv, inv3), n2, true, s));
-        sm = fe_mul(sm, w3);
+        TRY(ntt_power_table(key->icoset_q.as<Fr>() + mb * n, fe_inv(sm), key->dom->n_inv, n, true,
+                            s));
+        sm = fe_mul(sm, w8n);
       }
-      // k_coset3_combine: c[k + 2n l] = g^(-2nl) sum_m eta^(-ml) B'_m[k], eta = w3^(2n)
-      const Fr eta_inv = fe_inv(fe_pow_u64(w3, n2));
-      const Fr eta_inv2 = fe_sqr(eta_inv);
-      const Fr g1 = fe_inv(fe_pow_u64(gq, n2)), g2 = fe_sqr(g1);
-      const Fr cm[6] = {g1, fe_mul(g1, eta_inv), fe_mul(g1, eta_inv2),
-                        g2, fe_mul(g2, eta_inv2), fe_mul(g2, eta_inv)};
-      for (int j = 0; j < 6; ++j) key->comb[j] = fe_to_rx_domain(cm[j]);
-      // v_h(s_m w_2n^u) = g^n w3^(mn) (-1)^u - 1: index 2m + (u & 1)
-      for (int mb = 0; mb < kQBlocks; ++mb) {
-        const Fr x = fe_pow_u64(key->s_m[mb], n);
-        key->vh_inv[2 * mb] = fe_inv(fe_sub(x, one));
-        key->vh_inv[2 * mb + 1] = fe_inv(fe_sub(fe_neg(x), one));
+      // c_m = s_m^n = g^n w_8^m; v_h(s_m w_n^u) = c_m - 1 on the whole block
+      Fr cm[kQBlocksMax];
+      for (int mb = 0; mb < QB; ++mb) {
+        cm[mb] = fe_pow_u64(key->s_m[mb], n);
+        key->vh_inv[mb] = fe_inv(fe_sub(cm[mb], one));
+      }
+      // pk_coset_combine: the inverse of V[m][l] = c_m^l. Its column m holds the coefficients
+      // of the Lagrange polynomial prod_{j != m} (x - c_j) / (c_m - c_j)
+      for (int mb = 0; mb < QB; ++mb) {
+        Fr poly[kQBlocksMax + 1];
+        int deg = 0;
+        poly[0] = one;
+        Fr den = one;
+        for (int j = 0; j < QB; ++j) {
+          if (j == mb) continue;
+          poly[deg + 1] = fe_zero<FrCfg>();
+          for (int l = deg + 1; l >= 1; --l)  // times (x - c_j)
+            poly[l] = fe_sub(poly[l - 1], fe_mul(poly[l], cm[j]));
+          poly[0] = fe_neg(fe_mul(poly[0], cm[j]));
+          ++deg;
+          den = fe_mul(den, fe_sub(cm[mb], cm[j]));
+        }
+        const Fr dinv = fe_inv(den);
+        for (int l = 0; l < QB; ++l) key->comb.m[l * QB + mb] = fe_to_rx_domain(fe_mul(poly[l], dinv));
       }
     }
-    // forward coset transforms of n-coefficient polys onto the three blocks in one launch
+    // forward coset transforms of n-coefficient polys onto the QB blocks in one launch
     auto coset_fwd = [&](const Fr* in, Fr* out, uint64_t len, const DevBuf& table) {
       NttBatch b;
       b.in_stride = 0;  // the same coefficients for every block
-      b.out_stride = n2;
+      b.out_stride = n;
       b.pre = table.as<Fr>();
       b.pre_stride = n + 8;
-      return ntt_run_batch(key->domq, in, out, len, 1, 1, nullptr, s, kQBlocks, b);
+      return ntt_run_batch(key->dom, in, out, len, 1, 1, nullptr, s, QB, b);
     };
     TRY(key->selq.alloc(SEL_COUNTQ * nq * sizeof(Fr)));
     const int sel_src[SEL_COUNTQ] = {QM, QL, QR, QO, Q4, QC, QARITH, QRANGE, QLOGIC, QFIXED, QVAR};
@@ -1040,7 +1043,8 @@ int plk_prover_prove(plk_prover* P, const plk_composer* cs, uint64_t seed, plk_p
     DeviceGuard guard(key->ctx->device);
     hipStream_t s = P->stream;
     const uint64_t n = key->n, m = key->m, S = n + 8;  // S: padded poly stride
-    const uint64_t n2 = 2 * n, nq = kQBlocks * n2;       // quotient domain (prover.hpp)
+    const int QB = key->qb;
+    const uint64_t nq = (uint64_t)QB * n;  // quotient domain (prover.hpp)
     Rng rng{seed};
     const Fr one = fe_one<FrCfg>();
     const Fr K1 = fr_u64(7), K2 = fr_u64(13), K3 = fr_u64(17);
@@ -1069,8 +1073,8 @@ int plk_prover_prove(plk_prover* P, const plk_composer* cs, uint64_t seed, plk_p
                             hipHostMallocMapped | hipHostMallocCoherent | hipHostMallocPortable));
       PLK_HIP_TRY(hipHostGetDevicePointer(&P->eval_dev, P->eval_out.ptr, 0));
     }
-    // 4 nq: the four wires' 12 coset blocks transform in one batch (24n of scratch: the output
-    // doubles as the other ping-pong buffer, ntt_run_batch)
+    // 4 nq: the four wires' 4 QB coset blocks transform in one batch (4 QB n of scratch: the
+    // output doubles as the other ping-pong buffer, ntt_run_batch)
     TRY(P->ntt_scratch.alloc(4 * nq * sizeof(Fr)));
     Fr* nsc = P->ntt_scratch.as<Fr>();
 
@@ -1173,7 +1177,9 @@ int plk_prover_prove(plk_prover* P, const plk_composer* cs, uint64_t seed, plk_p
     // PI(X) = idft of the public-input vector (prover.rs:229): for a few public inputs
     // straight from its definition, one product per input and coefficient (no upload, no
     // transform); otherwise the vector is uploaded and transformed
-    const bool pi_direct = !pis.empty() && pis.size() <= (size_t)kPiDirect;
+    // at most kPiSparse: no PI polynomial at all, rotated rows of the key's L1 table instead
+    const bool pi_sparse = !pis.empty() && pis.size() <= (size_t)kPiSparse;
+    const bool pi_direct = !pis.empty() && !pi_sparse && pis.size() <= (size_t)kPiDirect;
     if (pi_direct) {
       PiDirect pd{};
       pd.count = (uint32_t)pis.size();
@@ -1182,7 +1188,7 @@ int plk_prover_prove(plk_prover* P, const plk_composer* cs, uint64_t seed, plk_p
         pd.c[i] = fe_mul(pis[i].second, key->dom->n_inv);
       }
       TRY(pk_pi_coef(pd, key->dom->tw_inv.as<Fr>(), n, P->pi_coef.as<Fr>(), s));
-    } else if (!pis.empty()) {
+    } else if (!pis.empty() && !pi_sparse) {
       PLK_HIP_TRY(hipMemsetAsync(pil, 0, n * sizeof(Fr), s));
       for (size_t i = 0; i < pis.size(); ++i) {
         P->pin_small.as<Fr>()[i] = pis[i].second;
@@ -1191,33 +1197,44 @@ int plk_prover_prove(plk_prover* P, const plk_composer* cs, uint64_t seed, plk_p
       }
     }
     // the six polynomials over the quotient domain (quotient_poly.rs:54-58,145 over g H_8n
-    // there): each a batch of the three coset blocks (prover.hpp) in one launch per pass
+    // there): each a batch of the QB coset blocks (prover.hpp) in one launch per pass; z and the
+    // wires are longer than n and fold onto the block (ntt_run_batch)
     Fr* ev = P->evq.as<Fr>();  // z, a, b, c, d, pi, nq points each
     auto coset_fwd = [&](const Fr* in, Fr* out, uint64_t len, const DevBuf& table) {
       NttBatch b;
       b.in_stride = 0;
-      b.out_stride = n2;
+      b.out_stride = n;
       b.pre = table.as<Fr>();
       b.pre_stride = n + 8;
-      return ntt_run_batch(key->domq, in, out, len, 1, 1, nsc, s, kQBlocks, b);
+      return ntt_run_batch(key->dom, in, out, len, 1, 1, nsc, s, QB, b);
     };
-    if (!pis.empty() && !pi_direct)
+    if (!pis.empty() && !pi_direct && !pi_sparse)
       TRY(ntt_run(key->dom, pil, P->pi_coef.as<Fr>(), n, -1, 0, nsc, s, 1));
     TRY(coset_fwd(zc, ev + 0 * nq, n + 3, key->coset_s));
     // wire evaluations at exponent -1 and PI at +1 for k_quotient's redundant-form
     // arithmetic (QuotientArgs): scaled coset tables, no extra pass
-    {  // the four wires' coset blocks as ONE batch of 12 (NttBatch::group: wire c, block m)
+    {  // the four wires' coset blocks as ONE batch of 4 QB (NttBatch::group: wire c, block m)
       NttBatch b;
-      b.group = kQBlocks;
+      b.group = QB;
       b.in_stride = 0;
       b.in_group_stride = S;
-      b.out_stride = n2;
+      b.out_stride = n;
       b.pre = key->coset_w.as<Fr>();
       b.pre_stride = n + 8;
-      TRY(ntt_run_batch(key->domq, wc, ev + nq, n + 2, 1, 1, nsc, s, 4 * kQBlocks, b));
+      TRY(ntt_run_batch(key->dom, wc, ev + nq, n + 2, 1, 1, nsc, s, 4 * QB, b));
     }
     // PI(X) over the coset; a circuit without public inputs has PI = 0 (the term is skipped)
-    if (!pis.empty()) TRY(coset_fwd(P->pi_coef.as<Fr>(), ev + 5 * nq, n, key->coset_pi));
+    if (pi_sparse) {
+      PiSparse ps{};
+      ps.count = (uint32_t)pis.size();
+      for (size_t i = 0; i < pis.size(); ++i) {
+        ps.idx[i] = (uint32_t)pis[i].first;
+        ps.v[i] = pis[i].second;
+      }
+      TRY(pk_pi_sparse(ps, key->l1q.as<Fr>(), key->k, nq, ev + 5 * nq, s));
+    } else if (!pis.empty()) {
+      TRY(coset_fwd(P->pi_coef.as<Fr>(), ev + 5 * nq, n, key->coset_pi));
+    }
     const Fr alpha2 = fe_sqr(alpha);
     QuotientArgs qa{};
     qa.z = ev;
@@ -1230,11 +1247,11 @@ int plk_prover_prove(plk_prover* P, const plk_composer* cs, uint64_t seed, plk_p
     qa.alpha2 = alpha2;
     qa.sel = key->selq.as<Fr>();
     qa.sigma = key->sigmaq.as<Fr>();
-    qa.elements = key->domq->tw_fwd.as<Fr>();
+    qa.elements = key->dom->tw_fwd.as<Fr>();
     qa.out = P->quotq.as<Fr>();
     qa.nq = nq;
-    qa.log_blk = key->k + 1;
-    qa.g = key->domq->g;
+    qa.log_blk = key->k;
+    qa.g = key->dom->g;
     qa.alpha = alpha;
     qa.beta = beta;
     qa.gamma = gamma;
@@ -1262,12 +1279,12 @@ int plk_prover_prove(plk_prover* P, const plk_composer* cs, uint64_t seed, plk_p
     qa.edwards_d = edwards_d();
     qa.has_fixed = key->has_fixed ? 1 : 0;
     qa.has_var = key->has_var ? 1 : 0;
-    for (int j = 0; j < 2 * kQBlocks; ++j) qa.vh_inv[j] = key->vh_inv[j];
+    for (int j = 0; j < QB; ++j) qa.vh_inv[j] = key->vh_inv[j];
     {  // exponent-scaled constants for k_quotient (x[e] = x R 2^(-5e); [-1] = R' domain)
       auto em1 = [](const Fr& x) { return fe_to_rx_domain(x); };
       auto em2 = [](const Fr& x) { return fe_to_rx_domain(fe_to_rx_domain(x)); };
       const Fr one = fe_one<FrCfg>(), two = fe_dbl(one);
-      for (int mb = 0; mb < kQBlocks; ++mb) qa.rx_bg[mb] = em2(fe_mul(beta, key->s_m[mb]));
+      for (int mb = 0; mb < QB; ++mb) qa.rx_bg[mb] = em2(fe_mul(beta, key->s_m[mb]));
       qa.rx_beta = em2(beta);
       qa.rx_gamma = em1(gamma);
       qa.rx_one_w = em1(one);
@@ -1277,31 +1294,30 @@ int plk_prover_prove(plk_prover* P, const plk_composer* cs, uint64_t seed, plk_p
       qa.rx_kappa2 = em1(qa.kappa2);
       qa.rx_kappa3 = em1(qa.kappa3);
       qa.rx_alpha2 = em1(alpha2);
-      for (int j = 0; j < 2 * kQBlocks; ++j) qa.rx_vh[j] = em2(key->vh_inv[j]);
+      for (int j = 0; j < QB; ++j) qa.rx_vh[j] = em2(key->vh_inv[j]);
       qa.rx_32 = fr_u64(32);
       qa.rx_inv32 = fe_inv(qa.rx_32);
     }
     TRY(pk_quotient(qa, s));
     Fr* tc = P->t_coef.as<Fr>();
-    {  // t = coset_idft over the quotient domain (quotient_poly.rs:115): the three blocks'
-       // inverse transforms (post-scaled by (2n)^-1 3^-1 s_m^-k) in place, then the radix-3
-       // combine into the 6n coefficients (t has at most 4n + 7; the rest are zero)
+    {  // t = coset_idft over the quotient domain (quotient_poly.rs:115): the QB blocks' inverse
+       // transforms (post-scaled by n^-1 s_m^-k) in place give t mod (X^n - c_m), then the
+       // combine into the QB n coefficients (t has at most 4n + 7; the rest are zero)
       NttBatch b;
-      b.in_stride = b.out_stride = n2;
+      b.in_stride = b.out_stride = n;
       b.post = key->icoset_q.as<Fr>();
-      b.post_stride = n2;
-      TRY(ntt_run_batch(key->domq, P->quotq.as<Fr>(), P->quotq.as<Fr>(), n2, -1, 1, nsc, s,
-                        kQBlocks, b));
-      TRY(pk_coset3_combine(P->quotq.as<Fr>(), n2, key->comb, tc, s));
+      b.post_stride = n;
+      TRY(ntt_run_batch(key->dom, P->quotq.as<Fr>(), P->quotq.as<Fr>(), n, -1, 1, nsc, s, QB, b));
+      TRY(pk_coset_combine(P->quotq.as<Fr>(), n, QB, key->comb, tc, s));
     }
     // split into t_low, t_mid, t_high (n each) and t_4 = t[3n..] (prover.rs:252-265)
     plk_g1 tcom[4];
-    // t_4 is t[3n..8n) in the reference (prover.rs:259) and t[3n..6n) here. For a satisfied
+    // t_4 is t[3n..8n) in the reference (prover.rs:259) and t[3n..QB n) here. For a satisfied
     // circuit t has degree <= 4n + 6 on either domain (prover.hpp), so t_4 ends below n + 8:
     // committing at most n + 8 points changes no commitment, and the zero check of the rest
-    // fails for an unsatisfied circuit (its interpolant does not vanish there) where the
-    // reference's commit fails (t_4 past the trimmed SRS, prover.rs:262-265) — including
-    // tiny circuits whose trimmed SRS covers all of t[3n..6n)
+    // fails for an unsatisfied circuit (its interpolant does not vanish there, prover.hpp)
+    // where the reference's commit fails (t_4 past the trimmed SRS, prover.rs:262-265) —
+    // including tiny circuits whose trimmed SRS covers all of t[3n..QB n)
     TRY(prover_commit(P, {tc, tc + n, tc + 2 * n, tc + 3 * n}, {n, n, n, nq - 3 * n}, tcom,
                       nullptr, n + 8));
     // its commit succeeded, so everything past the committed prefix is zero: t and t_4 end at

@@ -34,21 +34,50 @@ enum { SEL_QM = 0, SEL_QL, SEL_QR, SEL_QO, SEL_Q4, SEL_QC, SEL_QARITH, SEL_QRANG
        SEL_QFIXED, SEL_QVAR, SEL_COUNTQ };
 
 // The quotient domain (round 3). The reference evaluates the quotient over the coset g H_8n
-// (quotient_poly.rs:52-58,115); the numerator has degree at most 5n + 6 (z times four wire
-// factors) and t = num / Z_H at most 4n + 6, so any coset of more than 5n + 6 points
-// interpolates the same t — bit-identical coefficients, commitments and proofs. This backend
-// uses 6n points: g w3^m H_2n for m < 3 (w3 a primitive cube root of unity; gcd(3, 2n) = 1, so
-// the three cosets form g H_6n), 25% fewer points than 8n. Every quotient-domain vector is
-// laid out in three blocks of 2n (block m = coset m, natural order in u): evaluation point
-// x(m, u) = s_m w_2n^u with s_m = g w3^m, the next row (w_n x) is u + 2 in the same block, and
-// v_h(x) = x^n - 1 = g^n w3^(mn) (-1)^u - 1 takes 6 values (index 2m + (u & 1)).
-constexpr int kQBlocks = 3;
+// (quotient_poly.rs:52-58,115). The numerator (z times four wire factors, degree <= 5n + 6) is
+// never interpolated: k_quotient evaluates t(x) = num(x) / Z_H(x) exactly at each point from
+// exact evaluations of the factors, and only t is interpolated. t has degree <= 4n + 6, so ANY
+// 4n + 7 or more distinct points off H give the same coefficients, commitments and proofs, bit
+// for bit. This backend uses kQBlocks = 5 cosets of the n-domain itself, s_m H_n with
+// s_m = g w_8n^m (m < 5): 5n >= 4n + 8 points for n >= 8, every point is point 8u + m of the
+// reference's own g H_8n, and every block transform is an n-point one (key->dom). Every
+// quotient-domain vector is laid out in blocks of n (block m = coset m, natural order in u):
+// evaluation point x(m, u) = s_m w_n^u, the next row (w_n x) is u + 1 in the same block, and
+// v_h(x) = x^n - 1 = c_m - 1 with c_m = s_m^n = g^n w_8^m is constant per block (five distinct
+// values, none equal to 1).
+//
+// Inverse: the inverse block transform m gives r_m = t mod (X^n - c_m), r_m[k] = sum_l c_m^l
+// t_l[k] for the n-coefficient chunks t_l of t; the chunks come back through the inverse
+// Vandermonde matrix of the c_m (pk_coset_combine; the matrix is computed once per key).
+//
+// Unsatisfied circuits: num = q Z_H + rho with rho = num mod Z_H != 0, so the evaluated values
+// are q(x) + rho(x) / (c_m - 1) and the interpolant is q + rho(X) A(X^n), A the polynomial of
+// degree <= kQBlocks - 1 with A(c_m) = 1 / (c_m - 1). Its leading coefficient kappa is not
+// zero (else A(c)(c - 1) - 1, of degree <= kQBlocks - 1, would vanish at kQBlocks points and
+// hence at c = 1, where it is -1). q has degree <= 4n + 6, so the coefficients [4n + 8, 5n) of
+// the interpolant are kappa rho[8..n): the zero check of t_4 past its n + 8 committed points
+// (prover.hip) fails there (PLK_E_DEGREE) as it did on the 6n-point domain used before, by the
+// same argument. n = 8 (the smallest composer) leaves that range empty, so it takes
+// kQBlocksSmall = 6 blocks (the same cosets, m < 6) and the range [40, 48) = kappa rho.
+constexpr int kQBlocks = 5, kQBlocksSmall = 6, kQBlocksMax = 6;
+inline int q_blocks(uint64_t n) { return n >= 16 ? kQBlocks : kQBlocksSmall; }
+// PI over the quotient domain from at most kPiSparse public inputs as rotated reads of the
+// key's L1 table (pk_pi_sparse): L_i(X) = L_0(w^-i X), so PI(s_m w^u) = sum_i pi_i
+// l1q[m][(u - i) mod n] — one product per point and public input, no pk_pi_coef, idft or coset
+// transform. (Inside k_quotient the loop cost 2 spilled VGPRs at its 168-VGPR, 3-wave budget,
+// so it is a kernel of its own that fills the PI row k_quotient reads.)
+constexpr int kPiSparse = 4;
+struct PiSparse {
+  uint32_t count;
+  uint32_t idx[kPiSparse];  // gate index of each public input
+  Fr v[kPiSparse];          // its value (R domain)
+};
 
 struct QuotientArgs {
   const Fr *a, *b, *c, *d, *z, *pi, *l1, *sel, *sigma, *elements;  // pi null: no public inputs
   Fr* out;
-  uint64_t nq;        // quotient-domain points (6n): kQBlocks blocks of 2n
-  uint32_t log_blk;   // log2(2n)
+  uint64_t nq;        // quotient-domain points: q_blocks(n) blocks of n
+  uint32_t log_blk;   // log2(n)
   Fr g, alpha, alpha2, beta, gamma, k1, k2, k3;
   Fr range_sep, kappa, kappa2, kappa3;
   Fr logic_sep, lk, lk2, lk3, lk4;  // logic separation challenge and its kappa powers
@@ -56,17 +85,17 @@ struct QuotientArgs {
   Fr var_sep, vk, vk2;               // variable-base addition: sep, kappa = sep^2, ^2
   Fr edwards_d;                      // JubJub d = -10240/10241
   int has_range, has_logic, has_fixed, has_var;
-  Fr vh_inv[2 * kQBlocks];  // 1 / v_h, index 2m + (u & 1)
+  Fr vh_inv[kQBlocksMax];  // 1 / v_h of block m
   // k_quotient runs in the redundant form (ffr.hpp): a value with exponent e is stored as
   // x R 2^(-5e) (e = 0: the R domain; e = -1: the R' domain) and rx_mul adds exponents
   // plus one. Wire evaluations arrive at e = -1 (coset table scaled by 2^5), public
   // inputs at e = +1, z / selectors / sigmas / L1 / elements at e = 0; these constants are
   // pre-scaled so every term meets at e = 1 and num / v_h lands at e = 0 (the R domain).
-  Fr rx_bg[kQBlocks], rx_beta, rx_gamma;  // beta s_m and beta at e = -2, gamma at e = -1
+  Fr rx_bg[kQBlocksMax], rx_beta, rx_gamma;  // beta s_m and beta at e = -2, gamma at e = -1
   Fr rx_one_w, rx_two_w, rx_three_w;    // 1, 2, 3 at e = -1 (range widget deltas)
   Fr rx_kappa, rx_kappa2, rx_kappa3;    // range kappa powers at e = -1
   Fr rx_alpha2;                         // alpha^2 at e = -1 (alpha and range_sep at e = 0)
-  Fr rx_vh[2 * kQBlocks];               // 1 / v_h at e = -2
+  Fr rx_vh[kQBlocksMax];                // 1 / v_h at e = -2
   Fr rx_inv32, rx_32;                   // 2^-5 and 2^5 (R domain): k_quotient_ext converts
 };
 
@@ -155,6 +184,9 @@ int pk_blind_batch(const BlindBatch& bb, uint64_t n, hipStream_t s);
 // coefficients of PI(X) = idft(public-input vector) for at most kPiDirect public inputs:
 // out[j] = sum_k c_k w^(-idx_k j), w^-e from the domain's R'-domain table tw_inv
 int pk_pi_coef(const PiDirect& pd, const Fr* tw_inv, uint64_t n, Fr* out, hipStream_t s);
+// out[m n + u] = sum_k v_k l1[m n + ((u - idx_k) mod n)] at exponent +1, over nq = blocks * n points
+int pk_pi_sparse(const PiSparse& ps, const Fr* l1, uint32_t log_n, uint64_t nq, Fr* out,
+                 hipStream_t s);
 int pk_fill(Fr* out, const Fr& v, uint64_t n, hipStream_t s);
 int pk_perm_numden(const Fr* wires, const Fr* sigmas, const Fr* elements, uint64_t n,
                    const Fr& beta, const Fr& gamma, const Fr& k1, const Fr& k2, const Fr& k3,
@@ -164,10 +196,14 @@ uint64_t pk_scan_tmp_elems(uint64_t n);
 int pk_scan(const Fr* in, Fr* out, uint64_t n, bool mul, bool suffix, bool exclusive, Fr* tmp,
             hipStream_t s);
 int pk_quotient(const QuotientArgs& q, hipStream_t s);
-// t coefficients from the kQBlocks inverse block transforms B'_m (scaled by (2n)^-1 3^-1 s_m^-k):
-// out[k + 2n l] = g^(-2nl) sum_m eta^(-ml) B'_m[k], eta = w3^(2n); comb = R'-domain constants
-// {g^-2n, g^-2n eta^-1, g^-2n eta^-2, g^-4n, g^-4n eta^-2, g^-4n eta^-1}
-int pk_coset3_combine(const Fr* in, uint64_t n2, const Fr* comb, Fr* out, hipStream_t s);
+// t coefficients from the `blocks` inverse block transforms r_m (n coefficients each, in + m n):
+// out[k + l n] = sum_m mat[l * blocks + m] r_m[k] for l, m < blocks; mat: the inverse
+// Vandermonde matrix of the c_m (prover.hpp top), R'-domain constants
+struct CombineMat {
+  Fr m[kQBlocksMax * kQBlocksMax];
+};
+int pk_coset_combine(const Fr* in, uint64_t n, int blocks, const CombineMat& mat, Fr* out,
+                     hipStream_t s);
 // out[j] = in[j] * c (packed Montgomery product), j < n
 int pk_scale_copy(const Fr* in, const Fr& c, Fr* out, uint64_t n, hipStream_t s);
 uint32_t pk_eval_max_blocks(uint64_t max_len);
@@ -225,24 +261,24 @@ struct plk_key {
   std::string label;
   uint64_t m = 0, n = 0, n_trim = 0;
   uint32_t k = 0;
-  plk_domain* dom = nullptr;   // n
-  plk_domain* domq = nullptr;  // 2n: the blocks of the 6n quotient domain (prover.hpp top)
+  plk_domain* dom = nullptr;   // n (also the blocks of the quotient domain, prover.hpp top)
+  int qb = 0;                  // q_blocks(n)
   bool has_range = false, has_logic = false, has_fixed = false, has_var = false;
   // device-resident proving key
   plk::DevBuf q_coef;       // 11 x n selector coefficient polys
-  plk::DevBuf selq;         // SEL_COUNTQ x 6n quotient-domain evaluations
+  plk::DevBuf selq;         // SEL_COUNTQ x qb n quotient-domain evaluations
   plk::DevBuf sigma_coef;   // 4 x n
   plk::DevBuf sigma_lag;    // 4 x n Lagrange values (= dft of sigma_coef, cached)
-  plk::DevBuf sigmaq;       // 4 x 6n
+  plk::DevBuf sigmaq;       // 4 x qb n
   plk::DevBuf l1q;          // L1 over the quotient domain: coset_dft(idft(e_0)) (quotient_poly.rs:264-272)
-  // forward coset tables, kQBlocks rows of n + 8 (R' domain): s_m^j for selectors, sigmas,
+  // forward coset tables, qb rows of n + 8 (R' domain): s_m^j for selectors, sigmas,
   // L1 and z; 2^5 s_m^j for the wires (evaluations at e = -1); 2^-5 s_m^j for PI (e = +1)
   plk::DevBuf coset_s, coset_w, coset_pi;
-  plk::DevBuf icoset_q;     // kQBlocks rows of 2n: (2n)^-1 3^-1 s_m^-k (R'), inverse blocks
-  plk::Fr s_m[plk::kQBlocks];    // g w3^m (R domain)
-  plk::Fr comb[6];          // k_coset3_combine constants (R'): g^-2n w3'^-l m, l = 1, 2
+  plk::DevBuf icoset_q;     // qb rows of n: n^-1 s_m^-k (R'), inverse blocks
+  plk::Fr s_m[plk::kQBlocksMax];  // g w_8n^m (R domain)
+  plk::CombineMat comb;     // pk_coset_combine's matrix (R')
   plk::DevBuf wire_idx;     // 4 x n witness indices per gate (u32)
-  plk::Fr vh_inv[2 * plk::kQBlocks];
+  plk::Fr vh_inv[plk::kQBlocksMax];
   plk_g1 comms[15];         // q_m q_l q_r q_o q_c q_4 q_arith q_range q_logic q_fixed q_var s1..s4
   // the circuit the key was compiled from: plk_prove refuses a circuit whose structure hash
   // differs or whose witness vector does not cover the largest wire index (prover.rs:114-119

@@ -4,9 +4,10 @@
 //  * grand product z (permutation.rs:205-300): per-gate numerator/denominator, then
 //    z_i = N_i * S_i / D (exclusive prefix product of numerators, inclusive suffix product
 //    of denominators, ONE inversion) instead of the reference's n inversions + serial scan
-//  * quotient over the 8n coset (quotient_poly.rs:74-114,122-262): arithmetic + range
-//    widgets + PI + permutation identity/copy terms + L1 term, divided by v_h, whose
-//    8 distinct values (period 8) are inverted once on the host
+//  * quotient over five n-point cosets of the reference's 8n coset (prover.hpp;
+//    quotient_poly.rs:74-114,122-262): arithmetic + range widgets + PI + permutation
+//    identity/copy terms + L1 term, divided by v_h, whose one value per coset is inverted
+//    once on the host
 //  * batched polynomial evaluation (linearization_poly.rs:52-73,108)
 //  * linear combinations (t split / quot assembly prover.rs:252-259,408-418, r(X),
 //    aggregate witness numerators) and Ruffini division by (X - z)
@@ -92,6 +93,21 @@ __global__ void k_pi_coef(PiDirect pd, const Fr* __restrict__ tw_inv, uint64_t n
   for (uint32_t k = 0; k < pd.count; ++k)
     acc = rx_add(acc, rx_mul(rx_unpack(pd.c[k]), ldr(&tw_inv[(pd.idx[k] * j) & (n - 1)])));
   stf(&out[j], rx_pack_canonical(acc));
+}
+
+// PI over the quotient domain from a few public inputs (PiSparse, prover.hpp): block m, row u
+// of the output is sum_k v_k L1[m][(u - idx_k) mod n]. L1 and v_k are R-domain values, so the
+// redundant-form product lands at exponent +1 (QuotientArgs), where k_quotient expects PI.
+__global__ void __launch_bounds__(256) k_pi_sparse(PiSparse ps, const Fr* __restrict__ l1,
+                                                   uint32_t log_n, uint64_t nq,
+                                                   Fr* __restrict__ out) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nq) return;
+  const uint64_t mask = (1ull << log_n) - 1, base = i & ~mask, u = i & mask;
+  RFr acc = rx_mul(ldr(&l1[base + ((u - ps.idx[0]) & mask)]), rx_unpack(ps.v[0]));
+  for (uint32_t k = 1; k < ps.count; ++k)
+    acc = rx_add(acc, rx_mul(ldr(&l1[base + ((u - ps.idx[k]) & mask)]), rx_unpack(ps.v[k])));
+  stf(&out[i], rx_pack_canonical(acc));
 }
 
 // thread 4p + i: coefficient i of polynomial p
@@ -316,9 +332,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const uint64_t N = q.nq;
   if (i >= N) return;
-  // quotient-domain block m (coset g w3^m H_2n), position u; the next row w_n x is u + 2
+  // quotient-domain block m (coset s_m H_n), position u; the next row w_n x is u + 1
   const uint64_t blk = i >> q.log_blk, u = i & ((1ull << q.log_blk) - 1);
-  const uint64_t nx = (blk << q.log_blk) + ((u + 2) & ((1ull << q.log_blk) - 1));
+  const uint64_t nx = (blk << q.log_blk) + ((u + 1) & ((1ull << q.log_blk) - 1));
   const RFr a = ldr(&q.a[i]), b = ldr(&q.b[i]), c = ldr(&q.c[i]), d = ldr(&q.d[i]);
   const RFr z = ldr(&q.z[i]), z_next = ldr(&q.z[nx]);
   // arithmetic widget: q_arith (q_m a b + q_l a + q_r b + q_o c + q_4 d + q_c), terms [0]
@@ -354,7 +370,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))
   //                    - z_next (a + b s1 + g)(b + b s2 + g)(c + b s3 + g)(d + b s4 + g) ]
   //              + (z - 1) L1(X) alpha^2
   // K1..K3 = 7, 13, 17 (permutation.rs:28-30) by additions
-  const RFr bX = rx_mul(rx_unpack(q.rx_bg[blk]), ldr(&q.elements[u]));  // beta s_m w_2n^u [-1]
+  const RFr bX = rx_mul(rx_unpack(q.rx_bg[blk]), ldr(&q.elements[u]));  // beta s_m w_n^u [-1]
   const RFr bX2 = rx_dbl(bX), bX4 = rx_dbl(bX2), bX8 = rx_dbl(bX4), bX16 = rx_dbl(bX8);
   const RFr bX7 = rx_sub(bX8, bX), bX13 = rx_add(rx_add(bX8, bX4), bX), bX17 = rx_add(bX16, bX);
   const RFr gm = rx_unpack(q.rx_gamma);  // [-1]
@@ -379,7 +395,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))
     RFr num = t;
 #pragma unroll
     for (int l = 0; l < RxShape<FrCfg>::L; ++l) num.v[l] += perm.v[l];
-    stf(&q.out[i], rx_pack_canonical(rx_mul(num, rx_unpack(q.rx_vh[2 * blk + (u & 1)]))));
+    stf(&q.out[i], rx_pack_canonical(rx_mul(num, rx_unpack(q.rx_vh[blk]))));
   } else {
     stf(&q.out[i], rx_pack_canonical(rx_add(t, perm)));  // [1]
   }
@@ -391,7 +407,7 @@ __global__ void __launch_bounds__(256) k_quotient_ext(QuotientArgs q) {
   const uint64_t N = q.nq;
   if (i >= N) return;
   const uint64_t blk = i >> q.log_blk, u = i & ((1ull << q.log_blk) - 1);
-  const uint64_t nx = (blk << q.log_blk) + ((u + 2) & ((1ull << q.log_blk) - 1));
+  const uint64_t nx = (blk << q.log_blk) + ((u + 1) & ((1ull << q.log_blk) - 1));
   // k_quotient left num at exponent +1 and the wire evaluations are at -1 (QuotientArgs):
   // back to the R domain for the packed arithmetic here
   auto ldw = [&](const Fr* p) { return fe_mul(ldf(p), q.rx_inv32); };
@@ -437,22 +453,30 @@ __global__ void __launch_bounds__(256) k_quotient_ext(QuotientArgs q) {
       t = fe_add(t, fe_mul(fe_mul(w, qv), q.var_sep));
     }
   }
-  stf(&q.out[i], fe_mul(t, q.vh_inv[2 * blk + (u & 1)]));
+  stf(&q.out[i], fe_mul(t, q.vh_inv[blk]));
 }
 
-// t from the three inverse block transforms (pk_coset3_combine, prover.hpp)
-__global__ void __launch_bounds__(256) k_coset3_combine(const Fr* __restrict__ in, uint64_t n2,
-                                                        Fr c1a, Fr c1b, Fr c1c, Fr c2a, Fr c2b,
-                                                        Fr c2c, Fr* __restrict__ out) {
+// t from the B inverse block transforms (pk_coset_combine, prover.hpp): chunk l of t is row l
+// of the inverse Vandermonde matrix applied to the blocks' coefficients k
+template <int B>
+__global__ void __launch_bounds__(256) k_coset_combine(const Fr* __restrict__ in, uint64_t n,
+                                                       CombineMat mat, Fr* __restrict__ out) {
   const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= n2) return;
-  const RFr b0 = ldr(&in[k]), b1 = ldr(&in[n2 + k]), b2 = ldr(&in[2 * n2 + k]);  // R domain
-  stf(&out[k], rx_pack_canonical(rx_add(rx_add(b0, b1), b2)));
-  // constants in the R' domain: products land in the R domain
-  const RFr e1 = rx_add(rx_mul_add(b0, rx_unpack(c1a), b1, rx_unpack(c1b)), rx_mul(b2, rx_unpack(c1c)));
-  stf(&out[n2 + k], rx_pack_canonical(e1));
-  const RFr e2 = rx_add(rx_mul_add(b0, rx_unpack(c2a), b1, rx_unpack(c2b)), rx_mul(b2, rx_unpack(c2c)));
-  stf(&out[2 * n2 + k], rx_pack_canonical(e2));
+  if (k >= n) return;
+  RFr r[B];  // R domain
+#pragma unroll
+  for (int m = 0; m < B; ++m) r[m] = ldr(&in[m * n + k]);
+  // constants in the R' domain: products land in the R domain; pairs share one reduction
+#pragma unroll
+  for (int l = 0; l < B; ++l) {
+    const Fr* row = &mat.m[l * B];
+    RFr e = rx_mul_add(r[0], rx_unpack(row[0]), r[1], rx_unpack(row[1]));
+#pragma unroll
+    for (int m = 2; m + 1 < B; m += 2)
+      e = rx_add(e, rx_mul_add(r[m], rx_unpack(row[m]), r[m + 1], rx_unpack(row[m + 1])));
+    if (B & 1) e = rx_add(e, rx_mul(r[B - 1], rx_unpack(row[B - 1])));
+    stf(&out[l * n + k], rx_pack_canonical(e));
+  }
 }
 
 // ------------------------------------------------------------ scaled table copy
@@ -706,6 +730,15 @@ int pk_pi_coef(const PiDirect& pd, const Fr* tw_inv, uint64_t n, Fr* out, hipStr
   return PLK_OK;
 }
 
+int pk_pi_sparse(const PiSparse& ps, const Fr* l1, uint32_t log_n, uint64_t nq, Fr* out,
+                 hipStream_t s) {
+  if (ps.count == 0 || ps.count > (uint32_t)kPiSparse) return PLK_E_ARG;
+  hipLaunchKernelGGL(k_pi_sparse, dim3(blocks_for(nq, 256)), dim3(256), 0, s, ps, l1, log_n, nq,
+                     out);
+  PLK_HIP_TRY(hipGetLastError());
+  return PLK_OK;
+}
+
 int pk_blind_batch(const BlindBatch& bb, uint64_t n, hipStream_t s) {
   hipLaunchKernelGGL(k_blind_batch, dim3(1), dim3(64), 0, s, bb, n);
   PLK_HIP_TRY(hipGetLastError());
@@ -774,9 +807,15 @@ int pk_scan(const Fr* in, Fr* out, uint64_t n, bool mul, bool suffix, bool exclu
   return PLK_OK;
 }
 
-int pk_coset3_combine(const Fr* in, uint64_t n2, const Fr* comb, Fr* out, hipStream_t s) {
-  hipLaunchKernelGGL(k_coset3_combine, dim3(blocks_for(n2, 256)), dim3(256), 0, s, in, n2, comb[0],
-                     comb[1], comb[2], comb[3], comb[4], comb[5], out);
+int pk_coset_combine(const Fr* in, uint64_t n, int blocks, const CombineMat& mat, Fr* out,
+                     hipStream_t s) {
+  const dim3 grid(blocks_for(n, 256));
+  if (blocks == kQBlocks)
+    hipLaunchKernelGGL((k_coset_combine<kQBlocks>), grid, dim3(256), 0, s, in, n, mat, out);
+  else if (blocks == kQBlocksSmall)
+    hipLaunchKernelGGL((k_coset_combine<kQBlocksSmall>), grid, dim3(256), 0, s, in, n, mat, out);
+  else
+    return PLK_E_ARG;
   PLK_HIP_TRY(hipGetLastError());
   return PLK_OK;
 }

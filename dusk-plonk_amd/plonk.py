@@ -40,7 +40,7 @@ ABI_SYMBOLS = (
     "plk_ntt_dev", "plk_ntt_batch_dev", "plk_srs_setup", "plk_srs_load", "plk_srs_destroy",
     "plk_srs_len", "plk_srs_points", "plk_msm", "plk_commit", "plk_commit_dev",
     "plk_srs_last_msm_stats", "plk_debug_field_op", "plk_debug_rx_op", "plk_debug_g1r_op",
-    "plk_commit_batch_dev",
+    "plk_debug_block_eval", "plk_commit_batch_dev",
     "plk_commit_batch_dev_part",
     "plk_srs_setup_range", "plk_g1_sum", "plk_msm_sharded", "plk_srs_msm_stats_reset",
     "plk_srs_cum_msm_stats", "plk_ntt_stream", "plk_aggregate_witness",
@@ -118,6 +118,7 @@ def _lib():
             "plk_debug_field_op": (i32, [vp, i32, i32, vp, vp, vp, sz]),
             "plk_debug_rx_op": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, sz]),
             "plk_debug_g1r_op": (i32, [vp, i32, vp, vp, vp, vp, sz]),
+            "plk_debug_block_eval": (i32, [vp, vp, sz, vp, sz, C.POINTER(i32)]),
             "plk_commit_batch_dev": (i32, [vp, vp, vp, sz, vp, vp, vp]),
             "plk_commit_batch_dev_part": (i32, [vp, vp, vp, sz, u32, u32, vp, vp, vp]),
             "plk_srs_setup_range": (i32, [vp, vp, u64, sz, vp, pp]),

@@ -389,6 +389,13 @@ int plk_debug_rx_op(plk_ctx* ctx, int field, int op, const uint32_t* a, const ui
  * q may be NULL for the ops of p alone. */
 int plk_debug_g1r_op(plk_ctx* ctx, int op, const uint32_t* p, const uint32_t* q,
                      const uint32_t* flags, uint32_t* out, size_t n);
+/* The prover's forward block transform: the polynomial of `len` <= n + 8 coefficients
+ * (Montgomery form) evaluated on the blocks of the key's quotient domain, the cosets
+ * g w_8n^m H_n, m < blocks (5; 6 for n = 8): out[m * n + u] = p(g w_8n^m w_n^u), the point
+ * 8u + m of the reference's g H_8n. out holds blocks * n values; *blocks_out (may be NULL)
+ * receives the block count. out == NULL only reports the block count. */
+int plk_debug_block_eval(plk_key* key, const uint64_t* coef, size_t len, uint64_t* out,
+                         size_t out_cap, int* blocks_out);
 
 #ifdef __cplusplus
 }
