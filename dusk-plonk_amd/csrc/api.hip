@@ -93,6 +93,7 @@ int plk_ctx_destroy(plk_ctx* ctx) {
     DeviceGuard g(ctx->device);
     (void)stream_wait(ctx->stream);
     ctx->domains.clear();
+    msm_var_ws_delete(ctx->var_ws);
     (void)hipStreamDestroy(ctx->stream);
   }
   delete ctx;

@@ -137,11 +137,17 @@ struct plk_srs {
   ~plk_srs();
 };
 
+namespace plk {
+struct VarMsmWs;
+}
+
 struct plk_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
   std::map<uint32_t, std::unique_ptr<plk_domain>> domains;
   std::mutex mu;
+  // workspace of the variable-base MSM (msm_var.hip), made on first use, freed with the context
+  plk::VarMsmWs* var_ws = nullptr;
 };
 
 namespace plk {
@@ -249,6 +255,15 @@ int msm_run_batch(plk_srs* s, MsmWorkspace& w, const Fr* const* d_scalars, const
 // parts > 1 a wide bucket set, 2^(c-1) above the LDS histogram's range, and >= 2^14 buckets
 // per part)
 bool msm_parts_ok(const plk_srs* s, uint32_t parts);
+// Variable-base MSM (msm_var.hip), device pointers, on `stream`: outs[k] = sum over
+// i in [starts[k], starts[k] + lens[k]) of scalars[i] * points[i], k < count <= kMaxSlots, as one
+// batch. d_points: n points in the ABI layout (plk_g1), d_scalars: n Montgomery scalars. The
+// kernels are stream-ordered; the call returns after the host tail (it waits for the stream).
+// PLK_E_ARG when a finite point is off the curve or not canonical.
+int msm_var_run(plk_ctx* ctx, const plk_g1* d_points, const Fr* d_scalars, size_t n,
+                const size_t* starts, const size_t* lens, size_t count, plk_g1* outs,
+                hipStream_t stream);
+void msm_var_ws_delete(VarMsmWs* w);
 MsmWorkspace* msm_workspace_new();
 void msm_workspace_delete(MsmWorkspace* w);
 const MsmStats& msm_workspace_stats(const MsmWorkspace& w);

@@ -1326,7 +1326,7 @@ static Fp fp_rx_to_r(Fp x) {
   k.v[11] = 1u << (32 - SH);  // 2^(384 - SH) (< p)
   return fe_mul(x, k);
 }
-static G1xyzz rx_to_r_domain(const G1xyzz& p) {
+G1xyzz rx_to_r_domain(const G1xyzz& p) {
   G1xyzz r;
   r.X = fp_rx_to_r(p.X);
   r.Y = fp_rx_to_r(p.Y);

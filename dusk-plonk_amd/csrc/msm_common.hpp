@@ -169,6 +169,10 @@ inline int lane_tail_policy(uint64_t n) {
   return 0;
 }
 
+// R'-domain [0, 2p) packed XYZZ coordinates (ffr.hpp), as the reduction kernels store them ->
+// canonical R-domain (msm.hip): what the host tails read back
+G1xyzz rx_to_r_domain(const G1xyzz& p);
+
 // k_accumulate (msm_acc.hip) over grid.x * 256 task lanes per slot (grid.y = slots), stamped
 // with the start / stop events ev0 / ev1 by the dispatch itself
 void launch_accumulate(bool has_inf, bool lone, dim3 grid, hipStream_t stream, hipEvent_t ev0,

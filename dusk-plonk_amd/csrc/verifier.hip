@@ -1,0 +1,617 @@
+// verifier.hip — Verifier::new and everything of Verifier::verify up to the pairing
+// (/root/reference/src/verifier.rs:25-81, src/prover/proof.rs:70-591,
+// commitment_scheme.rs:24-152), batched over many proofs of one circuit.
+//
+// One proof's check is e(C, H) == e(W, [tau]H) with C and W linear combinations of the 15 key
+// commitments, the generator and the proof's 11 commitments. Any number of proofs fold into
+// one such pair with random weights rho_j: (sum_j rho_j C_j, sum_j rho_j W_j).
+//  1. Host: the merlin replay of every proof (transcript.hpp), spread over up to 16 threads.
+//     t_eval is absorbed in mid-replay, so the host computes it — with Z_H(z), L_1(z) and the
+//     barycentric PI(z), their inversions batched into one per proof.
+//  2. GPU, k_fold_scalars: one lane per proof expands C_j and W_j into scalars on the points
+//     — t_comm, r_comm, both AggregateProof::flatten sums and the u batching flattened, so no
+//     intermediate point is formed. k_fold_shared sums the 16 shared scalars (key commitments
+//     and generator) over the proofs.
+//  3. GPU: both sums as one variable-base MSM batch (msm_var.hip) over 16 + 11 count and
+//     2 count points.
+// The pairing stays with the caller: no G2 or pairing code lives here.
+#include <hip/hip_runtime.h>
+#include <sys/random.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cstring>
+#include <new>
+#include <random>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "internal.hpp"
+#include "msm_common.hpp"
+#include "transcript.hpp"
+
+using namespace plk;
+
+namespace plk {
+namespace {
+
+constexpr int kShared = 16;  // 15 key commitments + the generator
+constexpr int kPerProof = 11;
+
+// What the replay hands to the GPU for one proof (Montgomery form).
+struct FoldIn {
+  Fr ev[16];  // plk_proof order: a b c d a_next b_next d_next q_arith q_c q_l q_r s1 s2 s3 r perm
+  Fr ch[11];  // beta gamma alpha range logic fixed variable z v_a v_b u
+  Fr t_eval, l1, zn, rho;
+};
+
+struct FoldConst {
+  Fr omega, ed;  // the domain generator; the JubJub d = -10240 / 10241
+};
+
+PLK_HD Fr fr_small(uint32_t k) {
+  Fr r = fe_zero<FrCfg>();
+  r.v[0] = k;
+  return fe_to_mont(r);
+}
+
+PLK_HD Fr fr_delta(const Fr& f) {  // f (f - 1) (f - 2) (f - 3)
+  const Fr one = fe_one<FrCfg>();
+  const Fr f1 = fe_sub(f, one), f2 = fe_sub(f1, one), f3 = fe_sub(f2, one);
+  return fe_mul(fe_mul(f, f1), fe_mul(f2, f3));
+}
+
+// The scalars of rho (C_j, W_j) on the points (tests/verifier_pair.py states the same algebra):
+// shared[0..14] on the key commitments (q_m q_l q_r q_o q_c q_4 q_arith q_range q_logic
+// q_fixed_group_add q_variable_group_add s_sigma_1..4), shared[15] on the generator, pr[0..10] on
+// the proof's commitments in plk_proof order, ws[0..1] on (w_z_chall_comm, w_z_chall_w_comm) for W.
+PLK_HD void fold_scalars(const FoldIn& in, const FoldConst& k, Fr* shared, size_t shared_stride,
+                        Fr* pr, Fr* ws) {
+#define M fe_mul
+#define A fe_add
+#define S fe_sub
+  const Fr &beta = in.ch[0], &gamma = in.ch[1], &alpha = in.ch[2], &rs = in.ch[3], &ls = in.ch[4],
+           &fs = in.ch[5], &vs = in.ch[6], &z = in.ch[7], &va = in.ch[8], &vb = in.ch[9],
+           &u = in.ch[10];
+  const Fr &a = in.ev[0], &b = in.ev[1], &c = in.ev[2], &d = in.ev[3], &an = in.ev[4],
+           &bn = in.ev[5], &dn = in.ev[6], &qar = in.ev[7], &qc = in.ev[8], &ql = in.ev[9],
+           &qr = in.ev[10], &s1 = in.ev[11], &s2 = in.ev[12], &s3 = in.ev[13], &rp = in.ev[14],
+           &pe = in.ev[15];
+  const Fr one = fe_one<FrCfg>();
+  // every scalar leaves through these, times the proof's weight
+  auto SH = [&](int i, const Fr& val) { shared[(size_t)i * shared_stride] = fe_mul(val, in.rho); };
+  auto PR = [&](int i, const Fr& val) { pr[i] = fe_mul(val, in.rho); };
+  const Fr va2 = M(va, va), va3 = M(va2, va), va4 = M(va2, va2), va5 = M(va4, va), va6 = M(va3, va3),
+           va7 = M(va6, va), va8 = M(va4, va4);
+  const Fr vb2 = M(vb, vb), vb3 = M(vb2, vb);
+  const Fr four = fr_small(4);
+  // r_comm (proof.rs:459-527), every term times va (its place in the aggregate)
+  const Fr vq = M(va, qar);
+  SH(0, M(vq, M(a, b)));
+  SH(1, M(vq, a));
+  SH(2, M(vq, b));
+  SH(3, M(vq, c));
+  SH(4, vq);
+  SH(5, M(vq, d));
+  SH(6, fe_zero<FrCfg>());
+  {  // range::linearize
+    const Fr kap = M(rs, rs), kap2 = M(kap, kap), kap3 = M(kap2, kap);
+    Fr rr = fr_delta(S(c, M(four, d)));
+    rr = A(rr, M(fr_delta(S(b, M(four, c))), kap));
+    rr = A(rr, M(fr_delta(S(a, M(four, b))), kap2));
+    rr = A(rr, M(fr_delta(S(dn, M(four, a))), kap3));
+    SH(7, M(va, M(rr, rs)));
+  }
+  {  // logic::linearize
+    const Fr k1 = M(ls, ls), k2 = M(k1, k1), k3 = M(k2, k1), k4 = M(k2, k2);
+    const Fr qa = S(an, M(four, a)), qb = S(bn, M(four, b)), qd = S(dn, M(four, d));
+    const Fr& w = c;
+    const Fr c18 = fr_small(18), c81 = fr_small(81), c83 = fr_small(83), c9 = fr_small(9),
+             c3 = fr_small(3), c2 = fr_small(2);
+    const Fr sab = A(qa, qb);
+    // f = w (w (4 w - 18 (qa + qb) + 81) + 18 (qa^2 + qb^2) - 81 (qa + qb) + 83)
+    Fr f = A(S(M(four, w), M(c18, sab)), c81);
+    f = M(w, f);
+    f = A(f, M(c18, A(M(qa, qa), M(qb, qb))));
+    f = A(S(f, M(c81, sab)), c83);
+    f = M(w, f);
+    // 3 (qa + qb + qd) - 2 f + q_c (9 qd - 3 (qa + qb))
+    Fr xa = S(M(c3, A(sab, qd)), M(c2, f));
+    xa = A(xa, M(qc, S(M(c9, qd), M(c3, sab))));
+    Fr lt = fr_delta(qa);
+    lt = A(lt, M(fr_delta(qb), k1));
+    lt = A(lt, M(fr_delta(qd), k2));
+    lt = A(lt, M(S(w, M(qa, qb)), k3));
+    lt = A(lt, M(xa, k4));
+    SH(8, M(va, M(lt, ls)));
+  }
+  {  // curve_scalar::linearize (fixed base)
+    const Fr k1 = M(fs, fs), k2 = M(k1, k1), k3 = M(k2, k1);
+    const Fr &ax = a, &axn = an, &ay = b, &ayn = bn, &xya = c, &acc = d, &accn = dn;
+    const Fr &xb = ql, &yb = qr, &xyb = qc;
+    const Fr bit = S(accn, A(acc, acc));
+    const Fr ya = A(M(M(bit, bit), S(yb, one)), one);
+    const Fr xa = M(xb, bit);
+    const Fr prod = M(M(xya, ax), M(ay, k.ed));
+    Fr w = M(M(bit, S(bit, one)), A(bit, one));
+    w = A(w, M(S(M(bit, xyb), xya), k1));
+    w = A(w, M(S(A(axn, M(axn, prod)), A(M(ax, ya), M(ay, xa))), k2));
+    w = A(w, M(S(S(ayn, M(ayn, prod)), A(M(ay, ya), M(ax, xa))), k3));
+    SH(9, M(va, M(w, fs)));
+  }
+  {  // curve_addition::linearize (variable base)
+    const Fr k1 = M(vs, vs), k2 = M(k1, k1);
+    const Fr &x1 = a, &x3 = an, &y1 = b, &y3 = bn, &x2 = c, &y2 = d, &x1y2 = dn;
+    const Fr dp = M(M(k.ed, x1y2), M(y1, x2));
+    Fr w = S(M(x1, y2), x1y2);
+    w = A(w, M(S(A(x1y2, M(y1, x2)), A(x3, M(x3, dp))), k1));
+    w = A(w, M(S(A(M(y1, y2), M(x1, x2)), S(y3, M(y3, dp))), k2));
+    SH(10, M(va, M(w, vs)));
+  }
+  // permutation::linearize
+  const Fr b0 = A(A(a, M(beta, s1)), gamma), b1 = A(A(b, M(beta, s2)), gamma),
+           b2 = A(A(c, M(beta, s3)), gamma);
+  const Fr bz = M(beta, z);
+  Fr x = M(A(A(a, bz), gamma), A(A(b, M(fr_small(7), bz)), gamma));
+  x = M(x, A(A(c, M(fr_small(13), bz)), gamma));
+  x = M(x, A(A(d, M(fr_small(17), bz)), gamma));
+  x = M(x, alpha);
+  const Fr zc = A(x, M(in.l1, M(alpha, alpha)));  // on z_comm, inside r_comm
+  const Fr y = fe_neg(M(M(M(b0, b1), M(b2, beta)), M(pe, alpha)));
+  SH(11, va6);
+  SH(12, va7);
+  SH(13, va8);
+  SH(14, M(va, y));
+  // the evaluations of both flattened aggregates go on the generator, negated
+  Fr eva = A(in.t_eval, M(va, rp));
+  eva = A(eva, M(va2, a));
+  eva = A(eva, M(va3, b));
+  eva = A(eva, M(va4, c));
+  eva = A(eva, M(va5, d));
+  eva = A(eva, M(va6, s1));
+  eva = A(eva, M(va7, s2));
+  eva = A(eva, M(va8, s3));
+  Fr evb = A(pe, M(vb, an));
+  evb = A(evb, M(vb2, bn));
+  evb = A(evb, M(vb3, dn));
+  SH(15, fe_neg(A(eva, M(u, evb))));
+  const Fr zn2 = M(in.zn, in.zn);
+  PR(0, A(va2, M(u, vb)));    // a_comm
+  PR(1, A(va3, M(u, vb2)));   // b_comm
+  PR(2, va4);                 // c_comm
+  PR(3, A(va5, M(u, vb3)));   // d_comm
+  PR(4, A(M(va, zc), u));        // z_comm
+  PR(5, one);                    // t_low .. t_4: [t] = sum_i z^(i n) t_i, times va^0
+  PR(6, in.zn);
+  PR(7, zn2);
+  PR(8, M(zn2, in.zn));
+  PR(9, z);                      // w_z_chall_comm at z
+  PR(10, M(u, M(z, k.omega)));   // w_z_chall_w_comm at z omega, times u
+  ws[0] = in.rho;
+  ws[1] = M(u, in.rho);
+#undef M
+#undef A
+#undef S
+}
+
+// scalars: [16 shared][11 per proof][2 per proof]; tmp[k * count + j] = proof j's share of
+// shared scalar k
+__global__ void __launch_bounds__(128) k_fold_scalars(const FoldIn* __restrict__ in, FoldConst k,
+                                                      uint32_t count, Fr* __restrict__ scalars,
+                                                      Fr* __restrict__ tmp) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= count) return;
+  fold_scalars(in[j], k, tmp + j, count, scalars + kShared + (size_t)kPerProof * j,
+               scalars + kShared + (size_t)kPerProof * count + 2 * (size_t)j);
+}
+
+// scalars[k] = sum_j tmp[k * count + j], k = blockIdx.x
+__global__ void __launch_bounds__(256) k_fold_shared(const Fr* __restrict__ tmp, uint32_t count,
+                                                     Fr* __restrict__ scalars) {
+  __shared__ Fr sh[256];
+  const uint32_t k = blockIdx.x, t = threadIdx.x;
+  Fr acc = fe_zero<FrCfg>();
+  for (uint32_t j = t; j < count; j += 256) acc = fe_add(acc, tmp[(size_t)k * count + j]);
+  sh[t] = acc;
+  __syncthreads();
+  for (uint32_t h = 128; h >= 1; h >>= 1) {
+    if (t < h) sh[t] = fe_add(sh[t], sh[t + h]);
+    __syncthreads();
+  }
+  if (t == 0) scalars[k] = sh[0];
+}
+
+bool fr_abi_canonical(const plk_fr& a) {
+  uint64_t borrow = 0;
+  for (int i = 0; i < 4; ++i) {
+    const uint64_t p = (uint64_t)FrCfg::P[2 * i] | ((uint64_t)FrCfg::P[2 * i + 1] << 32);
+    const unsigned __int128 t = (unsigned __int128)a.l[i] - p - borrow;
+    borrow = (uint64_t)(t >> 64) & 1u;
+  }
+  return borrow != 0;  // a < r
+}
+
+Fr fr_from_abi(const plk_fr& a) {
+  Fr r;
+  for (int i = 0; i < 4; ++i) {
+    r.v[2 * i] = (uint32_t)a.l[i];
+    r.v[2 * i + 1] = (uint32_t)(a.l[i] >> 32);
+  }
+  return r;
+}
+
+void fr_to_abi(const Fr& a, plk_fr* out) {
+  for (int i = 0; i < 4; ++i) out->l[i] = (uint64_t)a.v[2 * i] | ((uint64_t)a.v[2 * i + 1] << 32);
+}
+
+}  // namespace
+}  // namespace plk
+
+struct plk_verifier {
+  std::string label;
+  uint64_t n = 0, m = 0;
+  uint32_t log_n = 0;
+  plk_g1 comms[15];
+  std::vector<uint64_t> pi_idx;
+  std::vector<Fr> pi_winv;  // omega^-index per public input
+  Fr omega, n_inv;
+  FoldConst consts;
+  Transcript base{""};  // Transcript::base(label, vk, m): what every proof's replay starts from
+  double replay_ms = 0.0;
+  float gpu_ms = 0.f;
+  // fold buffers (device), kept between calls
+  DevBuf d_points, d_scalars, d_in, d_tmp;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  int device = -1;
+};
+
+namespace plk {
+namespace {
+
+// The transcript replay of Proof::verify for one proof: the 11 challenges and what the scalar
+// kernel needs besides (t_eval, L_1(z), z^n). PLK_E_ARG on a non-canonical value, z_h(z) = 0 or
+// z = 1.
+int replay(const plk_verifier* v, const plk_proof& p, const plk_fr* pis, FoldIn& o) {
+  const plk_fr* evals = &p.a_eval;
+  for (int i = 0; i < 16; ++i) {
+    if (!fr_abi_canonical(evals[i])) return PLK_E_ARG;
+    o.ev[i] = fr_from_abi(evals[i]);
+  }
+  const size_t npi = v->pi_idx.size();
+  std::vector<Fr> pi(npi);
+  for (size_t i = 0; i < npi; ++i) {
+    if (!fr_abi_canonical(pis[i])) return PLK_E_ARG;
+    pi[i] = fr_from_abi(pis[i]);
+  }
+  Transcript t = v->base;
+  for (size_t i = 0; i < npi; ++i) t.append_scalar("pi", pi[i]);
+  t.append_commitment("a_w", p.a_comm);
+  t.append_commitment("b_w", p.b_comm);
+  t.append_commitment("c_w", p.c_comm);
+  t.append_commitment("d_w", p.d_comm);
+  const Fr beta = t.challenge_scalar("beta");
+  t.append_scalar("beta", beta);
+  const Fr gamma = t.challenge_scalar("gamma");
+  t.append_commitment("z", p.z_comm);
+  const Fr alpha = t.challenge_scalar("alpha");
+  o.ch[0] = beta;
+  o.ch[1] = gamma;
+  o.ch[2] = alpha;
+  o.ch[3] = t.challenge_scalar("range separation challenge");
+  o.ch[4] = t.challenge_scalar("logic separation challenge");
+  o.ch[5] = t.challenge_scalar("fixed base separation challenge");
+  o.ch[6] = t.challenge_scalar("variable base separation challenge");
+  t.append_commitment("t_low", p.t_low_comm);
+  t.append_commitment("t_mid", p.t_mid_comm);
+  t.append_commitment("t_high", p.t_high_comm);
+  t.append_commitment("t_4", p.t_4_comm);
+  const Fr z = t.challenge_scalar("z_challenge");
+  o.ch[7] = z;
+
+  const Fr one = fe_one<FrCfg>();
+  Fr zn = z;
+  for (uint32_t i = 0; i < v->log_n; ++i) zn = fe_sqr(zn);
+  const Fr z_h = fe_sub(zn, one), zm1 = fe_sub(z, one);
+  if (fe_is_zero(z_h) || fe_is_zero(zm1)) return PLK_E_ARG;
+  // one inversion for z_h, z - 1 and the barycentric denominators omega^-i z - 1 (none is zero:
+  // z is not in the domain). Zero public inputs are skipped, as in the reference (proof.rs:558).
+  std::vector<Fr> den;
+  den.reserve(npi + 2);
+  den.push_back(z_h);
+  den.push_back(zm1);
+  for (size_t i = 0; i < npi; ++i)
+    if (!fe_is_zero(pi[i])) den.push_back(fe_sub(fe_mul(v->pi_winv[i], z), one));
+  std::vector<Fr> pref(den.size());
+  Fr acc = one;
+  for (size_t i = 0; i < den.size(); ++i) {
+    pref[i] = acc;
+    acc = fe_mul(acc, den[i]);
+  }
+  Fr inv = fe_inv(acc);
+  for (size_t i = den.size(); i-- > 0;) {
+    const Fr di = den[i];
+    den[i] = fe_mul(inv, pref[i]);
+    inv = fe_mul(inv, di);
+  }
+  const Fr zh_inv = den[0];
+  const Fr l1 = fe_mul(fe_mul(z_h, v->n_inv), den[1]);  // z_h / (n (z - 1))
+  Fr pi_eval = fe_zero<FrCfg>();
+  size_t k = 2;
+  for (size_t i = 0; i < npi; ++i)
+    if (!fe_is_zero(pi[i])) pi_eval = fe_add(pi_eval, fe_mul(pi[i], den[k++]));
+  pi_eval = fe_mul(pi_eval, fe_mul(z_h, v->n_inv));
+  // t_eval (proof.rs:386-440)
+  const Fr *e = o.ev, &a = e[0], &b = e[1], &c = e[2], &d = e[3], &s1 = e[11], &s2 = e[12],
+           &s3 = e[13], &rp = e[14], &pe = e[15];
+  const Fr b0 = fe_add(fe_add(a, fe_mul(beta, s1)), gamma);
+  const Fr b1 = fe_add(fe_add(b, fe_mul(beta, s2)), gamma);
+  const Fr b2 = fe_add(fe_add(c, fe_mul(beta, s3)), gamma);
+  const Fr b3 = fe_mul(fe_mul(fe_add(d, gamma), pe), alpha);
+  const Fr b_term = fe_mul(fe_mul(b0, b1), fe_mul(b2, b3));
+  const Fr c_term = fe_mul(l1, fe_mul(alpha, alpha));
+  const Fr t_eval = fe_mul(fe_sub(fe_sub(fe_add(rp, pi_eval), b_term), c_term), zh_inv);
+  o.t_eval = t_eval;
+  o.l1 = l1;
+  o.zn = zn;
+  t.append_scalar("a_eval", e[0]);
+  t.append_scalar("b_eval", e[1]);
+  t.append_scalar("c_eval", e[2]);
+  t.append_scalar("d_eval", e[3]);
+  t.append_scalar("a_next_eval", e[4]);
+  t.append_scalar("b_next_eval", e[5]);
+  t.append_scalar("d_next_eval", e[6]);
+  t.append_scalar("s_sigma_1_eval", e[11]);
+  t.append_scalar("s_sigma_2_eval", e[12]);
+  t.append_scalar("s_sigma_3_eval", e[13]);
+  t.append_scalar("q_arith_eval", e[7]);
+  t.append_scalar("q_c_eval", e[8]);
+  t.append_scalar("q_l_eval", e[9]);
+  t.append_scalar("q_r_eval", e[10]);
+  t.append_scalar("perm_eval", e[15]);
+  t.append_scalar("t_eval", t_eval);
+  t.append_scalar("r_eval", e[14]);
+  o.ch[8] = t.challenge_scalar("v_challenge");
+  o.ch[9] = t.challenge_scalar("v_challenge");
+  t.append_commitment("w_z", p.w_z_chall_comm);
+  t.append_commitment("w_z_w", p.w_z_chall_w_comm);
+  o.ch[10] = t.challenge_scalar("batch");
+  o.rho = one;
+  return PLK_OK;
+}
+
+// The G1 generator (Montgomery form, ABI layout)
+plk_g1 g1_generator() {
+  static const uint32_t gx[12] = {0xdb22c6bbu, 0xfb3af00au, 0xf97a1aefu, 0x6c55e83fu,
+                                  0x171bac58u, 0xa14e3a3fu, 0x9774b905u, 0xc3688c4fu,
+                                  0x4fa9ac0fu, 0x2695638cu, 0x3197d794u, 0x17f1d3a7u};
+  static const uint32_t gy[12] = {0x46c5e7e1u, 0x0caa2329u, 0xa2888ae4u, 0xd03cc744u,
+                                  0x2c04b3edu, 0x00db18cbu, 0xd5d00af6u, 0xfcf5e095u,
+                                  0x741d8ae4u, 0xa09e30edu, 0xe3aaa0f1u, 0x08b3f481u};
+  Fp x, y;
+  for (int i = 0; i < 12; ++i) {
+    x.v[i] = gx[i];
+    y.v[i] = gy[i];
+  }
+  x = fe_to_mont(x);
+  y = fe_to_mont(y);
+  plk_g1 g{};
+  for (int i = 0; i < 6; ++i) {
+    g.x[i] = (uint64_t)x.v[2 * i] | ((uint64_t)x.v[2 * i + 1] << 32);
+    g.y[i] = (uint64_t)y.v[2 * i] | ((uint64_t)y.v[2 * i + 1] << 32);
+  }
+  return g;
+}
+
+// rho_0 = 1, rho_j = 128 bits of a merlin transcript over every proof's u challenge and 32 bytes
+// of OS entropy: nobody who fixed the proofs beforehand knows the weights
+int random_weights(std::vector<FoldIn>& in) {
+  uint8_t seed[32];
+  size_t got = 0;
+  while (got < sizeof seed) {
+    const ssize_t r = getrandom(seed + got, sizeof seed - got, 0);
+    if (r <= 0) break;
+    got += (size_t)r;
+  }
+  if (got < sizeof seed) {
+    std::random_device rd;
+    for (size_t i = 0; i < sizeof seed; i += 4) {
+      const uint32_t x = rd();
+      std::memcpy(seed + i, &x, 4);
+    }
+  }
+  Transcript t("plk-verifier-fold");
+  t.append_u64("count", in.size());
+  for (const FoldIn& f : in) t.append_scalar("u", f.ch[10]);
+  t.append_message("entropy", seed, sizeof seed);
+  for (size_t j = 1; j < in.size(); ++j) {
+    uint8_t b[16];
+    t.challenge_bytes("rho", b, 16);
+    Fr r = fe_zero<FrCfg>();
+    for (int i = 0; i < 4; ++i)
+      r.v[i] = (uint32_t)b[4 * i] | ((uint32_t)b[4 * i + 1] << 8) | ((uint32_t)b[4 * i + 2] << 16) |
+               ((uint32_t)b[4 * i + 3] << 24);
+    in[j].rho = fe_to_mont(r);
+  }
+  return PLK_OK;
+}
+
+}  // namespace
+}  // namespace plk
+
+#define PLK_V_BEGIN try {
+#define PLK_V_END                   \
+  }                                 \
+  catch (const std::bad_alloc&) {   \
+    return PLK_E_OOM;               \
+  }                                 \
+  catch (...) {                     \
+    return PLK_E_DEVICE;            \
+  }
+
+extern "C" {
+
+int plk_verifier_create(const char* label, uint64_t n, uint64_t m, const plk_g1 commitments[15],
+                        const uint64_t* pi_indexes, size_t pi_count, plk_verifier** out) {
+  PLK_V_BEGIN
+  if (!out) return PLK_E_ARG;
+  *out = nullptr;
+  if (!label || !commitments || (pi_count && !pi_indexes)) return PLK_E_ARG;
+  if (n < 2 || n > (1ull << 27) || (n & (n - 1)) || pi_count > n) return PLK_E_ARG;
+  for (size_t i = 0; i < pi_count; ++i)
+    if (pi_indexes[i] >= n || (i && pi_indexes[i] <= pi_indexes[i - 1])) return PLK_E_ARG;
+  std::unique_ptr<plk_verifier> v(new plk_verifier());
+  v->label = label;
+  v->n = n;
+  v->m = m;
+  v->log_n = (uint32_t)__builtin_ctzll(n);
+  std::memcpy(v->comms, commitments, sizeof v->comms);
+  v->pi_idx.assign(pi_indexes, pi_indexes + pi_count);
+  fr_root_of_unity(v->log_n, v->omega);
+  const Fr winv = fe_inv(v->omega);
+  v->pi_winv.resize(pi_count);
+  for (size_t i = 0; i < pi_count; ++i) v->pi_winv[i] = fe_pow_u64(winv, pi_indexes[i]);
+  v->n_inv = fe_inv(fr_small((uint32_t)n));
+  v->consts.omega = v->omega;
+  v->consts.ed = fe_neg(fe_mul(fr_small(10240), fe_inv(fr_small(10241))));
+  // Transcript::base(label, vk, constraints) (prover.rs:54-55, verifier.rs:33-34)
+  Transcript t(v->label);
+  static const char dom[] = "circuit_size";
+  t.append_message("dom-sep", reinterpret_cast<const uint8_t*>(dom), sizeof(dom) - 1);
+  t.append_u64("n", m);
+  static const char* labels[15] = {"q_m", "q_l", "q_r", "q_o", "q_c", "q_4", "q_arith", "q_range",
+                                   "q_logic", "q_fixed_group_add", "q_variable_group_add",
+                                   "s_sigma_1", "s_sigma_2", "s_sigma_3", "s_sigma_4"};
+  for (int i = 0; i < 15; ++i) t.append_commitment(labels[i], v->comms[i]);
+  v->base = t;
+  *out = v.release();
+  return PLK_OK;
+  PLK_V_END
+}
+
+int plk_verifier_destroy(plk_verifier* v) {
+  PLK_V_BEGIN
+  if (!v) return PLK_E_ARG;
+  if (v->device >= 0) {
+    DeviceGuard g(v->device);
+    if (v->e0) (void)hipEventDestroy(v->e0);
+    if (v->e1) (void)hipEventDestroy(v->e1);
+    delete v;  // frees the device buffers on their device
+    return PLK_OK;
+  }
+  delete v;
+  return PLK_OK;
+  PLK_V_END
+}
+
+int plk_verifier_challenges(const plk_verifier* v, const plk_proof* proof, const plk_fr* public_inputs,
+                            plk_fr out[11]) {
+  PLK_V_BEGIN
+  if (!v || !proof || !out || (!public_inputs && !v->pi_idx.empty())) return PLK_E_ARG;
+  FoldIn in;
+  const int st = replay(v, *proof, public_inputs, in);
+  if (st != PLK_OK) return st;
+  for (int i = 0; i < 11; ++i) fr_to_abi(in.ch[i], &out[i]);
+  return PLK_OK;
+  PLK_V_END
+}
+
+int plk_verifier_fold(plk_ctx* ctx, plk_verifier* v, const plk_proof* proofs,
+                      const plk_fr* public_inputs, size_t count, const plk_fr* weights,
+                      plk_kzg_pair* out) {
+  PLK_V_BEGIN
+  if (!ctx || !v || !proofs || !out || count == 0 || count > (1u << 24)) return PLK_E_ARG;
+  const size_t npi = v->pi_idx.size();
+  if (npi && !public_inputs) return PLK_E_ARG;
+  if (weights)
+    for (size_t j = 0; j < count; ++j)
+      if (!fr_abi_canonical(weights[j])) return PLK_E_ARG;
+  // 1. the transcript replays, on up to 16 host threads
+  const auto t0 = std::chrono::steady_clock::now();
+  std::vector<FoldIn> in(count);
+  const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
+  const size_t nth = std::min<size_t>({16, hw, (count + 7) / 8});
+  std::vector<int> status(std::max<size_t>(nth, 1), PLK_OK);
+  auto work = [&](size_t th) {
+    for (size_t j = th; j < count; j += std::max<size_t>(nth, 1)) {
+      const int st = replay(v, proofs[j], public_inputs ? public_inputs + j * npi : nullptr, in[j]);
+      if (st != PLK_OK) {
+        status[th] = st;
+        return;
+      }
+    }
+  };
+  if (nth <= 1) {
+    work(0);
+  } else {
+    std::vector<std::thread> workers;
+    workers.reserve(nth);
+    try {
+      for (size_t th = 0; th < nth; ++th) workers.emplace_back(work, th);
+    } catch (...) {
+      for (auto& w : workers) w.join();
+      throw;
+    }
+    for (auto& w : workers) w.join();
+  }
+  for (int st : status)
+    if (st != PLK_OK) return st;
+  if (weights) {
+    for (size_t j = 0; j < count; ++j) in[j].rho = fr_from_abi(weights[j]);
+  } else {
+    random_weights(in);
+  }
+  v->replay_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+
+  // 2. the points: [15 key commitments, generator][11 per proof][w_z, w_z_w per proof]
+  const size_t n_c = kShared + (size_t)kPerProof * count, n_pts = n_c + 2 * count;
+  std::vector<plk_g1> pts(n_pts);
+  std::memcpy(pts.data(), v->comms, sizeof v->comms);
+  pts[15] = g1_generator();
+  for (size_t j = 0; j < count; ++j) {
+    std::memcpy(&pts[kShared + kPerProof * j], &proofs[j].a_comm, kPerProof * sizeof(plk_g1));
+    pts[n_c + 2 * j] = proofs[j].w_z_chall_comm;
+    pts[n_c + 2 * j + 1] = proofs[j].w_z_chall_w_comm;
+  }
+  DeviceGuard g(ctx->device);
+  hipStream_t s = ctx->stream;
+  if (v->device >= 0 && v->device != ctx->device) return PLK_E_ARG;  // one GPU per verifier
+  v->device = ctx->device;
+  if (!v->e0) PLK_HIP_TRY(hipEventCreate(&v->e0));
+  if (!v->e1) PLK_HIP_TRY(hipEventCreate(&v->e1));
+  int st;
+  if ((st = v->d_points.alloc(n_pts * sizeof(plk_g1)))) return st;
+  if ((st = v->d_scalars.alloc(n_pts * sizeof(Fr)))) return st;
+  if ((st = v->d_in.alloc(count * sizeof(FoldIn)))) return st;
+  if ((st = v->d_tmp.alloc((size_t)kShared * count * sizeof(Fr)))) return st;
+  PLK_HIP_TRY(hipEventRecord(v->e0, s));
+  PLK_HIP_TRY(hipMemcpyAsync(v->d_points.ptr, pts.data(), n_pts * sizeof(plk_g1), hipMemcpyHostToDevice, s));
+  PLK_HIP_TRY(hipMemcpyAsync(v->d_in.ptr, in.data(), count * sizeof(FoldIn), hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(k_fold_scalars, dim3(cdiv(count, 128)), dim3(128), 0, s,
+                     (const FoldIn*)v->d_in.as<FoldIn>(), v->consts, (uint32_t)count,
+                     v->d_scalars.as<Fr>(), v->d_tmp.as<Fr>());
+  hipLaunchKernelGGL(k_fold_shared, dim3(kShared), dim3(256), 0, s, (const Fr*)v->d_tmp.as<Fr>(),
+                     (uint32_t)count, v->d_scalars.as<Fr>());
+  PLK_HIP_TRY(hipGetLastError());
+  // 3. both sums as one variable-base MSM batch
+  const size_t starts[2] = {0, n_c}, lens[2] = {n_c, 2 * count};
+  plk_g1 res[2];
+  st = msm_var_run(ctx, v->d_points.as<plk_g1>(), v->d_scalars.as<Fr>(), n_pts, starts, lens, 2, res, s);
+  PLK_HIP_TRY(hipEventRecord(v->e1, s));
+  PLK_HIP_TRY(stream_wait(s));
+  if (st != PLK_OK) return st;
+  (void)hipEventElapsedTime(&v->gpu_ms, v->e0, v->e1);
+  out->c = res[0];
+  out->w = res[1];
+  return PLK_OK;
+  PLK_V_END
+}
+
+int plk_verifier_last_fold_stats(const plk_verifier* v, double* replay_ms, float* gpu_ms) {
+  if (!v) return PLK_E_ARG;
+  if (replay_ms) *replay_ms = v->replay_ms;
+  if (gpu_ms) *gpu_ms = v->gpu_ms;
+  return PLK_OK;
+}
+
+}  // extern "C"

@@ -57,6 +57,9 @@ ABI_SYMBOLS = (
     "plk_prove", "plk_prover_create", "plk_prover_destroy", "plk_prover_stream",
     "plk_prover_prove", "plk_prover_msm_stats", "plk_prover_shard", "plk_prover_shard_buckets",
     "plk_proof_encode", "plk_proof_decode",
+    # variable-base MSM and the verifier (Verifier in dusk-plonk_amd/prover.py)
+    "plk_msm_points", "plk_msm_points_ranges", "plk_verifier_create", "plk_verifier_destroy",
+    "plk_verifier_challenges", "plk_verifier_fold", "plk_verifier_last_fold_stats",
 )
 
 
@@ -124,6 +127,8 @@ def _lib():
             "plk_srs_setup_range": (i32, [vp, vp, u64, sz, vp, pp]),
             "plk_g1_sum": (i32, [vp, sz, vp]),
             "plk_msm_sharded": (i32, [vp, i32, vp, sz, vp]),
+            "plk_msm_points": (i32, [vp, vp, vp, sz, vp]),
+            "plk_msm_points_ranges": (i32, [vp, vp, vp, sz, vp, vp, sz, vp]),
             "plk_srs_msm_stats_reset": (i32, [vp]),
             "plk_srs_cum_msm_stats": (i32, [vp, C.POINTER(C.c_double), C.POINTER(u64),
                                             C.POINTER(u64), C.POINTER(u64)]),
@@ -441,6 +446,38 @@ def msm_sharded(shards, scalars) -> Commitment:
     return Commitment(out)
 
 
+def msm_points_ranges(points, scalars, ranges, ctx: "Context | None" = None) -> list:
+    """Several variable-base MSMs over disjoint index ranges [(start, len), ...] of one point
+    array as one GPU batch (plk_msm_points_ranges); returns a Commitment per range."""
+    ctx = ctx or Context.default()
+    pts = np.ascontiguousarray(np.asarray(points, dtype=np.uint64).reshape(-1, 13))
+    vals = _as_fr_array(scalars) if len(scalars) else np.zeros((0, 4), dtype=np.uint64)
+    if pts.shape[0] != vals.shape[0]:
+        raise ValueError("msm_points: as many scalars as points")
+    k = len(ranges)
+    starts = (C.c_size_t * max(k, 1))(*[int(a) for a, _ in ranges])
+    lens = (C.c_size_t * max(k, 1))(*[int(n) for _, n in ranges])
+    outs = np.zeros((max(k, 1), 13), dtype=np.uint64)
+    _check(_lib().plk_msm_points_ranges(ctx.handle, _ptr(pts), _ptr(vals), pts.shape[0], starts,
+                                        lens, k, _ptr(outs)), "msm_points")
+    return [Commitment(outs[i]) for i in range(k)]
+
+
+def msm_points(points, scalars, ctx: "Context | None" = None) -> Commitment:
+    """msm_curve_addition(&[G1Affine], &[Fr]) for arbitrary affine points uint64[n, 13]
+    (proof.rs:507): plk_msm_points, the variable-base Pippenger. Identity points are skipped;
+    PlonkError(PLK_E_ARG) for a finite point off the curve."""
+    ctx = ctx or Context.default()
+    pts = np.ascontiguousarray(np.asarray(points, dtype=np.uint64).reshape(-1, 13))
+    vals = _as_fr_array(scalars) if len(scalars) else np.zeros((0, 4), dtype=np.uint64)
+    if pts.shape[0] != vals.shape[0]:
+        raise ValueError("msm_points: as many scalars as points")
+    out = np.zeros(13, dtype=np.uint64)
+    _check(_lib().plk_msm_points(ctx.handle, _ptr(pts), _ptr(vals), pts.shape[0], _ptr(out)),
+           "msm_points")
+    return Commitment(out)
+
+
 class PlonkParams:
     """zksnarks::plonk::PlonkParams<TatePairing> (the G1 side used by the prover).
 
@@ -507,6 +544,10 @@ class PlonkParams:
         out = np.zeros(13, dtype=np.uint64)
         _check(_lib().plk_msm(self._h, _ptr(vals), vals.shape[0], _ptr(out)), "msm")
         return Commitment(out)
+
+    def msm_points(self, points, scalars) -> Commitment:
+        """msm_curve_addition over arbitrary points (not this SRS) on this SRS's context."""
+        return msm_points(points, scalars, self.ctx)
 
     def commit_dev(self, d_ptr: int, length: int, stream: int = 0) -> Commitment:
         out = np.zeros(13, dtype=np.uint64)

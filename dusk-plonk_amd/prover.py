@@ -90,6 +90,11 @@ def _bind():
         "plk_prover_shard_buckets": [vp, i32, i32, vp, vp],
         "plk_proof_encode": [vp, vp, sz, C.POINTER(sz)],
         "plk_proof_decode": [vp, sz, vp],
+        "plk_verifier_create": [C.c_char_p, u64, u64, vp, vp, sz, pp],
+        "plk_verifier_destroy": [vp],
+        "plk_verifier_challenges": [vp, vp, vp, vp],
+        "plk_verifier_fold": [vp, vp, vp, vp, sz, vp, vp],
+        "plk_verifier_last_fold_stats": [vp, C.POINTER(C.c_double), C.POINTER(C.c_float)],
     }
     for name, args in sig.items():
         f = getattr(lib, name)
@@ -560,6 +565,85 @@ class VerifierData:
 
     def __init__(self, label: bytes, n: int, m: int, comms: np.ndarray, pi_indexes):
         self.label, self.n, self.m, self.comms, self.pi_indexes = label, n, m, comms, pi_indexes
+
+    def verifier(self, ctx=None) -> "Verifier":
+        return Verifier(self, ctx)
+
+
+class Verifier:
+    """zksnarks Verifier (src/verifier.rs) up to the pairing: ``fold`` returns the two G1 points
+    (C, W) of the final KZG check of a whole batch of proofs, e(C, H) == e(W, [tau]H), which the
+    caller finishes with its pairing library. Built from VerifierData; needs
+    no GPU until ``fold``."""
+
+    def __init__(self, vd: VerifierData, ctx=None):
+        self.vd, self.ctx = vd, ctx
+        comms = np.ascontiguousarray(vd.comms, dtype=np.uint64).reshape(15, 13)
+        k = len(vd.pi_indexes)
+        idx = (C.c_uint64 * max(1, k))(*[int(i) for i in vd.pi_indexes])
+        self._h = C.c_void_p()
+        _check(_bind().plk_verifier_create(vd.label, vd.n, vd.m, _ptr(comms), idx, k,
+                                           C.byref(self._h)), "Verifier::new")
+
+    def _pis(self, public_inputs, count: int):
+        """`count` lists of pi_count values (ints or Montgomery limbs) -> PlkFr array;
+        PlonkError(PLK_E_ARG) on a wrong length (InconsistentPublicInputsLen,
+        verifier.rs:51-56) before anything else runs."""
+        k = len(self.vd.pi_indexes)
+        if len(public_inputs) != count or any(len(p) != k for p in public_inputs):
+            raise PlonkError(2, "Verifier: InconsistentPublicInputsLen")
+        arr = (PlkFr * max(1, count * k))()
+        for j, p in enumerate(public_inputs):
+            for i, v in enumerate(p):
+                arr[j * k + i] = _fr(v)
+        return arr
+
+    def challenges(self, proof: "Proof", public_inputs) -> list:
+        """The transcript replay of Proof::verify: [beta, gamma, alpha, range, logic, fixed,
+        variable separation, z, v (aggregate), v (shifted), u] as canonical ints."""
+        pis = self._pis([list(public_inputs)], 1)
+        out = (PlkFr * 11)()
+        _check(_bind().plk_verifier_challenges(self._h, C.byref(proof.raw), pis, out),
+               "Verifier::challenges")
+        return [fr_int(out[i]) for i in range(11)]
+
+    def fold(self, proofs, public_inputs, weights=None):
+        """(C, W) as uint64[13] ABI points for the batch `proofs` (a list of Proof) with
+        `public_inputs` (one list per proof). weights: canonical ints / Montgomery limbs per
+        proof, or None for the sound random weights (plk_verifier_fold)."""
+        from .plonk import Context
+        count = len(proofs)
+        pis = self._pis(list(public_inputs), count)
+        if weights is not None and len(weights) != count:
+            raise PlonkError(2, "Verifier.fold: one weight per proof")
+        raw = (PlkProof * max(1, count))(*[p.raw for p in proofs])
+        wts = None
+        if weights is not None:
+            wts = (PlkFr * max(1, count))()
+            for j, w in enumerate(weights):
+                if isinstance(w, (int, np.integer)) and not 0 <= int(w) < R_MOD:
+                    raise PlonkError(2, "Verifier.fold: non-canonical weight")
+                wts[j] = _fr(w)
+        ctx = self.ctx or Context.default()
+        out = np.zeros((2, 13), dtype=np.uint64)
+        _check(_bind().plk_verifier_fold(ctx.handle, self._h, raw, pis, count, wts, _ptr(out)),
+               "Verifier::fold")
+        return out[0].copy(), out[1].copy()
+
+    def last_fold_stats(self):
+        """(host replay ms, GPU ms) of the most recent fold (measurement only)."""
+        a, b = C.c_double(), C.c_float()
+        _check(_bind().plk_verifier_last_fold_stats(self._h, C.byref(a), C.byref(b)),
+               "plk_verifier_last_fold_stats")
+        return a.value, b.value
+
+    def __del__(self):
+        try:
+            if self._h:
+                _bind().plk_verifier_destroy(self._h)
+        except Exception:
+            pass
+        self._h = None
 
 
 class Prover:

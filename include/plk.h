@@ -186,6 +186,19 @@ int plk_g1_sum(const plk_g1* points, size_t n, plk_g1* out);
 int plk_msm_sharded(plk_srs* const* per_gpu, int n_gpu, const plk_fr* scalars, size_t len,
                     plk_g1* out);
 
+/* msm_curve_addition(points, scalars) for arbitrary affine points (proof.rs:507): canonical
+ * affine out. Variable-base Pippenger (csrc/msm_var.hip): no precomputed window table, the
+ * points are used once. Host buffers; n = 0 gives the identity. Identity inputs (infinity = 1)
+ * are legal and skipped; a finite point with a coordinate >= p or off y^2 = x^3 + 4, or an
+ * infinity word other than 0 / 1, gives PLK_E_ARG. Subgroup membership is not checked.
+ * One call at a time per context. */
+int plk_msm_points(plk_ctx* ctx, const plk_g1* points, const plk_fr* scalars, size_t n, plk_g1* out);
+/* Several sums over disjoint index ranges of ONE point array as one GPU batch:
+ * outs[k] = sum_{i in [starts[k], starts[k] + lens[k])} scalars[i] * points[i], k < count <= 16,
+ * every range inside [0, n). What plk_verifier_fold runs for its two sums. */
+int plk_msm_points_ranges(plk_ctx* ctx, const plk_g1* points, const plk_fr* scalars, size_t n,
+                          const size_t* starts, const size_t* lens, size_t count, plk_g1* outs);
+
 /* ---- instrumentation (bench / profiling) ------------------------------------------- */
 /* Milliseconds of the dominant kernel of the most recent plk_commit/plk_msm on this SRS
  * (bucket accumulation), measured with HIP events on the launching stream; and the
@@ -329,6 +342,54 @@ int plk_prover_shard(plk_prover* p, plk_srs* slice, uint64_t slice_start, int ra
  * caller then keeps plk_prover_shard's slices. Undone by plk_prover_shard. */
 int plk_prover_shard_buckets(plk_prover* p, int rank, int world, plk_allgather_fn allgather,
                              void* user);
+
+/* ---- verifier: Verifier::new, Verifier::verify up to the pairing ------------------------
+ * The pairing itself stays with the caller: this library holds no G2 or
+ * pairing code. plk_verifier_fold returns the two G1 points of the final KZG check; all
+ * proofs of the batch are valid  <=>  e(c, H) == e(w, [tau]H)  (up to the soundness error of
+ * the random weights, 2^-128).
+ * Points are checked to be on the curve (identity commitments are legal: selector commitments
+ * of unused widgets, w_z_chall_w_comm of trivial circuits). Subgroup membership is NOT checked
+ * here: as in the reference (proof.rs:77, Proof holds decoded G1Affine values) it is the duty
+ * of whoever decoded the proof bytes into points. */
+typedef struct plk_verifier plk_verifier;
+typedef struct { plk_g1 c, w; } plk_kzg_pair;
+
+/* Verifier::new (verifier.rs:25-43). Host only, needs no GPU. n: the padded domain size (a
+ * power of two, 2 <= n <= 2^27), m: the gate count the transcript is seeded with,
+ * commitments: the 15 key commitments in plk_key_info order, pi_indexes: pi_count strictly
+ * increasing gate indexes < n (NULL when pi_count = 0). */
+int plk_verifier_create(const char* label, uint64_t n, uint64_t m, const plk_g1 commitments[15],
+                        const uint64_t* pi_indexes, size_t pi_count, plk_verifier** out);
+int plk_verifier_destroy(plk_verifier* v);
+
+/* The transcript replay of Proof::verify (proof.rs:87-178, 213-295, 344-376) for one proof.
+ * Host only. out[0..10] = beta, gamma, alpha, range / logic / fixed / variable separation, z,
+ * v (aggregate), v (shifted), u (batch). public_inputs: the verifier's pi_count values.
+ * PLK_E_ARG: a non-canonical evaluation or public input, z_h(z) = 0 or z = 1 (the reference
+ * panics there). Points are compressed as given (x and the sign of y), not curve-checked. */
+int plk_verifier_challenges(const plk_verifier* v, const plk_proof* proof, const plk_fr* public_inputs,
+                            plk_fr out[11]);
+
+/* Everything of Verifier::verify (verifier.rs:46-81) up to the pairing, for `count` proofs of
+ * this verifier's circuit: out = (sum_j rho_j C_j, sum_j rho_j W_j), where (C_j, W_j) is
+ * exactly batch_check's pair (commitment_scheme.rs:24-66) for proof j. public_inputs holds
+ * count * pi_count values. weights: `count` canonical scalars, or NULL. On NULL: rho_0 = 1 and
+ * rho_j = 128-bit values drawn from a merlin transcript over every proof's u challenge plus
+ * 32 bytes of OS entropy. The NULL form is the sound one; explicit weights exist for tests and
+ * for callers with their own Fiat-Shamir. The transcripts are replayed on the host (up to 16
+ * threads), every proof's scalars are derived and both sums run on the GPU as one
+ * plk_msm_points_ranges batch over 16 + 11 count and 2 count points.
+ * PLK_E_ARG: count = 0, a non-canonical evaluation / public input / weight, a finite point off
+ * the curve, z_h(z) = 0 or z = 1. One call at a time per context. */
+int plk_verifier_fold(plk_ctx* ctx, plk_verifier* v, const plk_proof* proofs,
+                      const plk_fr* public_inputs, size_t count, const plk_fr* weights,
+                      plk_kzg_pair* out);
+/* Timing of the most recent plk_verifier_fold on this verifier (measurement only): host
+ * milliseconds of the transcript replays (and the weights), and milliseconds between two HIP
+ * events on the context's stream, one before the upload of the points and one after the MSM
+ * has returned: the scalar kernels, the MSM's kernels and its host Horner tail. */
+int plk_verifier_last_fold_stats(const plk_verifier* v, double* replay_ms, float* gpu_ms);
 
 /* ---- Proof wire format (SCALE, src/prover/proof.rs:11,36) ---------------------------------
  * The reference derives parity-scale-codec Encode/Decode for Proof: fields in declaration
