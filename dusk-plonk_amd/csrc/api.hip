@@ -349,6 +349,18 @@ int plk_srs_load(plk_ctx* ctx, const plk_g1* points, size_t n_points, plk_srs** 
   PLK_API_END
 }
 
+int plk_srs_lagrange(plk_srs* srs, uint32_t log_n, plk_srs** out) {
+  PLK_API_BEGIN
+  if (!srs || !out || log_n < 1 || log_n > 26) return PLK_E_ARG;
+  *out = nullptr;
+  DeviceGuard g(srs->ctx->device);
+  plk_domain* dom = nullptr;
+  const int st = plk_domain_get(srs->ctx, log_n, &dom);
+  if (st != PLK_OK) return st;
+  return srs_lagrange_build(srs, dom, true, out);
+  PLK_API_END
+}
+
 int plk_srs_destroy(plk_srs* s) {
   PLK_API_BEGIN
   if (!s) return PLK_E_ARG;

@@ -239,7 +239,11 @@ int ntt_run_batch(plk_domain* d, const Fr* in, Fr* out, size_t len_in, int dir, 
 // in place of the domain's g^j table — a scaled table (c g^j) yields the evaluations of c p
 int ntt_run(plk_domain* d, const Fr* in, Fr* out, size_t len_in, int dir, int coset,
             Fr* scratch, hipStream_t stream, uint32_t count, const Fr* pre_table = nullptr);
-int msm_prepare_srs(plk_srs* s, hipStream_t stream);
+int msm_prepare_srs(plk_srs* s, hipStream_t stream, uint32_t force_c = 0, bool own_ws = true);
+// The Lagrange-basis SRS of `dom` from the first dom->n + 3 points of `src` (lagrange.hip):
+// [L_i(tau)]_1 for i < n, then [tau^(n+t)]_1 - [tau^t]_1 for t < 3; an ordinary SRS with src's
+// window size. PLK_E_ARG when src has fewer than n + 3 points.
+int srs_lagrange_build(plk_srs* src, plk_domain* dom, bool own_ws, plk_srs** out);
 int msm_run(plk_srs* s, const Fr* d_scalars, size_t len, size_t check_len, plk_g1* out,
             hipStream_t stream);
 // The SRS (window table) is only read: any number of threads may run batches on one SRS
@@ -248,9 +252,18 @@ int msm_run(plk_srs* s, const Fr* d_scalars, size_t len, size_t check_len, plk_g
 // range [part, part + 1) * 2^(c-1) / parts (wide bucket sets, 2^(c-1) / parts >= 2^14); the
 // parts' outputs sum to the whole MSM's (one large MSM split over GPUs by bucket
 // range, each GPU's reduction over its own buckets only).
+// guard_limit > 0: a slot whose largest bucket holds more than guard_limit entries is not
+// accumulated or reduced (msm.hip k_guard); info[k].hot reports it and outs[k] is void. info
+// (optional, `count` records): each slot's entry count and, for a guarded batch, its largest
+// bucket count.
+struct MsmSlotInfo {
+  uint32_t entries, max_count;
+  bool hot;
+};
 int msm_run_batch(plk_srs* s, MsmWorkspace& w, const Fr* const* d_scalars, const size_t* lens,
                   const size_t* check_lens, size_t count, plk_g1* outs, int* statuses,
-                  hipStream_t stream, uint32_t part = 0, uint32_t parts = 1);
+                  hipStream_t stream, uint32_t part = 0, uint32_t parts = 1,
+                  uint32_t guard_limit = 0, MsmSlotInfo* info = nullptr);
 // whether msm_run_batch accepts `parts` bucket ranges on this SRS (a power of two; for
 // parts > 1 a wide bucket set, 2^(c-1) above the LDS histogram's range, and >= 2^14 buckets
 // per part)

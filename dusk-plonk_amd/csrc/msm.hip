@@ -1080,8 +1080,13 @@ __global__ void __launch_bounds__(256, PLK_RUNSUM_WAVES) k_runsum2(uint32_t B, u
   G1xyzz* prev = &s_prev[threadIdx.x];
   G1R T = ld_g1r(&rsum[0]);
   for (uint32_t t = 1; t < K; ++t) {
+    // the suffix sums past a run's last filled bucket are infinity: a near-empty slot (a
+    // sparse Lagrange-basis column) pays a load and a test per step, not an addition and its
+    // repair path
+    const G1R v = ld_g1r(&rsum[t]);
+    if (g1r_is_inf(v)) continue;
     st_g1r(prev, T);
-    G1R c = g1r_add_lazy_sl(T, ld_g1r(&rsum[t]));
+    G1R c = g1r_add_lazy_sl(T, v);
     if (rx_is_zero(c.ZZ)) c = g1r_add_lazy_fix(ld_g1r(prev), ld_g1r(&rsum[t]), c.X);  // rare
     T = c;
   }
@@ -1314,6 +1319,49 @@ __global__ void k_any_nonzero(MsmBatch batch, uint32_t* __restrict__ flag, uint3
   if (!fe_is_zero(ld_fr(&batch.scalars[slot][i]))) flag[slot] = gen;
 }
 
+// Hot-bucket guard (msm_run_batch's guard_limit), after the sort and before the accumulation:
+// max_out[slot] = the slot's largest bucket count, and a slot above `limit` loses its tasks
+// (task_off cleared: the accumulation and the reductions of that slot then see empty buckets
+// and cost what a near-empty slot costs; its output is not used). k_runsum1 / k_bucket_sum walk
+// a bucket's partials one after the other in a single lane, so n equal small scalars (one bucket
+// of n entries) would make a reduction of n / chunk dependent additions.
+// state[slot] = running maximum, state[kMaxSlots + slot] = arrival counter, both zero between
+// batches (the slot's last workgroup resets them). max_out: mapped host memory, plain store.
+__global__ void __launch_bounds__(256) k_guard(const uint32_t* __restrict__ offsets,
+                                               uint32_t* __restrict__ task_off, uint32_t B,
+                                               uint32_t limit, uint32_t* __restrict__ state,
+                                               uint32_t* __restrict__ max_out) {
+  __shared__ uint32_t s_max, s_last;
+  const uint32_t slot = blockIdx.y, tid = threadIdx.x;
+  const uint32_t* off = offsets + (size_t)slot * (B + 1);
+  if (tid == 0) s_max = 0;
+  __syncthreads();
+  uint32_t m = 0;
+  for (uint32_t b = blockIdx.x * blockDim.x + tid; b < B; b += gridDim.x * blockDim.x)
+    m = max(m, off[b + 1] - off[b]);
+  if (m) atomicMax(&s_max, m);
+  __syncthreads();
+  if (tid == 0) {
+    if (s_max) atomicMax(&state[slot], s_max);
+    __threadfence();
+    s_last = atomicAdd(&state[kMaxSlots + slot], 1u) == gridDim.x - 1 ? 1u : 0u;
+  }
+  __syncthreads();
+  if (!s_last) return;
+  if (tid == 0) {
+    __threadfence();
+    s_max = atomicMax(&state[slot], 0u);  // the other workgroups' maxima included
+    max_out[slot] = s_max;
+    state[slot] = 0;  // ready for the next batch (stream order)
+    state[kMaxSlots + slot] = 0;
+  }
+  __syncthreads();
+  if (s_max > limit) {
+    uint32_t* to = task_off + (size_t)slot * (B + 1);
+    for (uint32_t b = tid; b <= B; b += blockDim.x) to[b] = 0;
+  }
+}
+
 }  // namespace
 
 // R'-domain [0, 2p) packed coordinates (ffr.hpp) -> canonical R-domain: x * 2^-SH
@@ -1398,6 +1446,10 @@ int ws_reserve(plk_srs* s, MsmWorkspace& w, size_t len, uint32_t slots, hipStrea
     if ((st = w.done.alloc(kMaxSlots * sizeof(uint32_t)))) return st;
     if (w.done.ptr != before) PLK_HIP_TRY(hipMemsetAsync(w.done.ptr, 0, kMaxSlots * sizeof(uint32_t), stream));
   }
+  if (!w.guard.ptr) {  // k_guard's state: zero between batches
+    if ((st = w.guard.alloc(2 * kMaxSlots * sizeof(uint32_t)))) return st;
+    PLK_HIP_TRY(hipMemsetAsync(w.guard.ptr, 0, 2 * kMaxSlots * sizeof(uint32_t), stream));
+  }
   {  // readback record: header (flags, entry counts) then the bit sums (nout <= 32 per slot),
      // in coherent mapped host memory (round 5: the per-batch copy dispatch it replaces cost
      // small proofs a dispatch per commit group). The previous batch has completed (every
@@ -1467,7 +1519,8 @@ bool msm_parts_ok(const plk_srs* s, uint32_t parts) {
 
 int msm_run_batch(plk_srs* s, MsmWorkspace& w, const Fr* const* d_scalars, const size_t* lens,
                   const size_t* check_lens, size_t count, plk_g1* outs, int* statuses,
-                  hipStream_t stream, uint32_t part, uint32_t parts) {
+                  hipStream_t stream, uint32_t part, uint32_t parts, uint32_t guard_limit,
+                  MsmSlotInfo* info) {
   if (count == 0) return PLK_OK;
   if (count > kMaxSlots) return PLK_E_ARG;
   if (!msm_parts_ok(s, parts) || part >= parts) return PLK_E_ARG;
@@ -1623,6 +1676,11 @@ int msm_run_batch(plk_srs* s, MsmWorkspace& w, const Fr* const* d_scalars, const
                          w.tasks.as<uint2>(), (uint64_t)w.task_stride);
     }
   }
+  if (guard_limit) {
+    hipLaunchKernelGGL(k_guard, dim3(std::min<uint32_t>(64, cdiv(B, 1024)), slots), dim3(256), 0, stream,
+                       (const uint32_t*)w.offsets.as<uint32_t>(), w.task_off.as<uint32_t>(), B,
+                       guard_limit, w.guard.as<uint32_t>(), hdr_dev->max_count);
+  }
   // 0: single-lane trees, 1: quad trees, 2: quad k_bitsum2 only (its few workgroups are
   // latency-bound at any load); chosen when the workspace is made (msm_common.hpp)
   const int tail = w.tail_quad;
@@ -1683,8 +1741,14 @@ int msm_run_batch(plk_srs* s, MsmWorkspace& w, const Fr* const* d_scalars, const
   MsmStats& stt = w.stats;
   float ms = 0.f;
   if (hipEventElapsedTime(&ms, w.ev0, w.ev1) == hipSuccess) stt.last_accumulate_ms = ms;
+  // a guarded slot over the limit ran no additions (k_guard cleared its tasks); its output is void
+  bool hot[kMaxSlots] = {};
+  for (uint32_t k = 0; k < slots; ++k) {
+    hot[k] = guard_limit && hdr->max_count[k] > guard_limit;
+    if (info) info[k] = MsmSlotInfo{ent[k], guard_limit ? hdr->max_count[k] : 0u, hot[k]};
+  }
   stt.last_point_adds = 0;
-  for (uint32_t k = 0; k < slots; ++k) stt.last_point_adds += ent[k];
+  for (uint32_t k = 0; k < slots; ++k) stt.last_point_adds += hot[k] ? 0u : ent[k];
   stt.last_slots = slots;
   stt.cum_accumulate_ms += stt.last_accumulate_ms;
   stt.cum_launches += 1;
@@ -1698,6 +1762,11 @@ int msm_run_batch(plk_srs* s, MsmWorkspace& w, const Fr* const* d_scalars, const
       *out = plk_g1{};
       if (statuses) statuses[k] = PLK_E_DEGREE;
       if (overall == PLK_OK) overall = PLK_E_DEGREE;
+      continue;
+    }
+    if (hot[k]) {  // the caller commits this slot another way (info[k].hot)
+      *out = plk_g1{};
+      if (statuses) statuses[k] = PLK_OK;
       continue;
     }
     // host tail: sum_j 2^j T_j (Horner), then canonical affine. The device stages work in

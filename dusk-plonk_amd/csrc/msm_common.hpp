@@ -92,10 +92,12 @@ inline uint32_t cdiv(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b
 // Head of a batch's readback record (MsmWorkspace::host_out, written by the kernels straight
 // into mapped host memory, the bit sums after it): per slot the degree-check flag (stamped
 // with the batch's generation number by k_any_nonzero) and the entry count (point
-// additions, written by k_bitsum2). 128 bytes, so the G1xyzz records after it stay aligned.
+// additions, written by k_bitsum2), and for a guarded batch (MsmGuard) the slot's largest
+// bucket count (k_guard). A multiple of 16 bytes, so the G1xyzz records after it stay aligned.
 struct ReadbackHeader {
   uint32_t flag[kMaxSlots];
   uint32_t entries[kMaxSlots];
+  uint32_t max_count[kMaxSlots];
 };
 static_assert(sizeof(ReadbackHeader) % 16 == 0, "alignment of the bit sums");
 
@@ -104,6 +106,7 @@ struct MsmWorkspace {
   // wide bucket sets only (msm.hip: two-level sort, run-sum reduction)
   DevBuf tmp, task_rel, bin_tot, len_fill, coarse_off, rsum, ys, zs;
   DevBuf done;  // k_bitsum1's per-slot arrival counters (its fold of k_bitsum2)
+  DevBuf guard;  // k_guard's per-slot running maxima and arrival counters (2 kMaxSlots words)
   // the readback record (ReadbackHeader + bit sums): coherent host memory mapped into the
   // device's address space, written by the kernels themselves (no copy dispatch per batch)
   PinnedBuf host_out;

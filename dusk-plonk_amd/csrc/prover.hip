@@ -305,7 +305,7 @@ uint32_t log2_ceil(uint64_t x) {
 // calling prover's MSM workspace and stream.
 int key_commit(plk_key* key, MsmWorkspace& ws, const std::vector<const Fr*>& ptrs,
                const std::vector<size_t>& lens, plk_g1* outs, int* statuses, hipStream_t s,
-               size_t cap = SIZE_MAX) {
+               size_t cap = SIZE_MAX, MsmSlotInfo* info = nullptr) {
   const size_t max_points = std::min<size_t>(std::min<size_t>(key->srs->n, key->n_trim), cap);
   std::vector<size_t> use(lens.size());
   for (size_t i = 0; i < lens.size(); ++i) use[i] = std::min(lens[i], max_points);
@@ -314,11 +314,32 @@ int key_commit(plk_key* key, MsmWorkspace& ws, const std::vector<const Fr*>& ptr
     const size_t m = std::min<size_t>(kMaxSlots, ptrs.size() - base);
     const int r = msm_run_batch(key->srs, ws, ptrs.data() + base, use.data() + base,
                                 lens.data() + base, m, outs + base,
-                                statuses ? statuses + base : nullptr, s);
+                                statuses ? statuses + base : nullptr, s, 0, 1, 0,
+                                info ? info + base : nullptr);
     if (r != PLK_OK && r != PLK_E_DEGREE) return r;
     if (r != PLK_OK) overall = r;
   }
   return overall;
+}
+
+// Round 1's guard on a Lagrange-basis wire commit: the most entries one bucket may hold. n equal
+// small values put n entries into one bucket, and the bucket reduction walks a bucket's partials
+// in a single lane. The bound is a fixed number of accumulation tasks per bucket whatever n,
+// 4 kChunkMax entries (a dense random column at c = 20 averages 26 per bucket), and never
+// below 4 times what a dense column of this length puts into every bucket, W len / 2^(c-1):
+// that is what the coefficient commit, the alternative, runs at anyway (n = 2^12 at c = 10:
+// 208 per bucket).
+uint32_t lagrange_bucket_max(const plk_srs* s, size_t len) {
+  const size_t dense = (size_t)s->windows * len >> (s->c - 1);
+  return (uint32_t)std::max<size_t>(4 * kChunkMax, 4 * dense);
+}
+
+// PLK_LAGRANGE_COMMIT=0: keys compiled while it is set carry no Lagrange-basis SRS, and round 1
+// commits their wires from the coefficients (the A/B switch). Read at key compile, never per
+// proof.
+bool lagrange_commit_enabled() {
+  const char* e = getenv("PLK_LAGRANGE_COMMIT");
+  return !(e && e[0] == '0' && e[1] == 0);
 }
 
 // The same commit group split over the ranks of a sharded prover (plk_prover_shard, SURVEY
@@ -756,6 +777,8 @@ int plk_key_compile(plk_srs* srs, const plk_composer* cs, const char* label, plk
       if (!fe_is_zero(g.q[QVAR])) key->has_var = true;
     }
     TRY(plk_domain_get(ctx, k, &key->dom));
+    // the Lagrange-basis SRS (round 1's wire commits): needs [tau^n .. tau^(n+2)] for the blinders
+    if (lagrange_commit_enabled() && srs->n >= n + 3) TRY(srs_lagrange_build(srs, key->dom, false, &key->lag));
     const int QB = key->qb = q_blocks(n);
     const uint64_t nq = (uint64_t)QB * n;  // quotient domain (prover.hpp)
 
@@ -1051,7 +1074,7 @@ int plk_prover_prove(plk_prover* P, const plk_composer* cs, uint64_t seed, plk_p
 
     // scratch (allocated once per prover)
     TRY(P->witness.alloc(std::max<size_t>(cs->witness.size(), 1) * sizeof(Fr)));
-    TRY(P->wires_lag.alloc(4 * n * sizeof(Fr)));
+    TRY(P->wires_lag.alloc(4 * S * sizeof(Fr)));  // per wire: n values, then its blinders
     TRY(P->wires_coef.alloc(4 * S * sizeof(Fr)));
     TRY(P->z_lag.alloc(n * sizeof(Fr)));
     TRY(P->z_coef.alloc(S * sizeof(Fr)));
@@ -1115,10 +1138,10 @@ int plk_prover_prove(plk_prover* P, const plk_composer* cs, uint64_t seed, plk_p
     }
     Fr* wl = P->wires_lag.as<Fr>();
     Fr* wc = P->wires_coef.as<Fr>();
-    TRY(pk_gather_wires(P->witness.as<Fr>(), key->wire_idx.as<uint32_t>(), m, n, wl, s));
+    TRY(pk_gather_wires(P->witness.as<Fr>(), key->wire_idx.as<uint32_t>(), m, n, wl, S, s));
     {  // the four wire idfts as one batch (one launch per pass instead of four)
       NttBatch b;
-      b.in_stride = n;
+      b.in_stride = S;
       b.out_stride = S;
       TRY(ntt_run_batch(key->dom, wl, wc, n, -1, 0, nsc, s, 4, b));
     }
@@ -1126,14 +1149,51 @@ int plk_prover_prove(plk_prover* P, const plk_composer* cs, uint64_t seed, plk_p
     bb.npoly = 4;
     for (int c = 0; c < 4; ++c) {
       bb.poly[c] = wc + c * S;  // blind(1): b(X)(X^n - 1), two scalars per wire, drawn in order
+      bb.lag[c] = wl + c * S;
       bb.b[c].count = 2;
       bb.b[c].r[0] = rng.fr();
       bb.b[c].r[1] = rng.fr();
     }
     TRY(pk_blind_batch(bb, n, s));
+    // The commits: from the Lagrange values [w(omega^i) | b_0 b_1] on the key's Lagrange-basis
+    // SRS (the same group element as the commit of the blinded coefficients; a zero or sparse
+    // column, the bench chain's fourth wire, then has next to no MSM entries), guarded: a wire
+    // whose values pile more than lagrange_bucket_max entries onto one bucket (small equal
+    // values, a wire of bits) would run a single-lane chain in the bucket reduction, and is
+    // committed from its coefficients instead, like every wire of a sharded prover or of a key
+    // without the Lagrange SRS. The coefficients are needed by rounds 3-5 either way.
     plk_g1 wcom[4];
-    TRY(prover_commit(P, {wc, wc + S, wc + 2 * S, wc + 3 * S}, {n + 2, n + 2, n + 2, n + 2}, wcom,
-                      nullptr));
+    {
+      bool coef[4] = {true, true, true, true};
+      for (int c = 0; c < 4; ++c) P->commit_basis[c] = 0, P->commit_entries[c] = 0;
+      if (key->lag && !P->shard && !P->shard_buckets) {
+        const Fr* ptrs[4] = {wl, wl + S, wl + 2 * S, wl + 3 * S};
+        const size_t lens[4] = {n + 2, n + 2, n + 2, n + 2};
+        MsmSlotInfo info[4];
+        TRY(msm_run_batch(key->lag, *P->ws, ptrs, lens, lens, 4, wcom, nullptr, s, 0, 1,
+                          lagrange_bucket_max(key->lag, n + 2), info));
+        for (int c = 0; c < 4; ++c) {
+          coef[c] = info[c].hot;
+          if (!coef[c]) P->commit_basis[c] = 1, P->commit_entries[c] = info[c].entries;
+        }
+      }
+      std::vector<const Fr*> cp;
+      std::vector<size_t> cl;
+      std::vector<int> which;
+      for (int c = 0; c < 4; ++c)
+        if (coef[c]) cp.push_back(wc + c * S), cl.push_back(n + 2), which.push_back(c);
+      if (!cp.empty()) {
+        plk_g1 cc[4];
+        MsmSlotInfo info[4] = {};
+        const bool sharded = P->shard || P->shard_buckets;
+        if (sharded) TRY(prover_commit(P, cp, cl, cc, nullptr));
+        else TRY(key_commit(key, *P->ws, cp, cl, cc, nullptr, s, SIZE_MAX, info));
+        for (size_t i = 0; i < which.size(); ++i) {
+          wcom[which[i]] = cc[i];
+          P->commit_entries[which[i]] = info[i].entries;
+        }
+      }
+    }
     tr.append_commitment("a_w", wcom[0]);
     tr.append_commitment("b_w", wcom[1]);
     tr.append_commitment("c_w", wcom[2]);
@@ -1145,7 +1205,7 @@ int plk_prover_prove(plk_prover* P, const plk_composer* cs, uint64_t seed, plk_p
     const Fr gamma = tr.challenge_scalar("gamma");
     Fr* num = P->num.as<Fr>();
     Fr* den = P->den.as<Fr>();
-    TRY(pk_perm_numden(wl, key->sigma_lag.as<Fr>(), key->dom->tw_fwd.as<Fr>(), n, beta, gamma, K1,
+    TRY(pk_perm_numden(wl, S, key->sigma_lag.as<Fr>(), key->dom->tw_fwd.as<Fr>(), n, beta, gamma, K1,
                        K2, K3, num, den, s));
     Fr* st = P->scan_tmp.as<Fr>();
     TRY(pk_scan(num, num, n, true, false, true, st, s));   // N_i = prod_{j<i} num_j
@@ -1561,4 +1621,13 @@ plk_prover::~plk_prover() {
   plk::msm_workspace_delete(ws);
 }
 
-plk_key::~plk_key() = default;
+plk_key::~plk_key() { delete lag; }
+
+int plk_prover_commit_info(const plk_prover* p, int basis[4], uint64_t entries[4]) {
+  if (!p) return PLK_E_ARG;
+  for (int c = 0; c < 4; ++c) {
+    if (basis) basis[c] = p->commit_basis[c];
+    if (entries) entries[c] = p->commit_entries[c];
+  }
+  return PLK_OK;
+}

@@ -25,6 +25,7 @@ struct PiDirect {
 // the blinding of up to 4 polynomials in one launch (round 1's four wires)
 struct BlindBatch {
   Fr* poly[4];
+  Fr* lag[4];  // when set: the blinders also go to lag[p][n + i], after the n Lagrange values
   BlindArgs b[4];
   uint32_t npoly;
 };
@@ -177,8 +178,9 @@ PLK_HD Fr widget_var_base(const Fr& x1, const Fr& x3, const Fr& y1, const Fr& y3
   return fe_add(fe_add(xy_consistency, fe_mul(x3c, k)), fe_mul(y3c, k2));
 }
 
+// out[col * stride + i] (col < 4, i < n): the wire's witness, zero for i >= m
 int pk_gather_wires(const Fr* witness, const uint32_t* idx, uint64_t m, uint64_t n, Fr* out,
-                    hipStream_t s);
+                    uint64_t stride, hipStream_t s);
 int pk_blind(Fr* poly, uint64_t n, const BlindArgs& b, hipStream_t s);
 int pk_blind_batch(const BlindBatch& bb, uint64_t n, hipStream_t s);
 // coefficients of PI(X) = idft(public-input vector) for at most kPiDirect public inputs:
@@ -188,8 +190,8 @@ int pk_pi_coef(const PiDirect& pd, const Fr* tw_inv, uint64_t n, Fr* out, hipStr
 int pk_pi_sparse(const PiSparse& ps, const Fr* l1, uint32_t log_n, uint64_t nq, Fr* out,
                  hipStream_t s);
 int pk_fill(Fr* out, const Fr& v, uint64_t n, hipStream_t s);
-int pk_perm_numden(const Fr* wires, const Fr* sigmas, const Fr* elements, uint64_t n,
-                   const Fr& beta, const Fr& gamma, const Fr& k1, const Fr& k2, const Fr& k3,
+int pk_perm_numden(const Fr* wires, uint64_t wire_stride, const Fr* sigmas, const Fr* elements,
+                   uint64_t n, const Fr& beta, const Fr& gamma, const Fr& k1, const Fr& k2, const Fr& k3,
                    Fr* num, Fr* den, hipStream_t s);
 int pk_mul3(const Fr* a, const Fr* b, const Fr& c, Fr* out, uint64_t n, hipStream_t s);
 uint64_t pk_scan_tmp_elems(uint64_t n);
@@ -262,6 +264,10 @@ struct plk_key {
   uint64_t m = 0, n = 0, n_trim = 0;
   uint32_t k = 0;
   plk_domain* dom = nullptr;   // n (also the blocks of the quotient domain, prover.hpp top)
+  // the Lagrange-basis SRS of the domain (lagrange.hip; owned): [L_i(tau)]_1, i < n, then the
+  // three blinder points, with the SRS's window size. Round 1 commits the wires from their
+  // values on it. Null when PLK_LAGRANGE_COMMIT=0 or the SRS has fewer than n + 3 points.
+  plk_srs* lag = nullptr;
   int qb = 0;                  // q_blocks(n)
   bool has_range = false, has_logic = false, has_fixed = false, has_var = false;
   // device-resident proving key
@@ -313,6 +319,10 @@ struct plk_prover {
   // the round-4 evaluations: coherent mapped host memory that k_eval_final writes directly
   plk::PinnedBuf eval_out;
   void* eval_dev = nullptr;  // eval_out's device address
+  // the last proof's wire commits (plk_prover_commit_info): basis (0 coefficients, 1
+  // Lagrange values) and MSM entry count per wire
+  int commit_basis[4] = {0, 0, 0, 0};
+  uint64_t commit_entries[4] = {0, 0, 0, 0};
   plk::DevBuf witness, wires_lag, wires_coef, z_lag, z_coef, num, den, tmp_a, scan_tmp, pi_lag,
       pi_coef, evq, quotq, t_coef, agg, agg2, w_coef, eval_partial, ntt_scratch;
   ~plk_prover();

@@ -67,11 +67,11 @@ inline uint32_t blocks_for(uint64_t n, uint32_t bs) { return (uint32_t)((n + bs 
 
 // ---------------------------------------------------------------------------- wires
 __global__ void k_gather_wires(const Fr* __restrict__ witness, const uint32_t* __restrict__ idx,
-                               uint64_t m, uint64_t n, Fr* __restrict__ out) {
+                               uint64_t m, uint64_t n, Fr* __restrict__ out, uint64_t stride) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t col = blockIdx.y;
   if (i >= n) return;
-  stf(&out[col * n + i], i < m ? ldf(&witness[idx[col * n + i]]) : fe_zero<FrCfg>());
+  stf(&out[col * stride + i], i < m ? ldf(&witness[idx[col * n + i]]) : fe_zero<FrCfg>());
 }
 
 // poly[i] -= r_i, poly[n + i] = r_i (i < count): p(X) + b(X)(X^n - 1)
@@ -117,6 +117,7 @@ __global__ void k_blind_batch(BlindBatch bb, uint64_t n) {
   Fr* poly = bb.poly[p];
   stf(&poly[i], fe_sub(ldf(&poly[i]), bb.b[p].r[i]));
   stf(&poly[n + i], bb.b[p].r[i]);
+  if (bb.lag[p]) stf(&bb.lag[p][n + i], bb.b[p].r[i]);
 }
 
 __global__ void k_fill(Fr* __restrict__ out, Fr v, uint64_t n) {
@@ -130,7 +131,7 @@ __global__ void k_fill(Fr* __restrict__ out, Fr v, uint64_t n) {
 // R-domain like the wires and gamma; the factors are carry-free sums (add3_u); a product
 // of four R-domain factors is R^4 / R'^3 times the value, and `fix` = R'^4 / R^3 mod r
 // (a plain integer) brings it back to R.
-__global__ void k_perm_numden(const Fr* __restrict__ wires, const Fr* __restrict__ sigmas,
+__global__ void k_perm_numden(const Fr* __restrict__ wires, uint64_t ws, const Fr* __restrict__ sigmas,
                               const Fr* __restrict__ elements, uint64_t n, Fr beta_rx, Fr gamma,
                               Fr k1_rx, Fr k2_rx, Fr k3_rx, Fr fix, Fr* __restrict__ num,
                               Fr* __restrict__ den) {
@@ -140,8 +141,8 @@ __global__ void k_perm_numden(const Fr* __restrict__ wires, const Fr* __restrict
   const RFr bx = rx_mul(be, ldr(&elements[i]));
   // the four wire factors written out (a loop over an array of the bX K_c values kept the
   // array in scratch memory)
-  auto tn = [&](int c, const RFr& bxk) { return add3_u(ldr(&wires[c * n + i]), g, bxk); };
-  auto td = [&](int c) { return add3_u(ldr(&wires[c * n + i]), g, rx_mul(be, ldr(&sigmas[c * n + i]))); };
+  auto tn = [&](int c, const RFr& bxk) { return add3_u(ldr(&wires[c * ws + i]), g, bxk); };
+  auto td = [&](int c) { return add3_u(ldr(&wires[c * ws + i]), g, rx_mul(be, ldr(&sigmas[c * n + i]))); };
   RFr nu = rx_norm(tn(0, bx)), de = rx_norm(td(0));
   nu = rx_mul(nu, tn(1, rx_mul(rx_unpack(k1_rx), bx)));
   de = rx_mul(de, td(1));
@@ -710,9 +711,9 @@ __global__ void __launch_bounds__(256) k_scale_powers(const Fr* __restrict__ c, 
 
 // ============================================================== host launchers
 int pk_gather_wires(const Fr* witness, const uint32_t* idx, uint64_t m, uint64_t n, Fr* out,
-                    hipStream_t s) {
+                    uint64_t stride, hipStream_t s) {
   hipLaunchKernelGGL(k_gather_wires, dim3(blocks_for(n, 256), 4), dim3(256), 0, s, witness, idx, m,
-                     n, out);
+                     n, out, stride);
   PLK_HIP_TRY(hipGetLastError());
   return PLK_OK;
 }
@@ -751,14 +752,14 @@ int pk_fill(Fr* out, const Fr& v, uint64_t n, hipStream_t s) {
   return PLK_OK;
 }
 
-int pk_perm_numden(const Fr* wires, const Fr* sigmas, const Fr* elements, uint64_t n,
-                   const Fr& beta, const Fr& gamma, const Fr& k1, const Fr& k2, const Fr& k3,
+int pk_perm_numden(const Fr* wires, uint64_t wire_stride, const Fr* sigmas, const Fr* elements,
+                   uint64_t n, const Fr& beta, const Fr& gamma, const Fr& k1, const Fr& k2, const Fr& k3,
                    Fr* num, Fr* den, hipStream_t s) {
   Fr fix = fe_zero<FrCfg>();  // 2^276 mod r = R'^4 / R^3 (k_perm_numden)
   fix.v[0] = 1;
   for (int b = 0; b < 4 * RxShape<FrCfg>::B * RxShape<FrCfg>::L - 3 * 256; ++b) fix = fe_dbl(fix);
-  hipLaunchKernelGGL(k_perm_numden, dim3(blocks_for(n, 256)), dim3(256), 0, s, wires, sigmas,
-                     elements, n, fe_to_rx_domain(beta), gamma, fe_to_rx_domain(k1),
+  hipLaunchKernelGGL(k_perm_numden, dim3(blocks_for(n, 256)), dim3(256), 0, s, wires, wire_stride,
+                     sigmas, elements, n, fe_to_rx_domain(beta), gamma, fe_to_rx_domain(k1),
                      fe_to_rx_domain(k2), fe_to_rx_domain(k3), fix, num, den);
   PLK_HIP_TRY(hipGetLastError());
   return PLK_OK;

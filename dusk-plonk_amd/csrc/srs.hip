@@ -135,10 +135,22 @@ static uint32_t choose_c(size_t n) {
   return 8;
 }
 
-int msm_prepare_srs(plk_srs* s, hipStream_t stream) {
-  s->c = choose_c(s->n);
+// temp[0 .. n) -> affine points and infinity flags (k_batch_affine; pref: n elements of scratch)
+int srs_batch_affine(const G1xyzz* temp, uint64_t n, Fp* pref, G1Affine* out, uint8_t* out_inf,
+                     hipStream_t stream) {
+  hipLaunchKernelGGL(k_batch_affine, dim3(cdiv(cdiv(n, kBatchAff), 128)), dim3(128), 0, stream, temp,
+                     n, pref, out, out_inf);
+  PLK_HIP_TRY(hipGetLastError());
+  return PLK_OK;
+}
+
+// force_c: another SRS's (final) window size instead of choose_c's (the Lagrange-basis SRS of a
+// key, lagrange.hip, shares its provers' workspaces with the key's SRS). own_ws = false: no
+// workspace of its own (an SRS that only msm_run_batch callers with their own workspace use).
+int msm_prepare_srs(plk_srs* s, hipStream_t stream, uint32_t force_c, bool own_ws) {
+  s->c = force_c ? force_c : choose_c(s->n);
   // every window would be c - 1 bits (c = 18: 15 x 17 = 255): that is the c - 1 layout
-  if ((s->c - 1) * ((255 + s->c - 1) / s->c) == 255) s->c -= 1;
+  if (!force_c && (s->c - 1) * ((255 + s->c - 1) / s->c) == 255) s->c -= 1;
   s->windows = (255 + s->c - 1) / s->c;  // scalars recoded from [0, (r-1)/2] (< 2^254)
   // balanced windows (round 5): the W windows cover exactly 255 bits, the top `narrow` = c W -
   // 255 of them c - 1 bits wide with digits scaled by 2 (msm.hip digit_at) and table rows
@@ -177,6 +189,7 @@ int msm_prepare_srs(plk_srs* s, hipStream_t stream) {
                      tab, (uint64_t)s->windows * n);
   PLK_HIP_TRY(hipGetLastError());
   PLK_HIP_TRY(stream_wait(stream));
+  if (!own_ws) return PLK_OK;
   s->ws.reset(new MsmWorkspace());
   const int r = ws_reserve(s, *s->ws, n, 1, stream);
   if (r != PLK_OK) return r;

@@ -60,6 +60,8 @@ ABI_SYMBOLS = (
     # variable-base MSM and the verifier (Verifier in dusk-plonk_amd/prover.py)
     "plk_msm_points", "plk_msm_points_ranges", "plk_verifier_create", "plk_verifier_destroy",
     "plk_verifier_challenges", "plk_verifier_fold", "plk_verifier_last_fold_stats",
+    # Lagrange-basis SRS and the wire commits' basis report
+    "plk_srs_lagrange", "plk_prover_commit_info",
 )
 
 
@@ -519,6 +521,16 @@ class PlonkParams:
         h = C.c_void_p()
         _check(_lib().plk_srs_load(ctx.handle, _ptr(pts), pts.shape[0], C.byref(h)), "plk_srs_load")
         return cls(h, pts.shape[0], ctx)
+
+    def lagrange(self, k: int) -> "PlonkParams":
+        """The Lagrange-basis SRS of the 2^k domain (plk_srs_lagrange): 2^k + 3 points, the
+        last three for a blinder b(X)(X^n - 1). commit([p(w^0) .. p(w^(n-1)), b0, b1, b2]) on it
+        equals commit(p + b (X^n - 1)) on this SRS, which must hold 2^k + 3 points."""
+        f = _lib().plk_srs_lagrange  # bound on use: a PLK_LIB build from before it still loads
+        f.restype, f.argtypes = C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]
+        h = C.c_void_p()
+        _check(f(self._h, k, C.byref(h)), "plk_srs_lagrange")
+        return PlonkParams(h, (1 << k) + 3, self.ctx)
 
     def trim(self, n: int) -> "PlonkParams":
         """Keep the first n + SLACK powers (key.rs:81-82)."""

@@ -751,6 +751,15 @@ class ProverLane:
                "plk_prover_msm_stats")
         return ms.value, la.value, ad.value, pt.value
 
+    def commit_info(self):
+        """The last proof's four wire commits (a, b, o, d): ([basis], [entries]) with basis
+        "lagrange" or "coefficient" and the commit's MSM entry count (plk_prover_commit_info)."""
+        f = _bind().plk_prover_commit_info  # bound on use: a PLK_LIB build from before it still loads
+        f.restype, f.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint64)]
+        basis, entries = (C.c_int * 4)(), (C.c_uint64 * 4)()
+        _check(f(self._h, basis, entries), "plk_prover_commit_info")
+        return (["lagrange" if b else "coefficient" for b in basis], [int(e) for e in entries])
+
     def close(self):
         if self._h:
             _bind().plk_prover_destroy(self._h)

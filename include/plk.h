@@ -119,6 +119,15 @@ int plk_srs_setup_range(plk_ctx* ctx, const plk_fr* tau, uint64_t start, size_t 
                         plk_g1* out_points, plk_srs** out);
 /* Load an existing SRS (e.g. a trimmed PlonkParams) from host affine points. */
 int plk_srs_load(plk_ctx* ctx, const plk_g1* points, size_t n_points, plk_srs** out);
+/* The Lagrange-basis SRS of the 2^log_n-point domain, computed from the first 2^log_n + 3
+ * points of `srs` alone (an inverse DFT over G1): point i < n is [L_i(tau)]G1, and points
+ * n, n + 1, n + 2 are [tau^(n+t)]G1 - [tau^t]G1, t = 0, 1, 2. A commit of the scalars
+ * [p(omega^0) .. p(omega^(n-1)) | b_0 b_1 b_2] on it is the commit of p(X) + b(X)(X^n - 1) on
+ * `srs`. An ordinary SRS (plk_commit, plk_srs_points, ...) that the caller destroys; points at
+ * infinity occur when tau is an n-th root of unity. PLK_E_ARG when `srs` has fewer than
+ * n + 3 points. plk_key_compile builds the key's own (round 1 commits the wire polynomials
+ * from their values on it) unless PLK_LAGRANGE_COMMIT=0 is set in the environment. */
+int plk_srs_lagrange(plk_srs* srs, uint32_t log_n, plk_srs** out);
 int plk_srs_destroy(plk_srs* srs);
 int plk_srs_len(const plk_srs* srs, size_t* n_points);
 /* Copy SRS points [start, start+count) back to the host. */
@@ -310,6 +319,12 @@ int plk_prover_prove(plk_prover* p, const plk_composer* circuit, uint64_t seed, 
  * clears the cumulative figures after reading them. Any output may be NULL. */
 int plk_prover_msm_stats(plk_prover* p, int reset, double* accumulate_ms, uint64_t* launches,
                          uint64_t* point_adds, uint64_t* points);
+/* The four wire commits (a, b, o, d) of this prover's last proof: basis[c] = 1 when wire c was
+ * committed from its Lagrange values on the key's Lagrange-basis SRS, 0 from its coefficients
+ * (no Lagrange SRS, a sharded prover, or a wire whose values crowd one MSM bucket);
+ * entries[c] = the MSM entries (point additions) of that commit, 0 for a sharded prover.
+ * Either output may be NULL. */
+int plk_prover_commit_info(const plk_prover* p, int basis[4], uint64_t entries[4]);
 
 /* ---- sharded commits: one proof, its MSMs split over the GPUs of a node ------------------
  * BASELINE configs[4] / SURVEY §8e. One process (rank) per GPU proves the SAME circuit with
