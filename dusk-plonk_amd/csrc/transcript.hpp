@@ -72,6 +72,10 @@ class Strobe128 {
       if (++pos_ == kR) run_f();
     }
   }
+  // the sponge as data: what a device-side replay (transcript_dev.hpp) continues from
+  const uint8_t* state() const { return st_; }
+  uint8_t pos() const { return pos_; }
+  uint8_t pos_begin() const { return pos_begin_; }
 
  private:
   static constexpr uint8_t kI = 1, kA = 2, kC = 4, kT = 8, kM = 16, kK = 32;
@@ -201,6 +205,8 @@ class Transcript {
     }
     out[0] |= 0x80 | (larger ? 0x20 : 0);
   }
+
+  const Strobe128& strobe() const { return s_; }
 
  private:
   Strobe128 s_;

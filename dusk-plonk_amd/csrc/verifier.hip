@@ -15,6 +15,10 @@
 //  3. GPU: both sums as one variable-base MSM batch (msm_var.hip) over 16 + 11 count and
 //     2 count points.
 // The pairing stays with the caller: no G2 or pairing code lives here.
+//
+// Device replay (plk_verifier_set_replay, PLK_REPLAY_DEVICE): step 1 runs on the GPU as well
+// (verifier_replay.hip). The host keeps the canonical-form checks, the uploads and, for random
+// weights, one sequential hash over the batch's u challenges (fold_device below).
 #include <hip/hip_runtime.h>
 #include <sys/random.h>
 
@@ -30,6 +34,7 @@
 #include "internal.hpp"
 #include "msm_common.hpp"
 #include "transcript.hpp"
+#include "verifier_replay.hpp"
 
 using namespace plk;
 
@@ -38,13 +43,6 @@ namespace {
 
 constexpr int kShared = 16;  // 15 key commitments + the generator
 constexpr int kPerProof = 11;
-
-// What the replay hands to the GPU for one proof (Montgomery form).
-struct FoldIn {
-  Fr ev[16];  // plk_proof order: a b c d a_next b_next d_next q_arith q_c q_l q_r s1 s2 s3 r perm
-  Fr ch[11];  // beta gamma alpha range logic fixed variable z v_a v_b u
-  Fr t_eval, l1, zn, rho;
-};
 
 struct FoldConst {
   Fr omega, ed;  // the domain generator; the JubJub d = -10240 / 10241
@@ -264,6 +262,13 @@ struct plk_verifier {
   DevBuf d_points, d_scalars, d_in, d_tmp;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   int device = -1;
+  // device replay: the mode, the compiled schedule (made on first use) and its buffers
+  int replay_mode = PLK_REPLAY_HOST;
+  float replay_kernel_ms = 0.f;
+  bool plan_ready = false, plan_on_device = false;
+  ReplayPlan plan;
+  DevBuf d_sched, d_winv, d_evals, d_pi, d_weights, d_vals, d_u, d_status, d_rho_sched;
+  hipEvent_t e2 = nullptr, e3 = nullptr;
 };
 
 namespace plk {
@@ -405,21 +410,25 @@ plk_g1 g1_generator() {
 
 // rho_0 = 1, rho_j = 128 bits of a merlin transcript over every proof's u challenge and 32 bytes
 // of OS entropy: nobody who fixed the proofs beforehand knows the weights
-int random_weights(std::vector<FoldIn>& in) {
-  uint8_t seed[32];
+void os_entropy(uint8_t seed[32]) {
   size_t got = 0;
-  while (got < sizeof seed) {
-    const ssize_t r = getrandom(seed + got, sizeof seed - got, 0);
+  while (got < 32) {
+    const ssize_t r = getrandom(seed + got, 32 - got, 0);
     if (r <= 0) break;
     got += (size_t)r;
   }
-  if (got < sizeof seed) {
+  if (got < 32) {
     std::random_device rd;
-    for (size_t i = 0; i < sizeof seed; i += 4) {
+    for (size_t i = 0; i < 32; i += 4) {
       const uint32_t x = rd();
       std::memcpy(seed + i, &x, 4);
     }
   }
+}
+
+int random_weights(std::vector<FoldIn>& in) {
+  uint8_t seed[32];
+  os_entropy(seed);
   Transcript t("plk-verifier-fold");
   t.append_u64("count", in.size());
   for (const FoldIn& f : in) t.append_scalar("u", f.ch[10]);
@@ -433,6 +442,179 @@ int random_weights(std::vector<FoldIn>& in) {
                ((uint32_t)b[4 * i + 3] << 24);
     in[j].rho = fe_to_mont(r);
   }
+  return PLK_OK;
+}
+
+}  // namespace
+}  // namespace plk
+
+// ---- device replay ------------------------------------------------------------------------
+namespace plk {
+namespace {
+
+// the schedule holds about a quarter of a block (1 KiB) per public input
+constexpr size_t kMaxDevicePi = 1u << 16;
+
+// Device-mode weights: the sequential part that binds the batch stays on the host — the root
+// transcript over the count, every proof's u and the entropy. rho_j is then drawn from a clone
+// of the root after append_u64("index", j), one lane per proof (k_fold_rho / rho_host).
+void fold_weights_root(const uint8_t entropy[32], const Fr* u, size_t count, RhoPlan& plan) {
+  Transcript t("plk-verifier-fold");
+  t.append_u64("count", count);
+  for (size_t j = 0; j < count; ++j) t.append_scalar("u", u[j]);
+  t.append_message("entropy", entropy, 32);
+  const Strobe128& s = t.strobe();
+  rho_plan_compile(s.state(), s.pos(), s.pos_begin(), plan);
+}
+
+// The canonical-form checks of replay(), for the whole batch, before any upload.
+int check_canonical(const plk_verifier* v, const plk_proof* proofs, const plk_fr* pis, size_t count) {
+  const size_t npi = v->pi_idx.size();
+  for (size_t j = 0; j < count; ++j) {
+    const plk_fr* evals = &proofs[j].a_eval;
+    for (int i = 0; i < 16; ++i)
+      if (!fr_abi_canonical(evals[i])) return PLK_E_ARG;
+  }
+  for (size_t i = 0; i < npi * count; ++i)
+    if (!fr_abi_canonical(pis[i])) return PLK_E_ARG;
+  return PLK_OK;
+}
+
+// Uploads the points (the layout of the fold's MSM), the evaluations, the public inputs and
+// the weights, and queues the replay kernels on the context's stream between the events e2 and
+// e3 (e0 goes before the uploads). On return d_in holds every proof's FoldIn (rho = its weight,
+// or one) and d_u the u challenges, stream-ordered. The caller holds the device guard.
+int replay_on_device(plk_ctx* ctx, plk_verifier* v, const plk_proof* proofs, const plk_fr* pis,
+                     size_t count, const plk_fr* weights) {
+  const size_t npi = v->pi_idx.size();
+  if (npi > kMaxDevicePi) return PLK_E_ARG;
+  hipStream_t s = ctx->stream;
+  if (v->device >= 0 && v->device != ctx->device) return PLK_E_ARG;  // one GPU per verifier
+  v->device = ctx->device;
+  for (hipEvent_t* e : {&v->e0, &v->e1, &v->e2, &v->e3})
+    if (!*e) PLK_HIP_TRY(hipEventCreate(e));
+  int st;
+  if (!v->plan_ready) {
+    const Strobe128& b = v->base.strobe();
+    replay_plan_compile(b.state(), b.pos(), b.pos_begin(), (uint32_t)npi, v->plan);
+    v->plan_ready = true;
+  }
+  if (!v->plan_on_device) {
+    if ((st = v->d_sched.alloc(v->plan.sched.size() * sizeof(uint32_t)))) return st;
+    if ((st = v->d_winv.alloc(std::max<size_t>(npi, 1) * sizeof(Fr)))) return st;
+    if ((st = v->d_status.alloc(sizeof(uint32_t)))) return st;
+    PLK_HIP_TRY(hipMemcpyAsync(v->d_sched.ptr, v->plan.sched.data(), v->plan.sched.size() * sizeof(uint32_t),
+                               hipMemcpyHostToDevice, s));
+    if (npi)
+      PLK_HIP_TRY(hipMemcpyAsync(v->d_winv.ptr, v->pi_winv.data(), npi * sizeof(Fr), hipMemcpyHostToDevice, s));
+    PLK_HIP_TRY(stream_wait(s));
+    v->plan_on_device = true;
+  }
+  // the points: [15 key commitments, generator][11 per proof][w_z, w_z_w per proof]
+  const size_t n_c = kShared + (size_t)kPerProof * count, n_pts = n_c + 2 * count;
+  std::vector<plk_g1> pts(n_pts);
+  std::memcpy(pts.data(), v->comms, sizeof v->comms);
+  pts[15] = g1_generator();
+  std::vector<plk_fr> evals(16 * count);
+  for (size_t j = 0; j < count; ++j) {
+    std::memcpy(&pts[kShared + kPerProof * j], &proofs[j].a_comm, kPerProof * sizeof(plk_g1));
+    pts[n_c + 2 * j] = proofs[j].w_z_chall_comm;
+    pts[n_c + 2 * j + 1] = proofs[j].w_z_chall_w_comm;
+    std::memcpy(&evals[16 * j], &proofs[j].a_eval, 16 * sizeof(plk_fr));
+  }
+  if ((st = v->d_points.alloc(n_pts * sizeof(plk_g1)))) return st;
+  if ((st = v->d_scalars.alloc(n_pts * sizeof(Fr)))) return st;
+  if ((st = v->d_in.alloc(count * sizeof(FoldIn)))) return st;
+  if ((st = v->d_tmp.alloc((size_t)kShared * count * sizeof(Fr)))) return st;
+  if ((st = v->d_evals.alloc(16 * count * sizeof(Fr)))) return st;
+  if ((st = v->d_pi.alloc(std::max<size_t>(npi * count, 1) * sizeof(Fr)))) return st;
+  if ((st = v->d_weights.alloc(count * sizeof(Fr)))) return st;
+  if ((st = v->d_u.alloc(count * sizeof(Fr)))) return st;
+  if ((st = v->d_vals.alloc((size_t)v->plan.lay.rows() * count * sizeof(uint32_t)))) return st;
+  PLK_HIP_TRY(hipEventRecord(v->e0, s));
+  PLK_HIP_TRY(hipMemcpyAsync(v->d_points.ptr, pts.data(), n_pts * sizeof(plk_g1), hipMemcpyHostToDevice, s));
+  PLK_HIP_TRY(hipMemcpyAsync(v->d_evals.ptr, evals.data(), 16 * count * sizeof(Fr), hipMemcpyHostToDevice, s));
+  if (npi)
+    PLK_HIP_TRY(hipMemcpyAsync(v->d_pi.ptr, pis, npi * count * sizeof(Fr), hipMemcpyHostToDevice, s));
+  if (weights)
+    PLK_HIP_TRY(hipMemcpyAsync(v->d_weights.ptr, weights, count * sizeof(Fr), hipMemcpyHostToDevice, s));
+  ReplayLaunch l;
+  l.d_sched = v->d_sched.as<uint32_t>();
+  l.blocks = v->plan.blocks;
+  l.lay = v->plan.lay;
+  l.base = v->plan.base;
+  l.n_inv = v->n_inv;
+  l.log_n = v->log_n;
+  l.count = (uint32_t)count;
+  l.d_comms = v->d_points.as<plk_g1>() + kShared;
+  l.d_evals = v->d_evals.as<Fr>();
+  l.d_pi = v->d_pi.as<Fr>();
+  l.d_winv = v->d_winv.as<Fr>();
+  l.d_weights = weights ? v->d_weights.as<Fr>() : nullptr;
+  l.d_vals = v->d_vals.as<uint32_t>();
+  l.d_in = v->d_in.as<FoldIn>();
+  l.d_u = v->d_u.as<Fr>();
+  l.d_status = v->d_status.as<uint32_t>();
+  PLK_HIP_TRY(hipEventRecord(v->e2, s));
+  if ((st = replay_launch(s, l))) return st;
+  PLK_HIP_TRY(hipEventRecord(v->e3, s));
+  return PLK_OK;
+}
+
+// plk_verifier_fold in device mode (the arguments are checked)
+int fold_device(plk_ctx* ctx, plk_verifier* v, const plk_proof* proofs, const plk_fr* public_inputs,
+                size_t count, const plk_fr* weights, plk_kzg_pair* out) {
+  using clock = std::chrono::steady_clock;
+  const auto t0 = clock::now();
+  int st;
+  if ((st = check_canonical(v, proofs, public_inputs, count))) return st;
+  double host_ms = std::chrono::duration<double, std::milli>(clock::now() - t0).count();
+  DeviceGuard g(ctx->device);
+  hipStream_t s = ctx->stream;
+  if ((st = replay_on_device(ctx, v, proofs, public_inputs, count, weights))) return st;
+  uint32_t status = 0;
+  if (!weights) {
+    std::vector<Fr> u(count);
+    PLK_HIP_TRY(hipMemcpyAsync(u.data(), v->d_u.ptr, count * sizeof(Fr), hipMemcpyDeviceToHost, s));
+    PLK_HIP_TRY(hipMemcpyAsync(&status, v->d_status.ptr, sizeof status, hipMemcpyDeviceToHost, s));
+    PLK_HIP_TRY(stream_wait(s));
+    if (status) return PLK_E_ARG;  // z_h(z) = 0 or z = 1 in some proof
+    const auto t1 = clock::now();
+    uint8_t seed[32];
+    os_entropy(seed);
+    RhoPlan rho;
+    fold_weights_root(seed, u.data(), count, rho);
+    host_ms += std::chrono::duration<double, std::milli>(clock::now() - t1).count();
+    if ((st = v->d_rho_sched.alloc(rho.sched.size() * sizeof(uint32_t)))) return st;
+    PLK_HIP_TRY(hipMemcpyAsync(v->d_rho_sched.ptr, rho.sched.data(), rho.sched.size() * sizeof(uint32_t),
+                               hipMemcpyHostToDevice, s));
+    if ((st = rho_launch(s, rho.root, v->d_rho_sched.as<uint32_t>(), rho.blocks, (uint32_t)count,
+                         &v->d_in.as<FoldIn>()->rho, (uint32_t)(sizeof(FoldIn) / sizeof(Fr)))))
+      return st;
+    // the schedule is read by the kernel: keep it alive until the stream has passed it
+    PLK_HIP_TRY(stream_wait(s));
+  }
+  v->replay_ms = host_ms;
+  hipLaunchKernelGGL(k_fold_scalars, dim3(cdiv(count, 128)), dim3(128), 0, s,
+                     (const FoldIn*)v->d_in.as<FoldIn>(), v->consts, (uint32_t)count,
+                     v->d_scalars.as<Fr>(), v->d_tmp.as<Fr>());
+  hipLaunchKernelGGL(k_fold_shared, dim3(kShared), dim3(256), 0, s, (const Fr*)v->d_tmp.as<Fr>(),
+                     (uint32_t)count, v->d_scalars.as<Fr>());
+  PLK_HIP_TRY(hipGetLastError());
+  const size_t n_c = kShared + (size_t)kPerProof * count, n_pts = n_c + 2 * count;
+  const size_t starts[2] = {0, n_c}, lens[2] = {n_c, 2 * count};
+  plk_g1 res[2];
+  st = msm_var_run(ctx, v->d_points.as<plk_g1>(), v->d_scalars.as<Fr>(), n_pts, starts, lens, 2, res, s);
+  PLK_HIP_TRY(hipEventRecord(v->e1, s));
+  if (weights)
+    PLK_HIP_TRY(hipMemcpyAsync(&status, v->d_status.ptr, sizeof status, hipMemcpyDeviceToHost, s));
+  PLK_HIP_TRY(stream_wait(s));
+  if (st != PLK_OK) return st;
+  if (status) return PLK_E_ARG;
+  (void)hipEventElapsedTime(&v->gpu_ms, v->e0, v->e1);
+  (void)hipEventElapsedTime(&v->replay_kernel_ms, v->e2, v->e3);
+  out->c = res[0];
+  out->w = res[1];
   return PLK_OK;
 }
 
@@ -496,6 +678,8 @@ int plk_verifier_destroy(plk_verifier* v) {
     DeviceGuard g(v->device);
     if (v->e0) (void)hipEventDestroy(v->e0);
     if (v->e1) (void)hipEventDestroy(v->e1);
+    if (v->e2) (void)hipEventDestroy(v->e2);
+    if (v->e3) (void)hipEventDestroy(v->e3);
     delete v;  // frees the device buffers on their device
     return PLK_OK;
   }
@@ -526,6 +710,9 @@ int plk_verifier_fold(plk_ctx* ctx, plk_verifier* v, const plk_proof* proofs,
   if (weights)
     for (size_t j = 0; j < count; ++j)
       if (!fr_abi_canonical(weights[j])) return PLK_E_ARG;
+  if (v->replay_mode == PLK_REPLAY_DEVICE)
+    return fold_device(ctx, v, proofs, public_inputs, count, weights, out);
+  v->replay_kernel_ms = 0.f;
   // 1. the transcript replays, on up to 16 host threads
   const auto t0 = std::chrono::steady_clock::now();
   std::vector<FoldIn> in(count);
@@ -603,6 +790,73 @@ int plk_verifier_fold(plk_ctx* ctx, plk_verifier* v, const plk_proof* proofs,
   (void)hipEventElapsedTime(&v->gpu_ms, v->e0, v->e1);
   out->c = res[0];
   out->w = res[1];
+  return PLK_OK;
+  PLK_V_END
+}
+
+int plk_verifier_set_replay(plk_verifier* v, int mode) {
+  if (!v || (mode != PLK_REPLAY_HOST && mode != PLK_REPLAY_DEVICE)) return PLK_E_ARG;
+  v->replay_mode = mode;
+  return PLK_OK;
+}
+
+int plk_verifier_challenges_batch(plk_ctx* ctx, plk_verifier* v, const plk_proof* proofs,
+                                  const plk_fr* public_inputs, size_t count, plk_fr* out) {
+  PLK_V_BEGIN
+  if (!ctx || !v || !proofs || !out || count == 0 || count > (1u << 24)) return PLK_E_ARG;
+  if (!public_inputs && !v->pi_idx.empty()) return PLK_E_ARG;
+  int st;
+  if ((st = check_canonical(v, proofs, public_inputs, count))) return st;
+  DeviceGuard g(ctx->device);
+  hipStream_t s = ctx->stream;
+  if ((st = replay_on_device(ctx, v, proofs, public_inputs, count, nullptr))) return st;
+  std::vector<FoldIn> in(count);
+  uint32_t status = 0;
+  PLK_HIP_TRY(hipMemcpyAsync(in.data(), v->d_in.ptr, count * sizeof(FoldIn), hipMemcpyDeviceToHost, s));
+  PLK_HIP_TRY(hipMemcpyAsync(&status, v->d_status.ptr, sizeof status, hipMemcpyDeviceToHost, s));
+  PLK_HIP_TRY(stream_wait(s));
+  (void)hipEventElapsedTime(&v->replay_kernel_ms, v->e2, v->e3);
+  if (status) return PLK_E_ARG;  // z_h(z) = 0 or z = 1 in some proof
+  for (size_t j = 0; j < count; ++j)
+    for (int i = 0; i < 11; ++i) fr_to_abi(in[j].ch[i], &out[11 * j + i]);
+  return PLK_OK;
+  PLK_V_END
+}
+
+int plk_verifier_last_replay_ms(const plk_verifier* v, float* kernel_ms) {
+  if (!v || !kernel_ms) return PLK_E_ARG;
+  *kernel_ms = v->replay_kernel_ms;
+  return PLK_OK;
+}
+
+int plk_debug_fold_weights(plk_ctx* ctx, const uint8_t entropy[32], const plk_fr* u, size_t count,
+                           plk_fr* out) {
+  PLK_V_BEGIN
+  if (!entropy || !u || !out || count == 0 || count > (1u << 24)) return PLK_E_ARG;
+  std::vector<Fr> um(count);
+  for (size_t j = 0; j < count; ++j) {
+    if (!fr_abi_canonical(u[j])) return PLK_E_ARG;
+    um[j] = fr_from_abi(u[j]);
+  }
+  RhoPlan rho;
+  fold_weights_root(entropy, um.data(), count, rho);
+  if (!ctx) {
+    for (size_t j = 0; j < count; ++j) fr_to_abi(rho_host(rho, (uint32_t)j), &out[j]);
+    return PLK_OK;
+  }
+  DeviceGuard g(ctx->device);
+  hipStream_t s = ctx->stream;
+  DevBuf d_sched, d_out;
+  int st;
+  if ((st = d_sched.alloc(rho.sched.size() * sizeof(uint32_t)))) return st;
+  if ((st = d_out.alloc(count * sizeof(Fr)))) return st;
+  PLK_HIP_TRY(hipMemcpyAsync(d_sched.ptr, rho.sched.data(), rho.sched.size() * sizeof(uint32_t),
+                             hipMemcpyHostToDevice, s));
+  if ((st = rho_launch(s, rho.root, d_sched.as<uint32_t>(), rho.blocks, (uint32_t)count, d_out.as<Fr>(), 1)))
+    return st;
+  PLK_HIP_TRY(hipMemcpyAsync(um.data(), d_out.ptr, count * sizeof(Fr), hipMemcpyDeviceToHost, s));
+  PLK_HIP_TRY(stream_wait(s));
+  for (size_t j = 0; j < count; ++j) fr_to_abi(um[j], &out[j]);
   return PLK_OK;
   PLK_V_END
 }

@@ -60,6 +60,9 @@ ABI_SYMBOLS = (
     # variable-base MSM and the verifier (Verifier in dusk-plonk_amd/prover.py)
     "plk_msm_points", "plk_msm_points_ranges", "plk_verifier_create", "plk_verifier_destroy",
     "plk_verifier_challenges", "plk_verifier_fold", "plk_verifier_last_fold_stats",
+    # the verifier's device-side transcript replay
+    "plk_verifier_set_replay", "plk_verifier_challenges_batch", "plk_verifier_last_replay_ms",
+    "plk_debug_fold_weights",
     # Lagrange-basis SRS and the wire commits' basis report
     "plk_srs_lagrange", "plk_prover_commit_info",
 )

@@ -95,6 +95,10 @@ def _bind():
         "plk_verifier_challenges": [vp, vp, vp, vp],
         "plk_verifier_fold": [vp, vp, vp, vp, sz, vp, vp],
         "plk_verifier_last_fold_stats": [vp, C.POINTER(C.c_double), C.POINTER(C.c_float)],
+        "plk_verifier_set_replay": [vp, i32],
+        "plk_verifier_challenges_batch": [vp, vp, vp, vp, sz, vp],
+        "plk_verifier_last_replay_ms": [vp, C.POINTER(C.c_float)],
+        "plk_debug_fold_weights": [vp, vp, vp, sz, vp],
     }
     for name, args in sig.items():
         f = getattr(lib, name)
@@ -574,9 +578,12 @@ class Verifier:
     """zksnarks Verifier (src/verifier.rs) up to the pairing: ``fold`` returns the two G1 points
     (C, W) of the final KZG check of a whole batch of proofs, e(C, H) == e(W, [tau]H), which the
     caller finishes with its pairing library. Built from VerifierData; needs
-    no GPU until ``fold``."""
+    no GPU until ``fold``. replay: where ``fold`` replays the transcripts, "host" (up to 16
+    threads) or "device" (one proof per GPU lane, plk_verifier_set_replay)."""
 
-    def __init__(self, vd: VerifierData, ctx=None):
+    REPLAY = {"host": 0, "device": 1}  # PLK_REPLAY_HOST, PLK_REPLAY_DEVICE
+
+    def __init__(self, vd: VerifierData, ctx=None, replay="host"):
         self.vd, self.ctx = vd, ctx
         comms = np.ascontiguousarray(vd.comms, dtype=np.uint64).reshape(15, 13)
         k = len(vd.pi_indexes)
@@ -584,6 +591,16 @@ class Verifier:
         self._h = C.c_void_p()
         _check(_bind().plk_verifier_create(vd.label, vd.n, vd.m, _ptr(comms), idx, k,
                                            C.byref(self._h)), "Verifier::new")
+        self.replay = "host"
+        self.set_replay(replay)
+
+    def set_replay(self, replay):
+        """"host" / "device" (or the PLK_REPLAY_* value); PlonkError(PLK_E_ARG) on another."""
+        mode = self.REPLAY.get(replay, replay)
+        if not isinstance(mode, int):
+            raise PlonkError(2, f"Verifier: replay mode {replay!r}")
+        _check(_bind().plk_verifier_set_replay(self._h, mode), "plk_verifier_set_replay")
+        self.replay = {v: k for k, v in self.REPLAY.items()}[mode]
 
     def _pis(self, public_inputs, count: int):
         """`count` lists of pi_count values (ints or Montgomery limbs) -> PlkFr array;
@@ -607,10 +624,38 @@ class Verifier:
                "Verifier::challenges")
         return [fr_int(out[i]) for i in range(11)]
 
-    def fold(self, proofs, public_inputs, weights=None):
+    def challenges_batch(self, proofs, public_inputs) -> list:
+        """``challenges`` of every proof of the batch, replayed on the GPU whatever the mode
+        (plk_verifier_challenges_batch): a list of 11-int lists."""
+        from .plonk import Context
+        count = len(proofs)
+        pis = self._pis(list(public_inputs), count)
+        raw = (PlkProof * max(1, count))(*[p.raw for p in proofs])
+        out = (PlkFr * max(1, 11 * count))()
+        ctx = self.ctx or Context.default()
+        _check(_bind().plk_verifier_challenges_batch(ctx.handle, self._h, raw, pis, count, out),
+               "Verifier::challenges_batch")
+        return [[fr_int(out[11 * j + i]) for i in range(11)] for j in range(count)]
+
+    def last_replay_ms(self) -> float:
+        """HIP-event milliseconds of the replay kernels of the most recent device-mode fold or
+        challenges_batch; 0 after a host-mode fold."""
+        a = C.c_float()
+        _check(_bind().plk_verifier_last_replay_ms(self._h, C.byref(a)), "plk_verifier_last_replay_ms")
+        return a.value
+
+    def fold(self, proofs, public_inputs, weights=None, replay=None):
         """(C, W) as uint64[13] ABI points for the batch `proofs` (a list of Proof) with
         `public_inputs` (one list per proof). weights: canonical ints / Montgomery limbs per
-        proof, or None for the sound random weights (plk_verifier_fold)."""
+        proof, or None for the sound random weights (plk_verifier_fold). replay: "host" /
+        "device" for this call only; None keeps the verifier's mode."""
+        if replay is not None and replay != self.replay:
+            keep = self.replay
+            self.set_replay(replay)
+            try:
+                return self.fold(proofs, public_inputs, weights)
+            finally:
+                self.set_replay(keep)
         from .plonk import Context
         count = len(proofs)
         pis = self._pis(list(public_inputs), count)

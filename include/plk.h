@@ -406,6 +406,35 @@ int plk_verifier_fold(plk_ctx* ctx, plk_verifier* v, const plk_proof* proofs,
  * has returned: the scalar kernels, the MSM's kernels and its host Horner tail. */
 int plk_verifier_last_fold_stats(const plk_verifier* v, double* replay_ms, float* gpu_ms);
 
+/* Where plk_verifier_fold replays the transcripts. PLK_REPLAY_HOST (the default): on up to 16
+ * host threads, as described above. PLK_REPLAY_DEVICE: on the GPU, one proof per lane
+ * (csrc/verifier_replay.hip); the host keeps the canonical-form checks, the uploads and, for
+ * weights = NULL, one sequential hash. With explicit weights the pair is byte-identical in both
+ * modes. z_h(z) = 0 and z = 1 are detected on the device and refused with PLK_E_ARG all the same.
+ * Device mode refuses verifiers with more than 2^16 public inputs (PLK_E_ARG): its compiled
+ * schedule grows with them.
+ * weights = NULL in device mode draws the weights differently (same soundness in the random-
+ * oracle model: independent 128-bit values bound to every proof's u and unknown to whoever
+ * chose the proofs): the host hashes root = Transcript("plk-verifier-fold"), append_u64("count",
+ * count), append_scalar("u", u_j) for every j, append_message("entropy", 32 OS bytes); rho_0 = 1
+ * and rho_j = the 128-bit little-endian value of challenge_bytes("rho", 16) taken from a clone
+ * of root after append_u64("index", j), one lane per proof. Host mode squeezes count - 1 times
+ * from one transcript instead.
+ * In device mode plk_verifier_last_fold_stats reports as replay_ms the host time before and
+ * inside the GPU phase (canonical checks, the weights root), and gpu_ms also spans the replay
+ * kernels. Host only; PLK_E_ARG on another mode. */
+#define PLK_REPLAY_HOST 0
+#define PLK_REPLAY_DEVICE 1
+int plk_verifier_set_replay(plk_verifier* v, int mode);
+/* The device replay alone, whatever the verifier's mode: out[11 j .. 11 j + 10] = the challenges
+ * of proof j in plk_verifier_challenges order. public_inputs: count * pi_count values.
+ * PLK_E_ARG: as plk_verifier_challenges, count = 0, or more than 2^16 public inputs. */
+int plk_verifier_challenges_batch(plk_ctx* ctx, plk_verifier* v, const plk_proof* proofs,
+                                  const plk_fr* public_inputs, size_t count, plk_fr* out);
+/* Milliseconds between two HIP events around the replay kernels of the most recent device-mode
+ * plk_verifier_fold or plk_verifier_challenges_batch; 0 after a host-mode fold. */
+int plk_verifier_last_replay_ms(const plk_verifier* v, float* kernel_ms);
+
 /* ---- Proof wire format (SCALE, src/prover/proof.rs:11,36) ---------------------------------
  * The reference derives parity-scale-codec Encode/Decode for Proof: fields in declaration
  * order, 11 Commitment<G1Affine> then ProofEvaluations. The element encodings live in the
@@ -472,6 +501,11 @@ int plk_debug_g1r_op(plk_ctx* ctx, int op, const uint32_t* p, const uint32_t* q,
  * receives the block count. out == NULL only reports the block count. */
 int plk_debug_block_eval(plk_key* key, const uint64_t* coef, size_t len, uint64_t* out,
                          size_t out_cap, int* blocks_out);
+/* The device-mode fold weights (plk_verifier_set_replay) from given entropy and u challenges
+ * (Montgomery form): out[j] = rho_j, j < count. ctx = NULL: the host mirror, no GPU; otherwise
+ * the kernel the fold runs. PLK_E_ARG: a NULL argument, count = 0, a non-canonical u. */
+int plk_debug_fold_weights(plk_ctx* ctx, const uint8_t entropy[32], const plk_fr* u, size_t count,
+                           plk_fr* out);
 
 #ifdef __cplusplus
 }

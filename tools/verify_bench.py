@@ -17,8 +17,16 @@ its host tail). Comparison points printed with every line: the reference's publi
 per single verification (its README, an Apple M1 figure — not this host) and the prover's own
 proofs/s at this size from README.md (9.6 M constraints/s at 2^12).
 
-Writes one JSON line per batch size to profiles/verify_fold.jsonl (or --out), each with the
-build id. Fails without a GPU.
+--replay host device (the default: both) folds every batch with the transcripts replayed on
+the host threads and on the GPU (plk_verifier_set_replay), the two modes one after the other
+for each batch size within every round: the host mode of the same run is the yardstick of the
+device mode.
+
+Writes one JSON line per batch size and mode to profiles/verify_fold_replay.jsonl (or --out),
+each with `replay`, `replay_ms` (host milliseconds before / between the GPU work), `gpu_ms`,
+`replay_kernel_ms` (the device replay's kernels, HIP events) and the build id.
+profiles/verify_fold.jsonl is the record of the host replay from before the device mode
+existed. Fails without a GPU.
 """
 from __future__ import annotations
 
@@ -43,7 +51,8 @@ def main(argv=None) -> int:
     ap.add_argument("--distinct", type=int, default=256, help="distinct proofs made up front")
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "verify_fold.jsonl"))
+    ap.add_argument("--replay", nargs="+", choices=["host", "device"], default=["host", "device"])
+    ap.add_argument("--out", default=str(ROOT / "profiles" / "verify_fold_replay.jsonl"))
     ns = ap.parse_args(argv)
 
     import torch
@@ -84,8 +93,9 @@ def main(argv=None) -> int:
         packed[b] = (raw, ver._pis(pis, b))
     out = np.zeros((2, 13), dtype=np.uint64)
 
-    def run(b):
+    def run(b, mode):
         raw, pis = packed[b]
+        ver.set_replay(mode)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(stream)
         st = lib.plk_verifier_fold(ctx.handle, ver._h, raw, pis, b, None, out.ctypes.data_as(C.c_void_p))
@@ -93,26 +103,28 @@ def main(argv=None) -> int:
         e1.synchronize()
         if st != plk.PLK_OK:
             raise plk.PlonkError(st, "plk_verifier_fold")
-        return (e0.elapsed_time(e1),) + ver.last_fold_stats()
+        return (e0.elapsed_time(e1),) + ver.last_fold_stats() + (ver.last_replay_ms(),)
 
-    times = {b: [] for b in ns.batches}
+    cases = [(b, mode) for b in ns.batches for mode in ns.replay]
+    times = {c: [] for c in cases}
     for rnd in range(ns.warmup + ns.rounds):
-        for b in ns.batches:  # interleaved: every round visits every batch size
-            t = run(b)
+        for c in cases:  # interleaved: every round visits every batch size in every mode
+            t = run(*c)
             if rnd >= ns.warmup:
-                times[b].append(t)
+                times[c].append(t)
     build = {key: info.get(key) for key in ("src", "flags", "variant", "tree_src")}
     lines = []
-    for b in ns.batches:
-        tot = [t[0] for t in times[b]]
+    for b, mode in cases:
+        tot = [t[0] for t in times[b, mode]]
         med = statistics.median(tot)
+        col = lambda i: round(statistics.median(t[i] for t in times[b, mode]), 4)
         line = {
-            "tool": "verify_bench", "log_n": k, "batch": b, "distinct_proofs": distinct,
+            "tool": "verify_bench", "log_n": k, "batch": b, "replay": mode, "distinct_proofs": distinct,
             "rounds": ns.rounds, "warmup": ns.warmup, "weights": "random (NULL)",
             "fold_ms_median": round(med, 4), "fold_ms_min": round(min(tot), 4),
             "fold_ms_max": round(max(tot), 4),
-            "host_replay_ms_median": round(statistics.median(t[1] for t in times[b]), 4),
-            "gpu_phase_ms_median": round(statistics.median(t[2] for t in times[b]), 4),
+            "replay_ms": col(1), "gpu_ms": col(2), "replay_kernel_ms": col(3),
+            "replay_kernel_us_per_proof": round(col(3) / b * 1e3, 4),
             "ms_per_proof": round(med / b, 6), "proofs_per_s": round(b / med * 1e3, 1),
             "reference_verify_ms_published_m1": REFERENCE_VERIFY_MS,
             "prover_proofs_per_s_readme": round(PROVER_CONSTRAINTS_PER_S_2_12 / n, 1),
