@@ -5,13 +5,14 @@ BLS12-381 Fr NTT family (poly_commit::Fft) and the G1 MSM behind KZG commit
 in include/plk.h. See DESIGN.md.
 """
 from .plonk import (  # noqa: F401
-    ABI_SYMBOLS, Coefficients, Commitment, Context, Fft, PLK_E_ARG, PLK_E_DEGREE, PLK_E_DEVICE,
-    PLK_E_NODEV, PLK_E_OOM, PLK_OK, PlonkError, PlonkParams, PointsValue, build_info, check_build,
-    device_count, g1_sum, msm_points, msm_points_ranges, msm_sharded,
+    ABI_SYMBOLS, Coefficients, Commitment, Context, Fft, OpeningKey, PLK_E_ARG, PLK_E_DEGREE,
+    PLK_E_DEVICE, PLK_E_NODEV, PLK_E_OOM, PLK_OK, PlonkError, PlonkParams, PointsValue, build_info, check_build,
+    debug_pairing, device_count, g1_sum, msm_points, msm_points_ranges, msm_sharded,
 )
 
 __all__ = [
-    "ABI_SYMBOLS", "Coefficients", "Commitment", "Context", "Fft", "PlonkError", "PlonkParams",
-    "PointsValue", "build_info", "check_build", "device_count", "g1_sum", "msm_points",
+    "ABI_SYMBOLS", "Coefficients", "Commitment", "Context", "Fft", "OpeningKey", "PlonkError",
+    "PlonkParams",
+    "PointsValue", "build_info", "check_build", "debug_pairing", "device_count", "g1_sum", "msm_points",
     "msm_points_ranges", "msm_sharded",
 ]

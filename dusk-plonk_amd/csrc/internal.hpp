@@ -277,6 +277,13 @@ int msm_var_run(plk_ctx* ctx, const plk_g1* d_points, const Fr* d_scalars, size_
                 const size_t* starts, const size_t* lens, size_t count, plk_g1* outs,
                 hipStream_t stream);
 void msm_var_ws_delete(VarMsmWs* w);
+// The batched pairing check (pairing.hip) on device buffers, stream-ordered on the context's
+// stream: d_ok[j] = 1 iff e(d_pairs[j].c, H) == e(d_pairs[j].w, beta_h). The points must be
+// canonical and on the curve (the caller's check). pairing_last_ms: the kernel's time once the
+// stream has passed it.
+int pairing_check_dev(plk_ctx* ctx, plk_opening_key* key, const plk_kzg_pair* d_pairs, size_t count,
+                      uint8_t* d_ok);
+int pairing_last_ms(plk_opening_key* key, float* ms);
 MsmWorkspace* msm_workspace_new();
 void msm_workspace_delete(MsmWorkspace* w);
 const MsmStats& msm_workspace_stats(const MsmWorkspace& w);

@@ -1,0 +1,322 @@
+// pairing.hip — the opening key (the G2 half of EvaluationKey), the host pairing check and the
+// batched pairing kernel: e(C, H) == e(W, [tau]H) for one pair per lane
+// (the reference's commitment_scheme.rs:24-66 ends in multi_miller_loop(..).final_exp()).
+//
+// The arithmetic is csrc/pairing.hpp, the same source on host and device. On the device a
+// lane's Fp12 values live in a workspace tiled by wave, [slot][coefficient][32-bit word][lane]
+// inside a tile (coalesced: the lanes of a wave read one 256-byte row per word); only Fp2
+// operands are in registers, so the kernel owns no scratch object. Both Miller loops of a pair share their 63 squarings, and both
+// line tables are read at lane-uniform addresses. G2 points are prepared on the host
+// (pairing_host.hpp); no G2 arithmetic runs here.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <memory>
+#include <new>
+#include <vector>
+
+#include "internal.hpp"
+#include "pairing_host.hpp"
+
+using namespace plk;
+
+struct plk_opening_key {
+  G2Aff h, bh;
+  // [0, 136): the lines of H; [136, 272): of beta_h; [272, 284): frob_table
+  std::vector<Fp2> tab;
+  int device = -1;
+  DevBuf d_tab, d_ws, d_pts, d_ok, d_out;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  float kernel_ms = 0.f;
+};
+
+namespace plk {
+namespace {
+
+constexpr int kTabH = 0, kTabB = 2 * kMillerLines, kTabFrob = 4 * kMillerLines;
+constexpr int kTabLen = kTabFrob + 12;
+constexpr uint32_t kF12Words = 144;  // one Fp12 value
+
+// A lane's Fp12 slots. The workspace is tiled by wave: tile t (the 64 lanes of block t) holds
+// [slot][coefficient][word][lane], so a wave reads one 256-byte row per word and every word's
+// offset from the coefficient's row is a compile-time constant (no address arithmetic in
+// registers beyond the row's).
+constexpr size_t kTileWords = (size_t)kF12Slots * kF12Words * 64;
+struct F12Dev {
+  uint32_t* base;  // the tile, already offset by the lane
+  __device__ __forceinline__ Fp2 ld(int slot, int i) const {
+    const uint32_t* p = base + (slot * 6 + i) * (24 * 64);
+    Fp2 r;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) {
+      r.c0.v[k] = p[k * 64];
+      r.c1.v[k] = p[(12 + k) * 64];
+    }
+    return r;
+  }
+  __device__ __forceinline__ void st(int slot, int i, const Fp2& a) {
+    uint32_t* p = base + (slot * 6 + i) * (24 * 64);
+#pragma unroll
+    for (int k = 0; k < 12; ++k) {
+      p[k * 64] = a.c0.v[k];
+      p[(12 + k) * 64] = a.c1.v[k];
+    }
+  }
+};
+
+// ABI point -> (x, y); false for the point at infinity
+__device__ __forceinline__ bool ld_g1_abi(const plk_g1* p, Fp& x, Fp& y) {
+  const uint64_t* q = reinterpret_cast<const uint64_t*>(p);
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    const uint64_t a = q[k], b = q[6 + k];
+    x.v[2 * k] = (uint32_t)a;
+    x.v[2 * k + 1] = (uint32_t)(a >> 32);
+    y.v[2 * k] = (uint32_t)b;
+    y.v[2 * k + 1] = (uint32_t)(b >> 32);
+  }
+  return q[12] == 0;
+}
+
+// pairs != 0: lane j checks (pts[2 j], pts[2 j + 1]) = (C, W) against (tab H, tab beta_h) and
+// writes ok[j]. pairs == 0: lane j writes ML(pts[j], Q)^(3 (p^12 - 1) / r) to out[72 j ..], Q's
+// lines at tab[0 ..]. ws: one tile of kTileWords words per block of 64 lanes.
+__global__ void __launch_bounds__(64) k_pairing(const plk_g1* __restrict__ pts, uint32_t count,
+                                                int pairs, const Fp2* __restrict__ tab,
+                                                uint32_t* __restrict__ ws,
+                                                uint8_t* __restrict__ ok, uint64_t* __restrict__ out) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= count) return;
+  F12Dev m{ws + (size_t)blockIdx.x * kTileWords + threadIdx.x};
+  Fp x0, y0, x1, y1;
+  const bool on0 = ld_g1_abi(pairs ? &pts[2 * (size_t)j] : &pts[j], x0, y0);
+  bool on1 = false;
+  if (pairs) {
+    on1 = ld_g1_abi(&pts[2 * (size_t)j + 1], x1, y1);
+    y1 = fe_neg(y1);
+  } else {
+    x1 = x0;
+    y1 = y0;
+  }
+  miller_loop(m, tab + kTabH, on0, x0, y0, pairs != 0, tab + kTabB, on1, x1, y1);
+  const int r = f12_final_exp(m, tab + kTabFrob);
+  if (pairs) {
+    ok[j] = f12_is_one(m, r) ? 1 : 0;
+  } else {
+    for (int i = 0; i < 6; ++i) {
+      const Fp2 a = m.ld(r, i);
+#pragma unroll
+      for (int k = 0; k < 6; ++k) {
+        out[72 * (size_t)j + 12 * i + k] = (uint64_t)a.c0.v[2 * k] | ((uint64_t)a.c0.v[2 * k + 1] << 32);
+        out[72 * (size_t)j + 12 * i + 6 + k] = (uint64_t)a.c1.v[2 * k] | ((uint64_t)a.c1.v[2 * k + 1] << 32);
+      }
+    }
+  }
+}
+
+int key_build(const G2Aff& h, const G2Aff& bh, plk_opening_key** out) {
+  std::unique_ptr<plk_opening_key> k(new plk_opening_key());
+  k->h = h;
+  k->bh = bh;
+  k->tab.resize(kTabLen);
+  if (!g2_prepare(h, &k->tab[kTabH]) || !g2_prepare(bh, &k->tab[kTabB])) return PLK_E_ARG;
+  frob_table(&k->tab[kTabFrob]);
+  *out = k.release();
+  return PLK_OK;
+}
+
+// the table on the context's device (uploaded once) and the events
+int key_on_device(plk_ctx* ctx, plk_opening_key* key, const Fp2* tab, DevBuf& d_tab, bool cache) {
+  if (key) {
+    if (key->device >= 0 && key->device != ctx->device) return PLK_E_ARG;  // one GPU per key
+    key->device = ctx->device;
+    if (!key->e0) PLK_HIP_TRY(hipEventCreate(&key->e0));
+    if (!key->e1) PLK_HIP_TRY(hipEventCreate(&key->e1));
+  }
+  if (cache && d_tab.ptr) return PLK_OK;
+  int st;
+  if ((st = d_tab.alloc(kTabLen * sizeof(Fp2)))) return st;
+  PLK_HIP_TRY(hipMemcpyAsync(d_tab.ptr, tab, kTabLen * sizeof(Fp2), hipMemcpyHostToDevice, ctx->stream));
+  PLK_HIP_TRY(stream_wait(ctx->stream));
+  return PLK_OK;
+}
+
+size_t ws_tiles(size_t count) { return (count + 63) / 64; }
+
+}  // namespace
+
+// d_pairs: `count` pairs on the device; d_ok: `count` bytes on the device. Stream-ordered on the
+// context's stream; the kernel sits between the key's events e0 and e1.
+int pairing_check_dev(plk_ctx* ctx, plk_opening_key* key, const plk_kzg_pair* d_pairs, size_t count,
+                      uint8_t* d_ok) {
+  if (count == 0 || count > (1u << 24)) return PLK_E_ARG;
+  int st;
+  if ((st = key_on_device(ctx, key, key->tab.data(), key->d_tab, true))) return st;
+  const size_t tiles = ws_tiles(count);
+  if ((st = key->d_ws.alloc(tiles * kTileWords * sizeof(uint32_t)))) return st;
+  hipStream_t s = ctx->stream;
+  PLK_HIP_TRY(hipEventRecord(key->e0, s));
+  hipLaunchKernelGGL(k_pairing, dim3((unsigned)tiles), dim3(64), 0, s,
+                     reinterpret_cast<const plk_g1*>(d_pairs), (uint32_t)count, 1,
+                     (const Fp2*)key->d_tab.as<Fp2>(), key->d_ws.as<uint32_t>(), d_ok,
+                     (uint64_t*)nullptr);
+  PLK_HIP_TRY(hipGetLastError());
+  PLK_HIP_TRY(hipEventRecord(key->e1, s));
+  return PLK_OK;
+}
+
+int pairing_last_ms(plk_opening_key* key, float* ms) {
+  *ms = 0.f;
+  if (!key->e0 || !key->e1) return PLK_OK;
+  (void)hipEventElapsedTime(ms, key->e0, key->e1);
+  key->kernel_ms = *ms;
+  return PLK_OK;
+}
+
+}  // namespace plk
+
+#define PLK_P_BEGIN try {
+#define PLK_P_END                   \
+  }                                 \
+  catch (const std::bad_alloc&) {   \
+    return PLK_E_OOM;               \
+  }                                 \
+  catch (...) {                     \
+    return PLK_E_DEVICE;            \
+  }
+
+extern "C" {
+
+int plk_opening_key_setup(const plk_fr* tau, plk_opening_key** out) {
+  PLK_P_BEGIN
+  if (!out) return PLK_E_ARG;
+  *out = nullptr;
+  if (!tau) return PLK_E_ARG;
+  Fr t;
+  for (int i = 0; i < 4; ++i) {
+    t.v[2 * i] = (uint32_t)tau->l[i];
+    t.v[2 * i + 1] = (uint32_t)(tau->l[i] >> 32);
+  }
+  Fr red = t;
+  fe_reduce_once(red);
+  if (!fe_eq(red, t) || fe_is_zero(t)) return PLK_E_ARG;  // not canonical, or zero
+  const Fr plain = fe_from_mont(t);
+  const G2Aff h = g2_generator();
+  return key_build(h, g2_mul(h, plain.v, 8), out);
+  PLK_P_END
+}
+
+int plk_opening_key_load(const plk_g2* h, const plk_g2* beta_h, plk_opening_key** out) {
+  PLK_P_BEGIN
+  if (!out) return PLK_E_ARG;
+  *out = nullptr;
+  if (!h || !beta_h) return PLK_E_ARG;
+  G2Aff a, b;
+  int st;
+  if ((st = g2_from_abi(*h, a)) || (st = g2_from_abi(*beta_h, b))) return st;
+  if (!g2_in_subgroup(a) || !g2_in_subgroup(b)) return PLK_E_ARG;
+  return key_build(a, b, out);
+  PLK_P_END
+}
+
+int plk_opening_key_points(const plk_opening_key* key, plk_g2* h, plk_g2* beta_h) {
+  if (!key) return PLK_E_ARG;
+  if (h) g2_to_abi(key->h, h);
+  if (beta_h) g2_to_abi(key->bh, beta_h);
+  return PLK_OK;
+}
+
+int plk_opening_key_destroy(plk_opening_key* key) {
+  PLK_P_BEGIN
+  if (!key) return PLK_E_ARG;
+  if (key->device >= 0) {
+    DeviceGuard g(key->device);
+    if (key->e0) (void)hipEventDestroy(key->e0);
+    if (key->e1) (void)hipEventDestroy(key->e1);
+    delete key;  // frees the device buffers on their device
+    return PLK_OK;
+  }
+  delete key;
+  return PLK_OK;
+  PLK_P_END
+}
+
+int plk_pairing_check(const plk_opening_key* key, const plk_kzg_pair* pair, int* ok) {
+  PLK_P_BEGIN
+  if (!key || !pair || !ok) return PLK_E_ARG;
+  G1In c, w;
+  int st;
+  if ((st = g1_from_abi(pair->c, c)) || (st = g1_from_abi(pair->w, w))) return st;
+  *ok = pairing_check_host(&key->tab[kTabH], &key->tab[kTabB], &key->tab[kTabFrob], c, w) ? 1 : 0;
+  return PLK_OK;
+  PLK_P_END
+}
+
+int plk_pairing_check_batch(plk_ctx* ctx, plk_opening_key* key, const plk_kzg_pair* pairs,
+                            size_t count, uint8_t* ok) {
+  PLK_P_BEGIN
+  if (!ctx || !key || !pairs || !ok || count == 0 || count > (1u << 24)) return PLK_E_ARG;
+  for (size_t j = 0; j < count; ++j) {
+    G1In t;
+    if (g1_from_abi(pairs[j].c, t) || g1_from_abi(pairs[j].w, t)) return PLK_E_ARG;
+  }
+  DeviceGuard g(ctx->device);
+  hipStream_t s = ctx->stream;
+  int st;
+  if ((st = key->d_pts.alloc(count * sizeof(plk_kzg_pair)))) return st;
+  if ((st = key->d_ok.alloc(count))) return st;
+  PLK_HIP_TRY(hipMemcpyAsync(key->d_pts.ptr, pairs, count * sizeof(plk_kzg_pair), hipMemcpyHostToDevice, s));
+  if ((st = pairing_check_dev(ctx, key, key->d_pts.as<plk_kzg_pair>(), count, key->d_ok.as<uint8_t>())))
+    return st;
+  PLK_HIP_TRY(hipMemcpyAsync(ok, key->d_ok.ptr, count, hipMemcpyDeviceToHost, s));
+  PLK_HIP_TRY(stream_wait(s));
+  float ms;
+  pairing_last_ms(key, &ms);
+  return PLK_OK;
+  PLK_P_END
+}
+
+int plk_opening_key_last_pairing_ms(const plk_opening_key* key, float* kernel_ms) {
+  if (!key || !kernel_ms) return PLK_E_ARG;
+  *kernel_ms = key->kernel_ms;
+  return PLK_OK;
+}
+
+int plk_debug_pairing(plk_ctx* ctx, const plk_g1* p, const plk_g2* q, size_t n, uint64_t* out) {
+  PLK_P_BEGIN
+  if (!p || !q || !out || n == 0 || n > 4096) return PLK_E_ARG;
+  G2Aff qa;
+  int st;
+  if ((st = g2_from_abi(*q, qa))) return st;
+  if (!g2_in_subgroup(qa)) return PLK_E_ARG;
+  std::vector<Fp2> tab(kTabLen);
+  if (!g2_prepare(qa, &tab[kTabH])) return PLK_E_ARG;
+  std::memcpy(&tab[kTabB], &tab[kTabH], 2 * kMillerLines * sizeof(Fp2));
+  frob_table(&tab[kTabFrob]);
+  std::vector<G1In> pts(n);
+  for (size_t i = 0; i < n; ++i)
+    if ((st = g1_from_abi(p[i], pts[i]))) return st;
+  if (!ctx) {
+    for (size_t i = 0; i < n; ++i) pairing_value_host(&tab[kTabH], &tab[kTabFrob], pts[i], out + 72 * i);
+    return PLK_OK;
+  }
+  DeviceGuard g(ctx->device);
+  hipStream_t s = ctx->stream;
+  DevBuf d_tab, d_ws, d_pts, d_out;
+  if ((st = key_on_device(ctx, nullptr, tab.data(), d_tab, false))) return st;
+  const size_t tiles = ws_tiles(n);
+  if ((st = d_ws.alloc(tiles * kTileWords * sizeof(uint32_t)))) return st;
+  if ((st = d_pts.alloc(n * sizeof(plk_g1)))) return st;
+  if ((st = d_out.alloc(n * 72 * sizeof(uint64_t)))) return st;
+  PLK_HIP_TRY(hipMemcpyAsync(d_pts.ptr, p, n * sizeof(plk_g1), hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(k_pairing, dim3((unsigned)tiles), dim3(64), 0, s,
+                     (const plk_g1*)d_pts.as<plk_g1>(), (uint32_t)n, 0, (const Fp2*)d_tab.as<Fp2>(),
+                     d_ws.as<uint32_t>(), (uint8_t*)nullptr, d_out.as<uint64_t>());
+  PLK_HIP_TRY(hipGetLastError());
+  PLK_HIP_TRY(hipMemcpyAsync(out, d_out.ptr, n * 72 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+  PLK_HIP_TRY(stream_wait(s));
+  return PLK_OK;
+  PLK_P_END
+}
+
+}  // extern "C"

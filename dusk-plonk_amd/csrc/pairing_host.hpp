@@ -1,0 +1,192 @@
+// pairing_host.hpp — the host-only half of the pairing: affine G2 arithmetic (one Fp2 inversion
+// per step; it runs once per key), the preparation of a G2 point into its Miller-loop lines, the
+// ABI conversions and the host pairing check. Plain C++ (no HIP): pairing.hip includes it, and so
+// does tools/pairing_selftest.cpp, which runs it under the host sanitizers.
+#pragma once
+#include <string.h>
+
+#include <vector>
+
+#include "../../include/plk.h"
+#include "pairing.hpp"
+
+namespace plk {
+
+struct G2Aff {
+  Fp2 x, y;
+  bool inf;
+};
+
+struct G1In {
+  Fp x, y;
+  bool inf;
+};
+
+inline Fp fp_from_words(const uint32_t* w) {
+  Fp r;
+  for (int i = 0; i < 12; ++i) r.v[i] = w[i];
+  return r;
+}
+
+inline Fp2 f2_from_words(const uint32_t (*w)[12]) { return {fp_from_words(w[0]), fp_from_words(w[1])}; }
+
+// xi^(i (p - 1) / 6), i < 6, then xi^(i (p^2 - 1) / 6), i < 6 (f12_final_exp's table)
+inline void frob_table(Fp2 out[12]) {
+  for (int i = 0; i < 6; ++i) {
+    out[i] = f2_from_words(pairing_consts::kFrob1[i]);
+    out[6 + i] = f2_from_words(pairing_consts::kFrob2[i]);
+  }
+}
+
+inline G2Aff g2_generator() {
+  return {f2_from_words(pairing_consts::kG2Gen[0]), f2_from_words(pairing_consts::kG2Gen[1]), false};
+}
+
+inline G2Aff g2_infinity() { return {f2_zero(), f2_zero(), true}; }
+
+// y^2 = x^3 + 4 xi
+inline bool g2_on_curve(const G2Aff& q) {
+  if (q.inf) return true;
+  const Fp four = fe_dbl(fe_dbl(fe_one<FpCfg>()));
+  const Fp2 b = f2_mul_xi({four, fe_zero<FpCfg>()});
+  return f2_eq(f2_sqr(q.y), f2_add(f2_mul(f2_sqr(q.x), q.x), b));
+}
+
+// a + b, every case; *lam (optional) receives the slope when both are finite and the sum is
+inline G2Aff g2_add(const G2Aff& a, const G2Aff& b, Fp2* lam_out = nullptr) {
+  if (a.inf) return b;
+  if (b.inf) return a;
+  Fp2 lam;
+  if (f2_eq(a.x, b.x)) {
+    if (!f2_eq(a.y, b.y) || f2_is_zero(a.y)) return g2_infinity();
+    const Fp2 xx = f2_sqr(a.x);
+    lam = f2_mul(f2_add(f2_dbl(xx), xx), f2_inv(f2_dbl(a.y)));
+  } else {
+    lam = f2_mul(f2_sub(b.y, a.y), f2_inv(f2_sub(b.x, a.x)));
+  }
+  G2Aff r;
+  r.x = f2_sub(f2_sub(f2_sqr(lam), a.x), b.x);
+  r.y = f2_sub(f2_mul(lam, f2_sub(a.x, r.x)), a.y);
+  r.inf = false;
+  if (lam_out) *lam_out = lam;
+  return r;
+}
+
+// [e] q for a little-endian exponent of `words` 32-bit words (plain integers, not Montgomery)
+inline G2Aff g2_mul(const G2Aff& q, const uint32_t* e, int words) {
+  G2Aff acc = g2_infinity();
+  for (int w = words - 1; w >= 0; --w)
+    for (int b = 31; b >= 0; --b) {
+      acc = g2_add(acc, acc);
+      if ((e[w] >> b) & 1u) acc = g2_add(acc, q);
+    }
+  return acc;
+}
+
+inline bool g2_in_subgroup(const G2Aff& q) { return g2_mul(q, FrCfg::P, 8).inf; }
+
+// The kMillerLines (lam xT - yT, lam) pairs of q in the order miller_loop consumes them. False
+// when a step meets infinity (q at infinity or of small order): such a point has no table.
+inline bool g2_prepare(const G2Aff& q, Fp2* out) {
+  if (q.inf) return false;
+  G2Aff t = q;
+  int idx = 0;
+  for (int b = 62; b >= 0; --b) {
+    const int steps = 1 + (int)((pairing_consts::kXAbs >> b) & 1ull);
+    for (int s = 0; s < steps; ++s, ++idx) {
+      Fp2 lam;
+      const G2Aff n = g2_add(t, s ? q : t, &lam);
+      if (n.inf) return false;
+      out[2 * idx] = f2_sub(f2_mul(lam, t.x), t.y);
+      out[2 * idx + 1] = lam;
+      t = n;
+    }
+  }
+  return idx == kMillerLines;
+}
+
+// ---- ABI conversions: 6 little-endian u64 Montgomery limbs are the memory image of Fp ---------
+inline Fp fp_from_abi(const uint64_t* l) {
+  Fp r;
+  for (int i = 0; i < 6; ++i) {
+    r.v[2 * i] = (uint32_t)l[i];
+    r.v[2 * i + 1] = (uint32_t)(l[i] >> 32);
+  }
+  return r;
+}
+
+inline void fp_to_abi(const Fp& a, uint64_t* l) {
+  for (int i = 0; i < 6; ++i) l[i] = (uint64_t)a.v[2 * i] | ((uint64_t)a.v[2 * i + 1] << 32);
+}
+
+inline bool fp_canonical(const Fp& a) {
+  uint32_t borrow = 0;
+  for (int i = 0; i < 12; ++i) {
+    const uint64_t t = (uint64_t)a.v[i] - FpCfg::P[i] - borrow;
+    borrow = (uint32_t)(t >> 63);
+  }
+  return borrow != 0;
+}
+
+// PLK_E_ARG: an infinity word other than 0 / 1, a finite point with a limb >= p or off
+// y^2 = x^3 + 4 (plk_msm_points' contract)
+inline int g1_from_abi(const plk_g1& p, G1In& o) {
+  o.x = o.y = fe_zero<FpCfg>();
+  o.inf = true;
+  if (p.infinity == 1) return PLK_OK;
+  if (p.infinity != 0) return PLK_E_ARG;
+  o.x = fp_from_abi(p.x);
+  o.y = fp_from_abi(p.y);
+  o.inf = false;
+  if (!fp_canonical(o.x) || !fp_canonical(o.y)) return PLK_E_ARG;
+  const Fp four = fe_dbl(fe_dbl(fe_one<FpCfg>()));
+  if (!fe_eq(fe_sqr(o.y), fe_add(fe_mul(fe_sqr(o.x), o.x), four))) return PLK_E_ARG;
+  return PLK_OK;
+}
+
+// PLK_E_ARG unless q is finite, canonical and on the twist (the subgroup check is the caller's)
+inline int g2_from_abi(const plk_g2& q, G2Aff& o) {
+  if (q.infinity != 0) return PLK_E_ARG;
+  o.x = {fp_from_abi(q.x), fp_from_abi(q.x + 6)};
+  o.y = {fp_from_abi(q.y), fp_from_abi(q.y + 6)};
+  o.inf = false;
+  if (!fp_canonical(o.x.c0) || !fp_canonical(o.x.c1) || !fp_canonical(o.y.c0) || !fp_canonical(o.y.c1))
+    return PLK_E_ARG;
+  return g2_on_curve(o) ? PLK_OK : PLK_E_ARG;
+}
+
+inline void g2_to_abi(const G2Aff& q, plk_g2* o) {
+  memset(o, 0, sizeof *o);
+  if (q.inf) {
+    o->infinity = 1;
+    return;
+  }
+  fp_to_abi(q.x.c0, o->x);
+  fp_to_abi(q.x.c1, o->x + 6);
+  fp_to_abi(q.y.c0, o->y);
+  fp_to_abi(q.y.c1, o->y + 6);
+}
+
+// e(c, Q0) == e(w, Q1), as ML(c, Q0) ML(-w, Q1) -> final exponentiation == 1. lines0 / lines1:
+// the prepared tables of Q0 / Q1; frob: frob_table.
+inline bool pairing_check_host(const Fp2* lines0, const Fp2* lines1, const Fp2* frob, const G1In& c,
+                               const G1In& w) {
+  F12Host m;
+  miller_loop(m, lines0, !c.inf, c.x, c.y, true, lines1, !w.inf, w.x, fe_neg(w.y));
+  const int r = f12_final_exp(m, frob);
+  return f12_is_one(m, r);
+}
+
+// out[72] = ML(p, Q)^(3 (p^12 - 1) / r), the six coefficients as (c0, c1) Montgomery limbs
+inline void pairing_value_host(const Fp2* lines, const Fp2* frob, const G1In& p, uint64_t* out) {
+  F12Host m;
+  miller_loop(m, lines, !p.inf, p.x, p.y, false, lines, false, p.x, p.y);
+  const int r = f12_final_exp(m, frob);
+  for (int i = 0; i < 6; ++i) {
+    const Fp2 a = m.ld(r, i);
+    fp_to_abi(a.c0, out + 12 * i);
+    fp_to_abi(a.c1, out + 12 * i + 6);
+  }
+}
+
+}  // namespace plk

@@ -14,7 +14,13 @@
 //     and generator) over the proofs.
 //  3. GPU: both sums as one variable-base MSM batch (msm_var.hip) over 16 + 11 count and
 //     2 count points.
-// The pairing stays with the caller: no G2 or pairing code lives here.
+// The fold's pair goes to the pairing check of pairing.hip (plk_verifier_verify), or to the
+// caller's own pairing library.
+//
+// Per-proof verdicts (plk_verifier_pairs, plk_verifier_verify_each): k_proof_pairs forms every
+// proof's OWN pair (C_j, W_j) from the scalars of step 2 at rho = 1 — half a wave per proof, one
+// point and scalar per lane, a 255-bit double-and-add and a segmented shuffle tree — and the
+// batched pairing kernel checks the pairs where they lie.
 //
 // Device replay (plk_verifier_set_replay, PLK_REPLAY_DEVICE): step 1 runs on the GPU as well
 // (verifier_replay.hip). The host keeps the canonical-form checks, the uploads and, for random
@@ -220,6 +226,131 @@ __global__ void __launch_bounds__(256) k_fold_shared(const Fr* __restrict__ tmp,
   if (t == 0) scalars[k] = sh[0];
 }
 
+// ---- per-proof pairs ---------------------------------------------------------------------------
+constexpr int kPairLanes = 32;  // half a wave per proof
+constexpr int kPairC = kShared + kPerProof;  // lanes [0, 27): the terms of C; 27, 28: of W
+
+__device__ __forceinline__ bool fp_is_canonical_dev(const Fp& a) {
+  uint32_t borrow = 0;
+#pragma unroll
+  for (int i = 0; i < 12; ++i) {
+    const uint64_t t = (uint64_t)a.v[i] - FpCfg::P[i] - borrow;
+    borrow = (uint32_t)(t >> 63);
+  }
+  return borrow != 0;
+}
+
+__device__ __forceinline__ G1xyzz xyzz_shfl_down(const G1xyzz& p, int off) {
+  G1xyzz r;
+#pragma unroll
+  for (int i = 0; i < 12; ++i) {
+    r.X.v[i] = __shfl_down(p.X.v[i], off, kPairLanes);
+    r.Y.v[i] = __shfl_down(p.Y.v[i], off, kPairLanes);
+    r.ZZ.v[i] = __shfl_down(p.ZZ.v[i], off, kPairLanes);
+    r.ZZZ.v[i] = __shfl_down(p.ZZZ.v[i], off, kPairLanes);
+  }
+  return r;
+}
+
+__device__ __forceinline__ void st_g1_abi(plk_g1* o, bool finite, const Fp& x, const Fp& y) {
+  uint64_t* q = reinterpret_cast<uint64_t*>(o);
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    q[k] = finite ? ((uint64_t)x.v[2 * k] | ((uint64_t)x.v[2 * k + 1] << 32)) : 0;
+    q[6 + k] = finite ? ((uint64_t)y.v[2 * k] | ((uint64_t)y.v[2 * k + 1] << 32)) : 0;
+  }
+  q[12] = finite ? 0 : 1;
+}
+
+// (C_j, W_j) of proof j = the fold of that proof alone at weight 1, as canonical affine points.
+// points / scalars: the fold's layout ([16 shared][11 per proof][2 per proof]); the proof's own
+// share of the 16 shared scalars is tmp[k * count + j] (k_fold_scalars at rho = 1). Lane l of the
+// proof's 32: l < 16 a shared point, 16 <= l < 27 one of the proof's commitments, 27 and 28 the
+// two terms of W, 29 .. 31 idle. Each lane multiplies its point by its scalar (double-and-add
+// over all 256 bits, g1.hpp's complete operations: identity points, zero scalars and equal
+// operands are ordinary inputs), a shuffle tree segmented at lane 27 leaves C in lane 0 and W in
+// lane 27, and lane 0 brings both to affine with one shared inversion. g1.hpp's packed XYZZ is
+// used, not g1r.hpp's redundant-limb form: the points stay in the ABI's Montgomery domain from
+// load to store and the operations are host-and-device code the host tail of the MSM already runs.
+// A finite point that is not canonical or not on the curve, or an infinity word other than
+// 0 / 1, sets *bad (the call fails with PLK_E_ARG) and counts as the identity.
+__global__ void __launch_bounds__(128) k_proof_pairs(const plk_g1* __restrict__ points,
+                                                     const Fr* __restrict__ scalars,
+                                                     const Fr* __restrict__ tmp, uint32_t count,
+                                                     plk_kzg_pair* __restrict__ out,
+                                                     uint32_t* __restrict__ bad) {
+  const uint32_t j = (blockIdx.x * blockDim.x + threadIdx.x) / kPairLanes;
+  const int l = (int)(threadIdx.x % kPairLanes);
+  if (j >= count) return;  // whole lane groups leave together
+  const size_t n_c = kShared + (size_t)kPerProof * count;
+  G1xyzz acc = xyzz_infinity();
+  if (l < kPairC + 2) {
+    size_t pi, si;
+    const Fr* sp = scalars;
+    if (l < kShared) {
+      pi = (size_t)l;
+      sp = tmp;
+      si = (size_t)l * count + j;
+    } else if (l < kPairC) {
+      pi = si = kShared + (size_t)kPerProof * j + (size_t)(l - kShared);
+    } else {
+      pi = si = n_c + 2 * (size_t)j + (size_t)(l - kPairC);
+    }
+    const uint64_t* q = reinterpret_cast<const uint64_t*>(&points[pi]);
+    const uint64_t flag = q[12];
+    Fp x, y;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      const uint64_t a = q[k], b = q[6 + k];
+      x.v[2 * k] = (uint32_t)a;
+      x.v[2 * k + 1] = (uint32_t)(a >> 32);
+      y.v[2 * k] = (uint32_t)b;
+      y.v[2 * k + 1] = (uint32_t)(b >> 32);
+    }
+    bool finite = flag == 0;
+    if (flag > 1) *bad = 1;
+    if (finite) {
+      bool ok = fp_is_canonical_dev(x) && fp_is_canonical_dev(y);
+      if (ok) {
+        const Fp four = fe_dbl(fe_dbl(fe_one<FpCfg>()));
+        ok = fe_eq(fe_sqr(y), fe_add(fe_mul(fe_sqr(x), x), four));
+      }
+      if (!ok) {
+        *bad = 1;
+        finite = false;
+      }
+    }
+    Fr s = fe_from_mont(sp[si]);
+    if (finite) {
+#pragma nounroll
+      for (int i = 0; i < 256; ++i) {
+        acc = xyzz_dbl(acc);
+        const uint32_t top = s.v[7] >> 31;
+#pragma unroll
+        for (int k = 7; k > 0; --k) s.v[k] = (s.v[k] << 1) | (s.v[k - 1] >> 31);
+        s.v[0] <<= 1;
+        if (top) acc = xyzz_add_affine(acc, x, y);
+      }
+    }
+  }
+  // lane l takes lane l + off's partial sum while both lie in one segment ([0, 27) or [27, 29)):
+  // after the last round lane 0 holds C and lane 27 holds W
+#pragma nounroll
+  for (int off = 1; off < kPairLanes; off <<= 1) {
+    const G1xyzz other = xyzz_shfl_down(acc, off);
+    const int src = l + off;
+    if (src < kPairC + 2 && (l < kPairC) == (src < kPairC)) acc = xyzz_add(acc, other);
+  }
+  const G1xyzz w = xyzz_shfl_down(acc, kPairC);  // lane 0 reads lane 27
+  if (l != 0) return;
+  const bool fc = !xyzz_is_inf(acc), fw = !xyzz_is_inf(w);
+  const Fp zc = fc ? acc.ZZZ : fe_one<FpCfg>(), zw = fw ? w.ZZZ : fe_one<FpCfg>();
+  const Fp inv = fe_inv(fe_mul(zc, zw));
+  const Fp ic = fe_mul(inv, zw), iw = fe_mul(inv, zc);  // 1 / ZZZ; 1 / ZZ = (ZZ / ZZZ)^2
+  st_g1_abi(&out[j].c, fc, fe_mul(acc.X, fe_sqr(fe_mul(acc.ZZ, ic))), fe_mul(acc.Y, ic));
+  st_g1_abi(&out[j].w, fw, fe_mul(w.X, fe_sqr(fe_mul(w.ZZ, iw))), fe_mul(w.Y, iw));
+}
+
 bool fr_abi_canonical(const plk_fr& a) {
   uint64_t borrow = 0;
   for (int i = 0; i < 4; ++i) {
@@ -269,6 +400,10 @@ struct plk_verifier {
   ReplayPlan plan;
   DevBuf d_sched, d_winv, d_evals, d_pi, d_weights, d_vals, d_u, d_status, d_rho_sched;
   hipEvent_t e2 = nullptr, e3 = nullptr;
+  // per-proof pairs (plk_verifier_pairs / plk_verifier_verify_each)
+  DevBuf d_pairs, d_pair_bad, d_ok;
+  hipEvent_t e4 = nullptr, e5 = nullptr;
+  float pairs_ms = 0.f, pairing_ms = 0.f;
 };
 
 namespace plk {
@@ -445,6 +580,57 @@ int random_weights(std::vector<FoldIn>& in) {
   return PLK_OK;
 }
 
+// The transcript replays of a whole batch on up to 16 host threads: in[j] for every proof, at
+// rho = 1. The first failing proof's status, or PLK_OK.
+int replay_host_batch(const plk_verifier* v, const plk_proof* proofs, const plk_fr* public_inputs,
+                      size_t count, std::vector<FoldIn>& in) {
+  const size_t npi = v->pi_idx.size();
+  in.resize(count);
+  const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
+  const size_t nth = std::min<size_t>({16, hw, (count + 7) / 8});
+  std::vector<int> status(std::max<size_t>(nth, 1), PLK_OK);
+  auto work = [&](size_t th) {
+    for (size_t j = th; j < count; j += std::max<size_t>(nth, 1)) {
+      const int st = replay(v, proofs[j], public_inputs ? public_inputs + j * npi : nullptr, in[j]);
+      if (st != PLK_OK) {
+        status[th] = st;
+        return;
+      }
+    }
+  };
+  if (nth <= 1) {
+    work(0);
+  } else {
+    std::vector<std::thread> workers;
+    workers.reserve(nth);
+    try {
+      for (size_t th = 0; th < nth; ++th) workers.emplace_back(work, th);
+    } catch (...) {
+      for (auto& w : workers) w.join();
+      throw;
+    }
+    for (auto& w : workers) w.join();
+  }
+  for (int st : status)
+    if (st != PLK_OK) return st;
+  return PLK_OK;
+}
+
+// The points of a batch in the fold's layout: [15 key commitments, generator][11 per proof]
+// [w_z, w_z_w per proof]
+std::vector<plk_g1> batch_points(const plk_verifier* v, const plk_proof* proofs, size_t count) {
+  const size_t n_c = kShared + (size_t)kPerProof * count;
+  std::vector<plk_g1> pts(n_c + 2 * count);
+  std::memcpy(pts.data(), v->comms, sizeof v->comms);
+  pts[15] = g1_generator();
+  for (size_t j = 0; j < count; ++j) {
+    std::memcpy(&pts[kShared + kPerProof * j], &proofs[j].a_comm, kPerProof * sizeof(plk_g1));
+    pts[n_c + 2 * j] = proofs[j].w_z_chall_comm;
+    pts[n_c + 2 * j + 1] = proofs[j].w_z_chall_w_comm;
+  }
+  return pts;
+}
+
 }  // namespace
 }  // namespace plk
 
@@ -618,6 +804,63 @@ int fold_device(plk_ctx* ctx, plk_verifier* v, const plk_proof* proofs, const pl
   return PLK_OK;
 }
 
+// Every proof's own pair (k_proof_pairs) into v->d_pairs, queued on the context's stream, in the
+// verifier's replay mode. The caller holds the device guard, has checked the arguments, and
+// reads the verdict of pairs_status once the stream has passed.
+int pairs_on_device(plk_ctx* ctx, plk_verifier* v, const plk_proof* proofs, const plk_fr* public_inputs,
+                    size_t count) {
+  hipStream_t s = ctx->stream;
+  int st;
+  if ((st = check_canonical(v, proofs, public_inputs, count))) return st;
+  const size_t n_c = kShared + (size_t)kPerProof * count, n_pts = n_c + 2 * count;
+  if (v->replay_mode == PLK_REPLAY_DEVICE) {
+    if ((st = replay_on_device(ctx, v, proofs, public_inputs, count, nullptr))) return st;  // rho = 1
+  } else {
+    std::vector<FoldIn> in;
+    if ((st = replay_host_batch(v, proofs, public_inputs, count, in))) return st;
+    const std::vector<plk_g1> pts = batch_points(v, proofs, count);
+    if (v->device >= 0 && v->device != ctx->device) return PLK_E_ARG;  // one GPU per verifier
+    v->device = ctx->device;
+    if ((st = v->d_points.alloc(n_pts * sizeof(plk_g1)))) return st;
+    if ((st = v->d_scalars.alloc(n_pts * sizeof(Fr)))) return st;
+    if ((st = v->d_in.alloc(count * sizeof(FoldIn)))) return st;
+    if ((st = v->d_tmp.alloc((size_t)kShared * count * sizeof(Fr)))) return st;
+    if ((st = v->d_status.alloc(sizeof(uint32_t)))) return st;
+    PLK_HIP_TRY(hipMemsetAsync(v->d_status.ptr, 0, sizeof(uint32_t), s));
+    PLK_HIP_TRY(hipMemcpyAsync(v->d_points.ptr, pts.data(), n_pts * sizeof(plk_g1), hipMemcpyHostToDevice, s));
+    PLK_HIP_TRY(hipMemcpyAsync(v->d_in.ptr, in.data(), count * sizeof(FoldIn), hipMemcpyHostToDevice, s));
+    PLK_HIP_TRY(stream_wait(s));  // pts and in leave scope
+  }
+  if (!v->e4) PLK_HIP_TRY(hipEventCreate(&v->e4));
+  if (!v->e5) PLK_HIP_TRY(hipEventCreate(&v->e5));
+  if ((st = v->d_pairs.alloc(count * sizeof(plk_kzg_pair)))) return st;
+  if ((st = v->d_pair_bad.alloc(sizeof(uint32_t)))) return st;
+  PLK_HIP_TRY(hipMemsetAsync(v->d_pair_bad.ptr, 0, sizeof(uint32_t), s));
+  hipLaunchKernelGGL(k_fold_scalars, dim3(cdiv(count, 128)), dim3(128), 0, s,
+                     (const FoldIn*)v->d_in.as<FoldIn>(), v->consts, (uint32_t)count,
+                     v->d_scalars.as<Fr>(), v->d_tmp.as<Fr>());
+  PLK_HIP_TRY(hipEventRecord(v->e4, s));
+  hipLaunchKernelGGL(k_proof_pairs, dim3(cdiv(count * kPairLanes, 128)), dim3(128), 0, s,
+                     (const plk_g1*)v->d_points.as<plk_g1>(), (const Fr*)v->d_scalars.as<Fr>(),
+                     (const Fr*)v->d_tmp.as<Fr>(), (uint32_t)count, v->d_pairs.as<plk_kzg_pair>(),
+                     v->d_pair_bad.as<uint32_t>());
+  PLK_HIP_TRY(hipGetLastError());
+  PLK_HIP_TRY(hipEventRecord(v->e5, s));
+  return PLK_OK;
+}
+
+// After the stream has passed pairs_on_device: PLK_E_ARG when a point was malformed or, in device
+// mode, some proof had z_h(z) = 0 or z = 1. Takes the kernel's time.
+int pairs_status(plk_ctx* ctx, plk_verifier* v) {
+  uint32_t bad[2] = {0, 0};
+  hipStream_t s = ctx->stream;
+  PLK_HIP_TRY(hipMemcpyAsync(&bad[0], v->d_pair_bad.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  PLK_HIP_TRY(hipMemcpyAsync(&bad[1], v->d_status.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  PLK_HIP_TRY(stream_wait(s));
+  (void)hipEventElapsedTime(&v->pairs_ms, v->e4, v->e5);
+  return (bad[0] || bad[1]) ? PLK_E_ARG : PLK_OK;
+}
+
 }  // namespace
 }  // namespace plk
 
@@ -680,6 +923,8 @@ int plk_verifier_destroy(plk_verifier* v) {
     if (v->e1) (void)hipEventDestroy(v->e1);
     if (v->e2) (void)hipEventDestroy(v->e2);
     if (v->e3) (void)hipEventDestroy(v->e3);
+    if (v->e4) (void)hipEventDestroy(v->e4);
+    if (v->e5) (void)hipEventDestroy(v->e5);
     delete v;  // frees the device buffers on their device
     return PLK_OK;
   }
@@ -715,34 +960,11 @@ int plk_verifier_fold(plk_ctx* ctx, plk_verifier* v, const plk_proof* proofs,
   v->replay_kernel_ms = 0.f;
   // 1. the transcript replays, on up to 16 host threads
   const auto t0 = std::chrono::steady_clock::now();
-  std::vector<FoldIn> in(count);
-  const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-  const size_t nth = std::min<size_t>({16, hw, (count + 7) / 8});
-  std::vector<int> status(std::max<size_t>(nth, 1), PLK_OK);
-  auto work = [&](size_t th) {
-    for (size_t j = th; j < count; j += std::max<size_t>(nth, 1)) {
-      const int st = replay(v, proofs[j], public_inputs ? public_inputs + j * npi : nullptr, in[j]);
-      if (st != PLK_OK) {
-        status[th] = st;
-        return;
-      }
-    }
-  };
-  if (nth <= 1) {
-    work(0);
-  } else {
-    std::vector<std::thread> workers;
-    workers.reserve(nth);
-    try {
-      for (size_t th = 0; th < nth; ++th) workers.emplace_back(work, th);
-    } catch (...) {
-      for (auto& w : workers) w.join();
-      throw;
-    }
-    for (auto& w : workers) w.join();
+  std::vector<FoldIn> in;
+  {
+    const int rst = replay_host_batch(v, proofs, public_inputs, count, in);
+    if (rst != PLK_OK) return rst;
   }
-  for (int st : status)
-    if (st != PLK_OK) return st;
   if (weights) {
     for (size_t j = 0; j < count; ++j) in[j].rho = fr_from_abi(weights[j]);
   } else {
@@ -752,14 +974,7 @@ int plk_verifier_fold(plk_ctx* ctx, plk_verifier* v, const plk_proof* proofs,
 
   // 2. the points: [15 key commitments, generator][11 per proof][w_z, w_z_w per proof]
   const size_t n_c = kShared + (size_t)kPerProof * count, n_pts = n_c + 2 * count;
-  std::vector<plk_g1> pts(n_pts);
-  std::memcpy(pts.data(), v->comms, sizeof v->comms);
-  pts[15] = g1_generator();
-  for (size_t j = 0; j < count; ++j) {
-    std::memcpy(&pts[kShared + kPerProof * j], &proofs[j].a_comm, kPerProof * sizeof(plk_g1));
-    pts[n_c + 2 * j] = proofs[j].w_z_chall_comm;
-    pts[n_c + 2 * j + 1] = proofs[j].w_z_chall_w_comm;
-  }
+  const std::vector<plk_g1> pts = batch_points(v, proofs, count);
   DeviceGuard g(ctx->device);
   hipStream_t s = ctx->stream;
   if (v->device >= 0 && v->device != ctx->device) return PLK_E_ARG;  // one GPU per verifier
@@ -792,6 +1007,64 @@ int plk_verifier_fold(plk_ctx* ctx, plk_verifier* v, const plk_proof* proofs,
   out->w = res[1];
   return PLK_OK;
   PLK_V_END
+}
+
+int plk_verifier_pairs(plk_ctx* ctx, plk_verifier* v, const plk_proof* proofs,
+                       const plk_fr* public_inputs, size_t count, plk_kzg_pair* out) {
+  PLK_V_BEGIN
+  if (!ctx || !v || !proofs || !out || count == 0 || count > (1u << 24)) return PLK_E_ARG;
+  if (!public_inputs && !v->pi_idx.empty()) return PLK_E_ARG;
+  DeviceGuard g(ctx->device);
+  int st;
+  if ((st = pairs_on_device(ctx, v, proofs, public_inputs, count))) return st;
+  std::vector<plk_kzg_pair> res(count);
+  PLK_HIP_TRY(hipMemcpyAsync(res.data(), v->d_pairs.ptr, count * sizeof(plk_kzg_pair), hipMemcpyDeviceToHost,
+                             ctx->stream));
+  if ((st = pairs_status(ctx, v))) return st;
+  v->pairing_ms = 0.f;
+  std::memcpy(out, res.data(), count * sizeof(plk_kzg_pair));
+  return PLK_OK;
+  PLK_V_END
+}
+
+int plk_verifier_verify(plk_ctx* ctx, plk_verifier* v, const plk_opening_key* key,
+                        const plk_proof* proofs, const plk_fr* public_inputs, size_t count,
+                        const plk_fr* weights, int* ok) {
+  if (!key || !ok) return PLK_E_ARG;
+  plk_kzg_pair pair;
+  const int st = plk_verifier_fold(ctx, v, proofs, public_inputs, count, weights, &pair);
+  if (st != PLK_OK) return st;
+  return plk_pairing_check(key, &pair, ok);
+}
+
+int plk_verifier_verify_each(plk_ctx* ctx, plk_verifier* v, plk_opening_key* key,
+                             const plk_proof* proofs, const plk_fr* public_inputs, size_t count,
+                             uint8_t* ok) {
+  PLK_V_BEGIN
+  if (!ctx || !v || !key || !proofs || !ok || count == 0 || count > (1u << 24)) return PLK_E_ARG;
+  if (!public_inputs && !v->pi_idx.empty()) return PLK_E_ARG;
+  DeviceGuard g(ctx->device);
+  int st;
+  if ((st = pairs_on_device(ctx, v, proofs, public_inputs, count))) return st;
+  if ((st = v->d_ok.alloc(count))) return st;
+  // a malformed point counts as the identity in k_proof_pairs, so the pairs are well-formed
+  // points whatever pairs_status says afterwards
+  if ((st = pairing_check_dev(ctx, key, v->d_pairs.as<plk_kzg_pair>(), count, v->d_ok.as<uint8_t>())))
+    return st;
+  std::vector<uint8_t> res(count);
+  PLK_HIP_TRY(hipMemcpyAsync(res.data(), v->d_ok.ptr, count, hipMemcpyDeviceToHost, ctx->stream));
+  if ((st = pairs_status(ctx, v))) return st;
+  pairing_last_ms(key, &v->pairing_ms);
+  std::memcpy(ok, res.data(), count);
+  return PLK_OK;
+  PLK_V_END
+}
+
+int plk_verifier_last_each_stats(const plk_verifier* v, float* pairs_ms, float* pairing_ms) {
+  if (!v) return PLK_E_ARG;
+  if (pairs_ms) *pairs_ms = v->pairs_ms;
+  if (pairing_ms) *pairing_ms = v->pairing_ms;
+  return PLK_OK;
 }
 
 int plk_verifier_set_replay(plk_verifier* v, int mode) {

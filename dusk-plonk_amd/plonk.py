@@ -65,6 +65,11 @@ ABI_SYMBOLS = (
     "plk_debug_fold_weights",
     # Lagrange-basis SRS and the wire commits' basis report
     "plk_srs_lagrange", "plk_prover_commit_info",
+    # opening key, pairing check and the verdicts (OpeningKey here, Verifier in prover.py)
+    "plk_opening_key_setup", "plk_opening_key_load", "plk_opening_key_points",
+    "plk_opening_key_destroy", "plk_pairing_check", "plk_pairing_check_batch",
+    "plk_opening_key_last_pairing_ms", "plk_debug_pairing", "plk_verifier_pairs",
+    "plk_verifier_verify", "plk_verifier_verify_each", "plk_verifier_last_each_stats",
 )
 
 
@@ -137,6 +142,14 @@ def _lib():
             "plk_srs_msm_stats_reset": (i32, [vp]),
             "plk_srs_cum_msm_stats": (i32, [vp, C.POINTER(C.c_double), C.POINTER(u64),
                                             C.POINTER(u64), C.POINTER(u64)]),
+            "plk_opening_key_setup": (i32, [vp, pp]),
+            "plk_opening_key_load": (i32, [vp, vp, pp]),
+            "plk_opening_key_points": (i32, [vp, vp, vp]),
+            "plk_opening_key_destroy": (i32, [vp]),
+            "plk_pairing_check": (i32, [vp, vp, C.POINTER(i32)]),
+            "plk_pairing_check_batch": (i32, [vp, vp, vp, sz, vp]),
+            "plk_opening_key_last_pairing_ms": (i32, [vp, C.POINTER(C.c_float)]),
+            "plk_debug_pairing": (i32, [vp, vp, vp, sz, vp]),
         }
         for name, (res, args) in sig.items():
             f = getattr(lib, name)
@@ -646,3 +659,97 @@ class PlonkParams:
         except Exception:
             pass
         self._h = None
+
+
+# ------------------------------------------------------------------- opening key, pairing
+G2_WORDS = 25  # plk_g2: x.c0, x.c1, y.c0, y.c1 (6 Montgomery u64 limbs each) + the infinity flag
+_FR_MOD = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
+
+
+def _as_pairs(pairs) -> np.ndarray:
+    a = np.ascontiguousarray(np.asarray(pairs, dtype=np.uint64))
+    if a.ndim == 2 and a.shape == (2, 13):
+        a = a.reshape(1, 2, 13)
+    if a.ndim != 3 or a.shape[1:] != (2, 13):
+        raise ValueError("expected uint64[n, 2, 13]: (C, W) ABI points per pair")
+    return a
+
+
+class OpeningKey:
+    """The G2 half of the reference's EvaluationKey: H and beta_h = [tau]H with their Miller-loop
+    lines prepared on the host (plk_opening_key). Points are uint64[25] rows in plk_g2 layout."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    @classmethod
+    def setup(cls, tau) -> "OpeningKey":
+        """H = the G2 generator, beta_h = [tau]H; tau: a canonical int or uint64[4] Montgomery
+        limbs (the explicit trapdoor of PlonkParams.setup)."""
+        if isinstance(tau, (int, np.integer)):
+            m = (int(tau) % _FR_MOD) * (1 << 256) % _FR_MOD
+            limbs = np.array([(m >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)], dtype=np.uint64)
+        else:
+            limbs = np.ascontiguousarray(np.asarray(tau, dtype=np.uint64).reshape(4))
+        h = C.c_void_p()
+        _check(_lib().plk_opening_key_setup(_ptr(limbs), C.byref(h)), "OpeningKey::setup")
+        return cls(h)
+
+    @classmethod
+    def load(cls, h, beta_h) -> "OpeningKey":
+        """An existing key; PlonkError(PLK_E_ARG) for a non-canonical limb, a point off the twist,
+        a point outside the order-r subgroup or the point at infinity."""
+        a = np.ascontiguousarray(np.asarray(h, dtype=np.uint64).reshape(G2_WORDS))
+        b = np.ascontiguousarray(np.asarray(beta_h, dtype=np.uint64).reshape(G2_WORDS))
+        out = C.c_void_p()
+        _check(_lib().plk_opening_key_load(_ptr(a), _ptr(b), C.byref(out)), "OpeningKey::load")
+        return cls(out)
+
+    def points(self):
+        """(H, beta_h) as uint64[25] rows."""
+        a, b = np.zeros(G2_WORDS, dtype=np.uint64), np.zeros(G2_WORDS, dtype=np.uint64)
+        _check(_lib().plk_opening_key_points(self._h, _ptr(a), _ptr(b)), "plk_opening_key_points")
+        return a, b
+
+    def check(self, pair) -> bool:
+        """e(C, H) == e(W, beta_h) on the host (plk_pairing_check); pair: (C, W) as uint64[2, 13]."""
+        a = _as_pairs(pair)
+        ok = C.c_int(0)
+        _check(_lib().plk_pairing_check(self._h, _ptr(a), C.byref(ok)), "plk_pairing_check")
+        return bool(ok.value)
+
+    def check_batch(self, pairs, ctx: "Context | None" = None) -> np.ndarray:
+        """The same check for uint64[n, 2, 13] pairs on the GPU, one pair per lane
+        (plk_pairing_check_batch): bool[n]."""
+        a = _as_pairs(pairs)
+        ctx = ctx or Context.default()
+        ok = np.zeros(a.shape[0], dtype=np.uint8)
+        _check(_lib().plk_pairing_check_batch(ctx.handle, self._h, _ptr(a), a.shape[0], _ptr(ok)),
+               "plk_pairing_check_batch")
+        return ok.astype(bool)
+
+    def last_pairing_ms(self) -> float:
+        """HIP-event milliseconds of the pairing kernel of the most recent device check."""
+        a = C.c_float()
+        _check(_lib().plk_opening_key_last_pairing_ms(self._h, C.byref(a)), "plk_opening_key_last_pairing_ms")
+        return a.value
+
+    def __del__(self):
+        try:
+            if self._h:
+                _lib().plk_opening_key_destroy(self._h)
+        except Exception:
+            pass
+        self._h = None
+
+
+def debug_pairing(points, q, ctx: "Context | None" = None) -> np.ndarray:
+    """Test support (plk_debug_pairing): e(p_i, q)^3 for uint64[n, 13] G1 points and one uint64[25]
+    G2 point, as uint64[n, 72] (six Fp2 coefficients of w^0 .. w^5, Montgomery limbs). ctx = None:
+    the host code; otherwise the kernel."""
+    a = np.ascontiguousarray(np.asarray(points, dtype=np.uint64).reshape(-1, 13))
+    g = np.ascontiguousarray(np.asarray(q, dtype=np.uint64).reshape(G2_WORDS))
+    out = np.zeros((a.shape[0], 72), dtype=np.uint64)
+    _check(_lib().plk_debug_pairing(None if ctx is None else ctx.handle, _ptr(a), _ptr(g), a.shape[0],
+                                    _ptr(out)), "plk_debug_pairing")
+    return out

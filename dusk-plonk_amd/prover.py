@@ -99,6 +99,10 @@ def _bind():
         "plk_verifier_challenges_batch": [vp, vp, vp, vp, sz, vp],
         "plk_verifier_last_replay_ms": [vp, C.POINTER(C.c_float)],
         "plk_debug_fold_weights": [vp, vp, vp, sz, vp],
+        "plk_verifier_pairs": [vp, vp, vp, vp, sz, vp],
+        "plk_verifier_verify": [vp, vp, vp, vp, vp, sz, vp, C.POINTER(i32)],
+        "plk_verifier_verify_each": [vp, vp, vp, vp, vp, sz, vp],
+        "plk_verifier_last_each_stats": [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)],
     }
     for name, args in sig.items():
         f = getattr(lib, name)
@@ -574,11 +578,16 @@ class VerifierData:
         return Verifier(self, ctx)
 
 
+class VerificationError(Exception):
+    """The reference's Err of Verifier::verify; str(e) names the variant (PairingCheckFailure)."""
+
+
 class Verifier:
-    """zksnarks Verifier (src/verifier.rs) up to the pairing: ``fold`` returns the two G1 points
-    (C, W) of the final KZG check of a whole batch of proofs, e(C, H) == e(W, [tau]H), which the
-    caller finishes with its pairing library. Built from VerifierData; needs
-    no GPU until ``fold``. replay: where ``fold`` replays the transcripts, "host" (up to 16
+    """zksnarks Verifier (src/verifier.rs). ``fold`` returns the two G1 points (C, W) of the final
+    KZG check of a whole batch of proofs, e(C, H) == e(W, [tau]H); ``verify`` / ``verify_batch``
+    finish it with the pairing check against an OpeningKey, ``verify_each`` gives one verdict per
+    proof on the GPU and ``pairs`` every proof's own (C, W). Built from VerifierData; needs no GPU
+    until one of these runs. replay: where ``fold`` replays the transcripts, "host" (up to 16
     threads) or "device" (one proof per GPU lane, plk_verifier_set_replay)."""
 
     REPLAY = {"host": 0, "device": 1}  # PLK_REPLAY_HOST, PLK_REPLAY_DEVICE
@@ -674,6 +683,63 @@ class Verifier:
         _check(_bind().plk_verifier_fold(ctx.handle, self._h, raw, pis, count, wts, _ptr(out)),
                "Verifier::fold")
         return out[0].copy(), out[1].copy()
+
+    def _batch(self, proofs, public_inputs):
+        from .plonk import Context
+        count = len(proofs)
+        pis = self._pis(list(public_inputs), count)
+        raw = (PlkProof * max(1, count))(*[p.raw for p in proofs])
+        return self.ctx or Context.default(), raw, pis, count
+
+    def pairs(self, proofs, public_inputs) -> np.ndarray:
+        """Every proof's own (C_j, W_j) as uint64[n, 2, 13]: exactly ``fold([p], [pi], [1])`` of
+        each proof, in one GPU pass (plk_verifier_pairs)."""
+        ctx, raw, pis, count = self._batch(proofs, public_inputs)
+        out = np.zeros((max(1, count), 2, 13), dtype=np.uint64)
+        _check(_bind().plk_verifier_pairs(ctx.handle, self._h, raw, pis, count, _ptr(out)),
+               "Verifier::pairs")
+        return out[:count]
+
+    def verify_batch(self, proofs, public_inputs, opening_key, weights=None) -> bool:
+        """True iff every proof of the batch is valid: the fold (weights None: the sound random
+        weights) and one host pairing check (plk_verifier_verify). Malformed input raises
+        PlonkError(PLK_E_ARG); it is not a verdict."""
+        ctx, raw, pis, count = self._batch(proofs, public_inputs)
+        wts = None
+        if weights is not None:
+            if len(weights) != count:
+                raise PlonkError(2, "Verifier.verify_batch: one weight per proof")
+            wts = (PlkFr * max(1, count))()
+            for j, w in enumerate(weights):
+                if isinstance(w, (int, np.integer)) and not 0 <= int(w) < R_MOD:
+                    raise PlonkError(2, "Verifier.verify_batch: non-canonical weight")
+                wts[j] = _fr(w)
+        ok = C.c_int(0)
+        _check(_bind().plk_verifier_verify(ctx.handle, self._h, opening_key._h, raw, pis, count, wts,
+                                           C.byref(ok)), "Verifier::verify")
+        return bool(ok.value)
+
+    def verify(self, proof: "Proof", public_inputs, opening_key) -> None:
+        """Verifier::verify (verifier.rs:46-81): returns None (the reference's Ok(())) or raises
+        VerificationError("PairingCheckFailure")."""
+        if not self.verify_batch([proof], [list(public_inputs)], opening_key, weights=[1]):
+            raise VerificationError("PairingCheckFailure")
+
+    def verify_each(self, proofs, public_inputs, opening_key) -> np.ndarray:
+        """One verdict per proof, bool[n], computed on the GPU (plk_verifier_verify_each). One
+        malformed proof makes the whole call raise PlonkError(PLK_E_ARG)."""
+        ctx, raw, pis, count = self._batch(proofs, public_inputs)
+        ok = np.zeros(max(1, count), dtype=np.uint8)
+        _check(_bind().plk_verifier_verify_each(ctx.handle, self._h, opening_key._h, raw, pis, count,
+                                                _ptr(ok)), "Verifier::verify_each")
+        return ok[:count].astype(bool)
+
+    def last_each_stats(self):
+        """(pairs kernel ms, pairing kernel ms) of the most recent pairs / verify_each."""
+        a, b = C.c_float(), C.c_float()
+        _check(_bind().plk_verifier_last_each_stats(self._h, C.byref(a), C.byref(b)),
+               "plk_verifier_last_each_stats")
+        return a.value, b.value
 
     def last_fold_stats(self):
         """(host replay ms, GPU ms) of the most recent fold (measurement only)."""

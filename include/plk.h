@@ -358,11 +358,12 @@ int plk_prover_shard(plk_prover* p, plk_srs* slice, uint64_t slice_start, int ra
 int plk_prover_shard_buckets(plk_prover* p, int rank, int world, plk_allgather_fn allgather,
                              void* user);
 
-/* ---- verifier: Verifier::new, Verifier::verify up to the pairing ------------------------
- * The pairing itself stays with the caller: this library holds no G2 or
- * pairing code. plk_verifier_fold returns the two G1 points of the final KZG check; all
- * proofs of the batch are valid  <=>  e(c, H) == e(w, [tau]H)  (up to the soundness error of
- * the random weights, 2^-128).
+/* ---- verifier: Verifier::new, Verifier::verify ------------------------------------------
+ * plk_verifier_fold returns the two G1 points of the final KZG check; all proofs of the batch
+ * are valid  <=>  e(c, H) == e(w, [tau]H)  (up to the soundness error of the random weights,
+ * 2^-128). The pairing check itself is plk_pairing_check / plk_pairing_check_batch against a
+ * plk_opening_key (H, [tau]H), and plk_verifier_verify / plk_verifier_verify_each below give the
+ * verdicts: the fold stays available for callers with a pairing library of their own.
  * Points are checked to be on the curve (identity commitments are legal: selector commitments
  * of unused widgets, w_z_chall_w_comm of trivial circuits). Subgroup membership is NOT checked
  * here: as in the reference (proof.rs:77, Proof holds decoded G1Affine values) it is the duty
@@ -435,6 +436,67 @@ int plk_verifier_challenges_batch(plk_ctx* ctx, plk_verifier* v, const plk_proof
  * plk_verifier_fold or plk_verifier_challenges_batch; 0 after a host-mode fold. */
 int plk_verifier_last_replay_ms(const plk_verifier* v, float* kernel_ms);
 
+/* ---- opening key and pairing check: the G2 half of EvaluationKey, TatePairing ---------------
+ * plk_g2 is a G2 point on the twist y^2 = x^3 + 4 (1 + u) over Fp2 = Fp[u] / (u^2 + 1): x.c0,
+ * x.c1, y.c0, y.c1 as 6 LE u64 Montgomery Fp limbs each, then the infinity flag. ASSUMED
+ * (parity unpinned, like the SCALE codec below): the field order of zkcrypto's G2Affine; the
+ * reference's pairing crate is not vendored and no fixture of it holds a G2 point.
+ * An opening key holds H and beta_h = [tau]H and, prepared once on the host, the 68 line
+ * coefficients per point that the Miller loop consumes (csrc/pairing.hpp); no G2 arithmetic
+ * runs on the GPU. The prepared lines are uploaded to a context's device on first device use;
+ * a key serves one device. */
+typedef struct { uint64_t x[12]; uint64_t y[12]; uint64_t infinity; } plk_g2; /* 200 bytes */
+typedef struct plk_opening_key plk_opening_key;
+/* H = the standard G2 generator, beta_h = [tau]H (tau: canonical Montgomery Fr, not zero). Host
+ * only: the counterpart of plk_srs_setup's explicit trapdoor. */
+int plk_opening_key_setup(const plk_fr* tau, plk_opening_key** out);
+/* An existing key. PLK_E_ARG for either point: a limb >= p, a point off the twist, a point not
+ * of order r (one host scalar multiplication each), the point at infinity. */
+int plk_opening_key_load(const plk_g2* h, const plk_g2* beta_h, plk_opening_key** out);
+int plk_opening_key_points(const plk_opening_key* key, plk_g2* h, plk_g2* beta_h);
+int plk_opening_key_destroy(plk_opening_key* key);
+
+/* *ok = 1 iff e(pair.c, H) == e(pair.w, beta_h): ML(c, H) ML(-w, beta_h) final-exponentiates
+ * to 1 (one shared Miller loop, as the reference's multi_miller_loop). Host only, needs no GPU.
+ * Finite points must be canonical and on the curve (PLK_E_ARG otherwise, as in plk_msm_points);
+ * subgroup membership is not checked (plk_verifier_fold's contract). A point at infinity
+ * contributes the factor 1: (inf, inf) is accepted, (finite, inf) and (inf, finite) rejected. */
+int plk_pairing_check(const plk_opening_key* key, const plk_kzg_pair* pair, int* ok);
+/* The same check for `count` pairs on the GPU, one pair per lane (csrc/pairing.hip): ok[j] =
+ * 0 / 1. Host buffers; one malformed point makes the whole call PLK_E_ARG. One call at a time
+ * per context and per key. */
+int plk_pairing_check_batch(plk_ctx* ctx, plk_opening_key* key, const plk_kzg_pair* pairs,
+                            size_t count, uint8_t* ok);
+/* Milliseconds of the pairing kernel of the most recent device check on this key (HIP events
+ * around the kernel; measurement only). */
+int plk_opening_key_last_pairing_ms(const plk_opening_key* key, float* kernel_ms);
+
+/* (C_j, W_j) of every proof: out[j] is exactly plk_verifier_fold(count = 1, weight 1) of proof
+ * j, bit for bit, for `count` proofs in one GPU pass (csrc/verifier.hip k_proof_pairs: half a
+ * wave per proof, one point and scalar per lane). Both replay modes feed it. PLK_E_ARG as the
+ * fold: one malformed proof refuses the whole call. One call at a time per context. */
+int plk_verifier_pairs(plk_ctx* ctx, plk_verifier* v, const plk_proof* proofs,
+                       const plk_fr* public_inputs, size_t count, plk_kzg_pair* out);
+/* Verifier::verify (verifier.rs:46-81) to its end, for a batch: plk_verifier_fold (weights =
+ * NULL: the sound random weights; or explicit) plus one host plk_pairing_check. *ok = 1: every
+ * proof of the batch is valid; 0: the reference's Err(PairingCheckFailure). Malformed input
+ * (whatever the fold refuses) is PLK_E_ARG, not a verdict. */
+int plk_verifier_verify(plk_ctx* ctx, plk_verifier* v, const plk_opening_key* key,
+                        const plk_proof* proofs, const plk_fr* public_inputs, size_t count,
+                        const plk_fr* weights, int* ok);
+/* One verdict per proof on the GPU: plk_verifier_pairs, then the batched pairing kernel on the
+ * pairs where they lie (no host round trip): ok[j] = 0 / 1. A malformed proof anywhere in the
+ * batch makes the whole call PLK_E_ARG and leaves ok untouched — it never hides as ok = 0 and
+ * never lets the other verdicts pass silently; decode and screen proofs first
+ * (plk_proof_decode) when single malformed ones must be told apart. */
+int plk_verifier_verify_each(plk_ctx* ctx, plk_verifier* v, plk_opening_key* key,
+                             const plk_proof* proofs, const plk_fr* public_inputs, size_t count,
+                             uint8_t* ok);
+/* Milliseconds of the two GPU phases of the most recent plk_verifier_pairs /
+ * plk_verifier_verify_each on this verifier (HIP events around each kernel): the per-proof pairs
+ * kernel and, for verify_each, the pairing kernel (0 after plk_verifier_pairs). */
+int plk_verifier_last_each_stats(const plk_verifier* v, float* pairs_ms, float* pairing_ms);
+
 /* ---- Proof wire format (SCALE, src/prover/proof.rs:11,36) ---------------------------------
  * The reference derives parity-scale-codec Encode/Decode for Proof: fields in declaration
  * order, 11 Commitment<G1Affine> then ProofEvaluations. The element encodings live in the
@@ -506,6 +568,12 @@ int plk_debug_block_eval(plk_key* key, const uint64_t* coef, size_t len, uint64_
  * the kernel the fold runs. PLK_E_ARG: a NULL argument, count = 0, a non-canonical u. */
 int plk_debug_fold_weights(plk_ctx* ctx, const uint8_t entropy[32], const plk_fr* u, size_t count,
                            plk_fr* out);
+/* out[72 i ..] = ML(p_i, q)^(3 (p^12 - 1) / r) = e(p_i, q)^3 as 12 Fp values (6 LE u64 Montgomery
+ * limbs each): the coefficient of w^k, k < 6, of Fp12 = Fp2[w] / (w^6 - (1 + u)) as (c0, c1). A p_i
+ * at infinity gives one. ctx = NULL: the host code; otherwise the kernel. This project's own
+ * coefficient order and power (the cube), not a reference-compatible Gt encoding. q: finite,
+ * canonical, on the twist, of order r; n <= 4096. */
+int plk_debug_pairing(plk_ctx* ctx, const plk_g1* p, const plk_g2* q, size_t n, uint64_t* out);
 
 #ifdef __cplusplus
 }
