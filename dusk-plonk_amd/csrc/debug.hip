@@ -1,6 +1,7 @@
 // debug.hip — test hooks: elementwise device arithmetic on host arrays for the parity tests.
 // plk_debug_field_op: the packed field of ff.hpp; plk_debug_rx_op: the redundant-limb field of
-// ffr.hpp on raw limb rows; plk_debug_g1r_op: the XYZZ group law of g1r.hpp on raw limb rows;
+// ffr.hpp on raw limb rows; plk_debug_ntt_lazy_op: the NTT pass' lazy butterfly helpers (the
+// kernel is in ntt.hip); plk_debug_g1r_op: the XYZZ group law of g1r.hpp on raw limb rows;
 // plk_debug_block_eval: the prover's forward block transform onto a key's quotient domain.
 #include <hip/hip_runtime.h>
 
@@ -301,6 +302,17 @@ extern "C" int plk_debug_rx_op(plk_ctx* ctx, int field, int op, const uint32_t* 
     for (int k = 0; k < 4; ++k) in[k] = {k < nin ? rows[k] : nullptr, n * row};
     plk::DeviceGuard g(ctx->device);
     return plk::run_rows(ctx, kern, in, out, n * row * plk::rx_op_nout(op), n, n);
+  } catch (...) {
+    return PLK_E_DEVICE;
+  }
+}
+
+extern "C" int plk_debug_ntt_lazy_op(plk_ctx* ctx, int op, const uint32_t* in, uint32_t* out,
+                                     size_t n) {
+  try {
+    if (!ctx || !in || !out) return PLK_E_ARG;
+    plk::DeviceGuard g(ctx->device);
+    return plk::ntt_lazy_op(ctx, op, in, out, n);
   } catch (...) {
     return PLK_E_DEVICE;
   }

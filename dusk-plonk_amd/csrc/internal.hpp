@@ -290,6 +290,8 @@ const MsmStats& msm_workspace_stats(const MsmWorkspace& w);
 MsmStats& msm_workspace_stats(MsmWorkspace& w);
 void fr_root_of_unity(uint32_t log_n, Fr& omega);
 int ntt_vanishing(plk_domain* d, uint64_t deg, Fr* d_out, hipStream_t s);
+// plk_debug_ntt_lazy_op (include/plk.h): the pass kernel's lazy butterfly helpers on host rows
+int ntt_lazy_op(plk_ctx* ctx, int op, const uint32_t* in, uint32_t* out, size_t n);
 // out[e] = base^e * scale, e < n (R domain; to_rx: converted to the R' domain)
 int ntt_power_table(Fr* out, const Fr& base, const Fr& scale, uint64_t n, bool to_rx,
                     hipStream_t s);

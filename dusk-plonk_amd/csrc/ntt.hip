@@ -188,9 +188,10 @@ __device__ __forceinline__ RFr add_u(const RFr& a, const RFr& b) {
   return r;
 }
 
-// a (limbs below 2^31, value below 2^260 and >= q r) -> a - q r normalised, q from the
-// unnormalised top limb (low by at most 1): value < (q + 2) 2^255 - q r <= 4r for a < 20r,
-// < 1.6r for a normalised a < 5r (q exact)
+// a (limbs below 2^31.6 as sub_u2<11> leaves them: a limb + a table limb + the carry stays
+// below 2^32; value below 2^260 and >= q r) -> a - q r normalised, q from the unnormalised top
+// limb (low by at most 1): value < (q + 2) 2^255 - q r <= 4r for a < 20r, < 1.6r for a
+// normalised a < 5r (q exact). Pinned by tests/test_ntt_lazy.py with the helpers around it.
 __device__ __forceinline__ RFr reduce_q(const RFr& a, const uint32_t* ztab) {
   constexpr uint32_t MASK = (1u << kB) - 1;
   const uint32_t* z = ztab + (a.v[kL - 1] >> (255 - kB * (kL - 1))) * kL;
@@ -239,9 +240,9 @@ __device__ __forceinline__ void r4_math(const uint32_t* twl, uint32_t TS, const 
   const RFr y0 = add_u(x0, x2), y1 = add_u(x1, x3);
   if constexpr (H1) {  // r = 0 in every group: no twiddle on x0 / x2 nor in the second stage
     const RFr y2 = reduce_q(rx_sub_u<FrCfg, 6>(x0, x2), ztab);  // < 4r
-    const RFr y3 = twmul(rx_sub_u<FrCfg, 6>(x1, x3), twl, TS, 1u << sh1);  // < 3r
+    const RFr y3 = twmul(rx_sub_u<FrCfg, 6>(x1, x3), twl, TS, 1u << sh1);  // < 2r
     o0 = reduce_q(add_u(y0, y1), ztab);             // < 20r -> < 4r
-    o2 = reduce_q(add_u(y2, y3), ztab);             // < 7r -> < 4r
+    o2 = reduce_q(add_u(y2, y3), ztab);             // < 6r -> < 4r
     o1 = reduce_q(sub_u2<11>(y0, y1), ztab);        // < 21r -> < 4r
     o3 = reduce_q(rx_sub_u<FrCfg, 5>(y2, y3), ztab);
   } else {
@@ -535,6 +536,100 @@ __global__ void __launch_bounds__(256, PLK_NTT_MINW) k_ntt_pass(const Fr* __rest
     else v = reduce_q(v, ztab);  // < 1.6r
     st_fr(&out[pos], rx_pack_canonical(v));
   }
+}
+
+// ---- plk_debug_ntt_lazy_op: the helpers above on raw limb rows ---------------------------
+// One case per thread, the functions k_ntt_pass calls (not copies), kZTab staged in LDS as
+// there. in: NIN rows of kL limbs per case, copied into RFr values unchanged; out: NOUT rows.
+// The stage twiddles of r4_math / twmul are read from LDS by index: thread t owns the indices
+// 4 t + (1, 2, 3) of planes of stride TS = 4 * blockDim, and (r, h, sh1, sh2) = (1, 2, 0, 1)
+// makes r4_math<false> read r << sh1 = 1, (r + h) << sh1 = 3 and r << sh2 = 2 of them.
+enum : int {
+  kLzReduceQ = 0, kLzAddU, kLzSubU, kLzSubU2, kLzR4, kLzR4H1, kLzR2First, kLzOddLast,
+  kLzStore0, kLzStore1, kLzStore2, kLzCount
+};
+constexpr int lz_nin(int op) {
+  switch (op) {
+    case kLzReduceQ: case kLzStore0: return 1;
+    case kLzR4: return 7;
+    case kLzR4H1: return 5;
+    case kLzR2First: return 3;
+    default: return 2;
+  }
+}
+constexpr int lz_nout(int op) {
+  return (op == kLzR4 || op == kLzR4H1) ? 4 : (op == kLzR2First || op == kLzOddLast) ? 2 : 1;
+}
+constexpr uint32_t kLzBlock = 64;
+
+__device__ __forceinline__ RFr lz_ld(const uint32_t* __restrict__ p, uint64_t row) {
+  RFr r;
+#pragma unroll
+  for (int l = 0; l < kL; ++l) r.v[l] = p[row * kL + l];
+  return r;
+}
+__device__ __forceinline__ void lz_st(uint32_t* __restrict__ p, uint64_t row, const RFr& v) {
+#pragma unroll
+  for (int l = 0; l < kL; ++l) p[row * kL + l] = v.v[l];
+}
+// the first 8 words of a row as a packed value (a table entry / a stored word)
+__device__ __forceinline__ Fr lz_words(const RFr& v) {
+  Fr w;
+#pragma unroll
+  for (int l = 0; l < 8; ++l) w.v[l] = v.v[l];
+  return w;
+}
+__device__ __forceinline__ RFr lz_row(const Fr& w) {
+  RFr v = rx_zero<FrCfg>();
+#pragma unroll
+  for (int l = 0; l < 8; ++l) v.v[l] = w.v[l];
+  return v;
+}
+
+template <int OP>
+__global__ void __launch_bounds__(kLzBlock)
+    k_ntt_lazy_op(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, Fr post_scalar,
+                  uint64_t n) {
+  constexpr int NIN = lz_nin(OP), NOUT = lz_nout(OP);
+  constexpr uint32_t TS = 4 * kLzBlock;
+  __shared__ uint32_t twl[kL * TS];
+  __shared__ uint32_t ztab[kQMax * kL];
+  const uint32_t tid = threadIdx.x;
+  const uint64_t i = (uint64_t)blockIdx.x * kLzBlock + tid;
+  const bool live = i < n;
+  for (uint32_t x = tid; x < kQMax * kL; x += kLzBlock) ztab[x] = kZTab.v[x];
+  RFr x[NIN];
+#pragma unroll
+  for (int k = 0; k < NIN; ++k) x[k] = live ? lz_ld(in, i * NIN + k) : rx_zero<FrCfg>();
+  // the case's twiddle rows (its last operands) at the thread's own indices
+  constexpr int NTW = OP == kLzR4 ? 3 : (OP == kLzR4H1 || OP == kLzR2First) ? 1 : 0;
+#pragma unroll
+  for (int k = 0; k < NTW; ++k)  // rows (a, b, c) of r4_math<false> at indices (1, 3, 2)
+    lds_st(twl, TS, 4 * tid + (k == 0 ? 1 : 4 - k), x[NIN - NTW + k]);
+  __syncthreads();
+  if (!live) return;
+  const uint32_t* tw = twl + 4 * tid;
+  RFr o[NOUT];
+  if constexpr (OP == kLzReduceQ) o[0] = reduce_q(x[0], ztab);
+  else if constexpr (OP == kLzAddU) o[0] = add_u(x[0], x[1]);
+  else if constexpr (OP == kLzSubU) o[0] = sub_u(x[0], x[1]);
+  else if constexpr (OP == kLzSubU2) o[0] = sub_u2<11>(x[0], x[1]);
+  else if constexpr (OP == kLzR4)  // twiddle rows in the order (r << sh1, (r + h) << sh1, r << sh2)
+    r4_math<false>(tw, TS, ztab, 1, 2, 0, 1, x[0], x[1], x[2], x[3], o[0], o[1], o[2], o[3]);
+  else if constexpr (OP == kLzR4H1)  // reads index 1 << sh1
+    r4_math<true>(tw, TS, ztab, 0, 1, 0, 1, x[0], x[1], x[2], x[3], o[0], o[1], o[2], o[3]);
+  else if constexpr (OP == kLzR2First) {
+    o[0] = reduce_q(add_u(x[0], x[1]), ztab);
+    o[1] = twmul(sub_u(x[0], x[1]), tw, TS, 1);
+  } else if constexpr (OP == kLzOddLast) {
+    o[0] = reduce_q(add_u(x[0], x[1]), ztab);
+    o[1] = reduce_q(rx_sub_u<FrCfg, 6>(x[0], x[1]), ztab);
+  } else if constexpr (OP == kLzStore0) o[0] = lz_row(rx_pack_canonical(reduce_q(x[0], ztab)));
+  else if constexpr (OP == kLzStore1)
+    o[0] = lz_row(rx_pack_canonical(rx_mul(x[0], rx_unpack(post_scalar))));
+  else o[0] = lz_row(rx_pack_canonical(rx_mul(x[0], rx_unpack(lz_words(x[1])))));
+#pragma unroll
+  for (int k = 0; k < NOUT; ++k) lz_st(out, i * NOUT + k, o[k]);
 }
 
 // pass twiddles: out[(j << lp) + k] = w_N^{(j k) << shift} for j < R, k < p (R' domain;
@@ -841,6 +936,37 @@ int ntt_vanishing(plk_domain* d, uint64_t deg, Fr* d_out, hipStream_t s) {
   const uint32_t nb = (uint32_t)((d->n + bs - 1) / bs);
   hipLaunchKernelGGL(k_vanishing, dim3(nb), dim3(bs), 0, s, d_out, gdeg, wdeg, (uint64_t)d->n);
   PLK_HIP_TRY(hipGetLastError());
+  return PLK_OK;
+}
+
+int ntt_lazy_op(plk_ctx* ctx, int op, const uint32_t* in, uint32_t* out, size_t n) {
+  using Kernel = void (*)(const uint32_t*, uint32_t*, Fr, uint64_t);
+  Kernel kern = nullptr;
+  switch (op) {
+#define PLK_LZ_CASE(OP) \
+  case OP: kern = k_ntt_lazy_op<OP>; break;
+    PLK_LZ_CASE(kLzReduceQ) PLK_LZ_CASE(kLzAddU) PLK_LZ_CASE(kLzSubU) PLK_LZ_CASE(kLzSubU2)
+    PLK_LZ_CASE(kLzR4) PLK_LZ_CASE(kLzR4H1) PLK_LZ_CASE(kLzR2First) PLK_LZ_CASE(kLzOddLast)
+    PLK_LZ_CASE(kLzStore0) PLK_LZ_CASE(kLzStore1) PLK_LZ_CASE(kLzStore2)
+#undef PLK_LZ_CASE
+    default: return PLK_E_ARG;
+  }
+  if (n == 0) return PLK_OK;
+  const size_t row = kL * sizeof(uint32_t);
+  const size_t in_bytes = n * lz_nin(op) * row, out_bytes = n * lz_nout(op) * row;
+  Fr scalar = fe_zero<FrCfg>();  // POST 1: the packed scale of case 0, a kernel argument
+  if (op == kLzStore1)
+    for (int l = 0; l < 8; ++l) scalar.v[l] = in[kL + l];
+  DevBuf din, dout;
+  int st;
+  if ((st = din.alloc(in_bytes)) || (st = dout.alloc(out_bytes))) return st;
+  hipStream_t s = ctx->stream;
+  PLK_HIP_TRY(hipMemcpyAsync(din.ptr, in, in_bytes, hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(kern, dim3((unsigned)((n + kLzBlock - 1) / kLzBlock)), dim3(kLzBlock), 0, s,
+                     din.as<uint32_t>(), dout.as<uint32_t>(), scalar, (uint64_t)n);
+  PLK_HIP_TRY(hipGetLastError());
+  PLK_HIP_TRY(hipMemcpyAsync(out, dout.ptr, out_bytes, hipMemcpyDeviceToHost, s));
+  PLK_HIP_TRY(stream_wait(s));
   return PLK_OK;
 }
 

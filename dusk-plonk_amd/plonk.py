@@ -40,7 +40,7 @@ ABI_SYMBOLS = (
     "plk_ntt_dev", "plk_ntt_batch_dev", "plk_srs_setup", "plk_srs_load", "plk_srs_destroy",
     "plk_srs_len", "plk_srs_points", "plk_msm", "plk_commit", "plk_commit_dev",
     "plk_srs_last_msm_stats", "plk_debug_field_op", "plk_debug_rx_op", "plk_debug_g1r_op",
-    "plk_debug_block_eval", "plk_commit_batch_dev",
+    "plk_debug_block_eval", "plk_debug_ntt_lazy_op", "plk_commit_batch_dev",
     "plk_commit_batch_dev_part",
     "plk_srs_setup_range", "plk_g1_sum", "plk_msm_sharded", "plk_srs_msm_stats_reset",
     "plk_srs_cum_msm_stats", "plk_ntt_stream", "plk_aggregate_witness",
@@ -130,6 +130,7 @@ def _lib():
                                              C.POINTER(u32)]),
             "plk_debug_field_op": (i32, [vp, i32, i32, vp, vp, vp, sz]),
             "plk_debug_rx_op": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, sz]),
+            "plk_debug_ntt_lazy_op": (i32, [vp, i32, vp, vp, sz]),
             "plk_debug_g1r_op": (i32, [vp, i32, vp, vp, vp, vp, sz]),
             "plk_debug_block_eval": (i32, [vp, vp, sz, vp, sz, C.POINTER(i32)]),
             "plk_commit_batch_dev": (i32, [vp, vp, vp, sz, vp, vp, vp]),
@@ -281,6 +282,29 @@ class Context:
         ptrs = [_ptr(o) for o in ops] + [None] * (4 - nin)
         _check(_lib().plk_debug_rx_op(self.handle, 0 if field == "fr" else 1, code + cp, *ptrs,
                                       _ptr(out), n), "plk_debug_rx_op")
+        return out
+
+    # op -> (code, operand rows, output rows) of plk_debug_ntt_lazy_op (include/plk.h)
+    NTT_LAZY_OPS = {"reduce_q": (0, 1, 1), "add_u": (1, 2, 1), "sub_u": (2, 2, 1),
+                    "sub_u2_11": (3, 2, 1), "r4": (4, 7, 4), "r4_h1": (5, 5, 4),
+                    "r2first": (6, 3, 2), "odd_last": (7, 2, 2), "store0": (8, 1, 1),
+                    "store1": (9, 2, 1), "store2": (10, 2, 1)}
+
+    def ntt_lazy_op(self, op: str, *rows) -> np.ndarray:
+        """The NTT pass kernel's lazy butterfly helpers (csrc/ntt.hip) on raw rows of 9 uint32
+        limbs (test support): op a key of NTT_LAZY_OPS, one array of n rows per operand; returns
+        [n, outputs, 9]. 'store1' applies the scale row of case 0 to every case."""
+        code, nin, nout = self.NTT_LAZY_OPS[op]
+        if len(rows) != nin:
+            raise ValueError(f"ntt_lazy_op {op} takes {nin} operand arrays")
+        ops = [np.asarray(r, dtype=np.uint32).reshape(-1, 9) for r in rows]
+        n = ops[0].shape[0]
+        if any(o.shape[0] != n for o in ops):
+            raise ValueError("ntt_lazy_op operands differ in length")
+        cases = np.ascontiguousarray(np.stack(ops, axis=1))  # [n, operands, 9]
+        out = np.zeros((n, nout, 9), dtype=np.uint32)
+        _check(_lib().plk_debug_ntt_lazy_op(self.handle, code, _ptr(cases), _ptr(out), n),
+               "plk_debug_ntt_lazy_op")
         return out
 
     def g1r_op(self, op: str, p, q=None, flags=None) -> np.ndarray:

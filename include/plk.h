@@ -541,6 +541,24 @@ int plk_debug_field_op(plk_ctx* ctx, int field, int op, const uint64_t* a, const
  * The two tests write 0 / 1 into limb 0 of an otherwise zero row. Other codes: PLK_E_ARG. */
 int plk_debug_rx_op(plk_ctx* ctx, int field, int op, const uint32_t* a, const uint32_t* b,
                     const uint32_t* c, const uint32_t* d, uint32_t* out, size_t n);
+/* The lazy butterfly helpers of the NTT pass kernel (csrc/ntt.hip), the functions k_ntt_pass
+ * calls, on raw Fr limb rows (9 uint32 each, copied into the kernel's values unchanged). in holds
+ * n cases of (operand rows of the op) rows, out n cases of (outputs) rows; a twiddle t is an
+ * R'-domain limb row that the hook stages in LDS where the helper reads it. Ops (operands ->
+ * outputs):
+ *    0 reduce_q a                              1 add_u a + b            2 sub_u a + 3r - b
+ *    3 sub_u2<11> a + 11r - b, the raw unnormalised limbs
+ *    4 r4_math<false> x0 x1 x2 x3, t(r s1) t((r + h) s1) t(r s2) -> o0 o1 o2 o3
+ *    5 r4_math<true> x0 x1 x2 x3, t -> o0 o1 o2 o3
+ *    6 the first stage of an odd radix: a v t -> reduce_q(add_u(a, v)), twmul(sub_u(a, v), t)
+ *    7 the last stage of an odd radix: a c -> reduce_q(add_u(a, c)), reduce_q(rx_sub_u<6>(a, c))
+ *    8 the store without a scale (POST 0): v -> rx_pack_canonical(reduce_q(v))
+ *    9 the store with the scalar (POST 1): v s -> rx_pack_canonical(rx_mul(v, rx_unpack(s))); s is
+ *      the kernel argument, taken from case 0 for all cases
+ *   10 the store with the scale table (POST 2): the same with each case's own s
+ * s is a packed canonical R'-domain value in the first 8 words of its row; the stores return the
+ * packed word the same way (word 8 is 0). Other codes, a NULL argument: PLK_E_ARG. */
+int plk_debug_ntt_lazy_op(plk_ctx* ctx, int op, const uint32_t* in, uint32_t* out, size_t n);
 /* The XYZZ group law over that field (csrc/g1r.hpp) on raw limb rows: p, q and out are rows of
  * 4 x 13 limbs (X, Y, ZZ, ZZZ; R' = 2^390 domain), an affine q uses X and Y only. Bit 0 of
  * flags[i] (flags may be NULL) negates q: the lazy 4p - Y (rx_neg_lazy) for the lazy ops,

@@ -152,6 +152,7 @@ def test_hooks_reject_bad_arguments_without_gpu(plk):
     lib = plk.plonk._lib()
     assert lib.plk_debug_rx_op(None, 1, 0, None, None, None, None, None, 0) == plk.PLK_E_ARG
     assert lib.plk_debug_g1r_op(None, 0, None, None, None, None, 0) == plk.PLK_E_ARG
+    assert lib.plk_debug_ntt_lazy_op(None, 0, None, None, 0) == plk.PLK_E_ARG
 
 
 # ------------------------------------------------------------------------------- GPU tests
