@@ -2,8 +2,12 @@
 // plk_debug_field_op: the packed field of ff.hpp; plk_debug_rx_op: the redundant-limb field of
 // ffr.hpp on raw limb rows; plk_debug_ntt_lazy_op: the NTT pass' lazy butterfly helpers (the
 // kernel is in ntt.hip); plk_debug_g1r_op: the XYZZ group law of g1r.hpp on raw limb rows;
-// plk_debug_block_eval: the prover's forward block transform onto a key's quotient domain.
+// plk_debug_block_eval: the prover's forward block transform onto a key's quotient domain;
+// plk_debug_prover_stage: one pk_* launcher of prover_kernels.hip on caller arrays.
 #include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <vector>
 
 #include "g1r.hpp"
 #include "internal.hpp"
@@ -282,6 +286,217 @@ int run_rows(plk_ctx* ctx, K kern, const RowArg (&in)[NA], uint32_t* out, size_t
   return PLK_OK;
 }
 
+
+// ---- plk_debug_prover_stage: the prover's pk_* launchers on caller arrays ----------------
+enum : int {
+  kStPermNumDen = 0, kStScan, kStQuotient, kStPiSparse, kStPiCoef, kStCosetCombine, kStEval,
+  kStLinComb, kStScalePowers, kStRuffini, kStCount
+};
+
+Fr fr_from_abi(const plk_fr& a) {
+  Fr r;
+  for (int i = 0; i < 4; ++i) {
+    r.v[2 * i] = (uint32_t)a.l[i];
+    r.v[2 * i + 1] = (uint32_t)(a.l[i] >> 32);
+  }
+  return r;
+}
+
+struct StageCall {
+  int stage;
+  const uint64_t* const* in;
+  const size_t* len;  // Fr elements per input array
+  size_t n_in;
+  const plk_fr* sc;
+  size_t n_sc;
+  const uint64_t* par;
+  size_t n_par;
+  uint64_t* out;
+  size_t out_cap;  // Fr elements
+};
+
+// The stage's launcher on device copies of c.in; PLK_E_ARG unless the array lengths are the
+// ones the kernels index (every read and write of a launch lies inside an array checked here).
+int run_stage(plk_ctx* ctx, const StageCall& c) {
+  hipStream_t s = ctx->stream;
+  int st;
+  std::vector<DevBuf> d(c.n_in);
+  for (size_t k = 0; k < c.n_in; ++k) {
+    if (c.len[k] == 0) continue;
+    if ((st = d[k].alloc(c.len[k] * sizeof(Fr)))) return st;
+    PLK_HIP_TRY(hipMemcpyAsync(d[k].ptr, c.in[k], c.len[k] * sizeof(Fr), hipMemcpyHostToDevice, s));
+  }
+  auto in = [&](size_t k) { return d[k].as<Fr>(); };
+  auto sc = [&](size_t k) { return fr_from_abi(c.sc[k]); };
+  DevBuf dout;
+  auto finish = [&](const Fr* res, size_t count) -> int {
+    if (count) PLK_HIP_TRY(hipMemcpyAsync(c.out, res, count * sizeof(Fr), hipMemcpyDeviceToHost, s));
+    PLK_HIP_TRY(stream_wait(s));
+    return PLK_OK;
+  };
+  switch (c.stage) {
+    case kStPermNumDen: {  // in: wires (4 x stride), sigmas (4 x n), elements; sc: beta gamma k1 k2 k3
+      if (c.n_in != 3 || c.n_sc != 5 || c.n_par != 2) return PLK_E_ARG;
+      const uint64_t n = c.par[0], ws = c.par[1];
+      if (n == 0) return PLK_OK;
+      if (ws < n || c.len[0] != 4 * ws || c.len[1] != 4 * n || c.len[2] != n || c.out_cap < 2 * n)
+        return PLK_E_ARG;
+      if ((st = dout.alloc(2 * n * sizeof(Fr)))) return st;
+      if ((st = pk_perm_numden(in(0), ws, in(1), in(2), n, sc(0), sc(1), sc(2), sc(3), sc(4),
+                               dout.as<Fr>(), dout.as<Fr>() + n, s)))
+        return st;
+      return finish(dout.as<Fr>(), 2 * n);
+    }
+    case kStScan: {  // par: flags (1 mul, 2 suffix, 4 exclusive, 8 in place); out: n values, tmp[nb]
+      if (c.n_in != 1 || c.n_par != 1 || c.par[0] > 15) return PLK_E_ARG;
+      const uint64_t n = c.len[0], f = c.par[0];
+      if (n == 0) return PLK_OK;
+      if (c.out_cap < n + 1) return PLK_E_ARG;
+      const uint64_t nt = pk_scan_tmp_elems(n);
+      DevBuf tmp;
+      if ((st = tmp.alloc(nt * sizeof(Fr)))) return st;
+      Fr* res = in(0);
+      if (!(f & 8)) {
+        if ((st = dout.alloc(n * sizeof(Fr)))) return st;
+        res = dout.as<Fr>();
+      }
+      if ((st = pk_scan(in(0), res, n, f & 1, f & 2, f & 4, tmp.as<Fr>(), s))) return st;
+      PLK_HIP_TRY(hipMemcpyAsync(c.out + 4 * n, tmp.as<Fr>() + (nt - 1), sizeof(Fr),
+                                 hipMemcpyDeviceToHost, s));
+      return finish(res, n);
+    }
+    case kStQuotient: {
+      // in: a b c d z pi l1 sel sigma elements, as k_quotient reads them (QuotientArgs; pi of
+      // length 0: no public inputs); sc: alpha beta gamma range_sep logic_sep fixed_sep var_sep,
+      // s_m[blocks], vh_inv[blocks]; par: log2 n, blocks, has_range | 2 has_logic | 4 has_fixed |
+      // 8 has_var
+      if (c.n_in != 10 || c.n_par != 3 || c.par[0] > 24 || c.par[2] > 15) return PLK_E_ARG;
+      const uint64_t blocks = c.par[1], n = 1ull << c.par[0], nq = blocks * n;
+      if ((blocks != kQBlocks && blocks != kQBlocksSmall) || c.n_sc != 7 + 2 * blocks) return PLK_E_ARG;
+      for (int k = 0; k < 7; ++k)
+        if (c.len[k] != nq && !(k == 5 && c.len[k] == 0)) return PLK_E_ARG;
+      if (c.len[7] != SEL_COUNTQ * nq || c.len[8] != 4 * nq || c.len[9] != n || c.out_cap < nq)
+        return PLK_E_ARG;
+      if ((st = dout.alloc(nq * sizeof(Fr)))) return st;
+      QuotientArgs qa{};
+      qa.a = in(0), qa.b = in(1), qa.c = in(2), qa.d = in(3), qa.z = in(4);
+      qa.pi = c.len[5] ? in(5) : nullptr;
+      qa.l1 = in(6), qa.sel = in(7), qa.sigma = in(8), qa.elements = in(9);
+      qa.out = dout.as<Fr>();
+      qa.nq = nq;
+      qa.log_blk = (uint32_t)c.par[0];
+      Fr s_m[kQBlocksMax], vh[kQBlocksMax];
+      for (uint64_t m = 0; m < blocks; ++m) s_m[m] = sc(7 + m), vh[m] = sc(7 + blocks + m);
+      const uint64_t f = c.par[2];
+      quotient_constants(qa, QuotientChallenges{sc(0), sc(1), sc(2), sc(3), sc(4), sc(5), sc(6)}, s_m,
+                         vh, (int)blocks, f & 1, f & 2, f & 4, f & 8);
+      if ((st = pk_quotient(qa, s))) return st;
+      return finish(dout.as<Fr>(), nq);
+    }
+    case kStPiSparse: {  // in: l1 (nq); sc: the values; par: log2 n, then the gate indices
+      if (c.n_in != 1 || c.n_par != 1 + c.n_sc || c.par[0] > 24) return PLK_E_ARG;
+      const uint64_t nq = c.len[0];
+      if (nq == 0) return PLK_OK;
+      if (nq & ((1ull << c.par[0]) - 1) || c.out_cap < nq) return PLK_E_ARG;
+      PiSparse ps{};
+      ps.count = (uint32_t)c.n_sc;  // 0 or more than kPiSparse: pk_pi_sparse refuses
+      for (size_t k = 0; k < c.n_sc && k < (size_t)kPiSparse; ++k) {
+        ps.idx[k] = (uint32_t)c.par[1 + k];
+        ps.v[k] = sc(k);
+      }
+      if ((st = dout.alloc(nq * sizeof(Fr)))) return st;
+      if ((st = pk_pi_sparse(ps, in(0), (uint32_t)c.par[0], nq, dout.as<Fr>(), s))) return st;
+      return finish(dout.as<Fr>(), nq);
+    }
+    case kStPiCoef: {  // in: tw_inv (n, R'); sc: value n^-1 per input; par: the gate indices
+      if (c.n_in != 1 || c.n_par != c.n_sc) return PLK_E_ARG;
+      const uint64_t n = c.len[0];
+      if (n == 0) return PLK_OK;
+      if (c.out_cap < n) return PLK_E_ARG;
+      PiDirect pd{};
+      pd.count = (uint32_t)c.n_sc;  // more than kPiDirect: pk_pi_coef refuses
+      for (size_t k = 0; k < c.n_sc && k < (size_t)kPiDirect; ++k) {
+        pd.idx[k] = c.par[k];
+        pd.c[k] = sc(k);
+      }
+      if ((st = dout.alloc(n * sizeof(Fr)))) return st;
+      if ((st = pk_pi_coef(pd, in(0), n, dout.as<Fr>(), s))) return st;
+      return finish(dout.as<Fr>(), n);
+    }
+    case kStCosetCombine: {  // in: blocks x n coefficients; sc: blocks^2 matrix entries (R'); par: blocks
+      if (c.n_in != 1 || c.n_par != 1) return PLK_E_ARG;
+      const uint64_t blocks = c.par[0];
+      if (blocks == 0 || blocks > 64 || c.n_sc != blocks * blocks || c.len[0] % blocks) return PLK_E_ARG;
+      const uint64_t n = c.len[0] / blocks;
+      if (n == 0) return PLK_OK;
+      if (c.out_cap < blocks * n) return PLK_E_ARG;
+      CombineMat mat{};
+      for (size_t k = 0; k < c.n_sc && k < (size_t)(kQBlocksMax * kQBlocksMax); ++k) mat.m[k] = sc(k);
+      if ((st = dout.alloc(blocks * n * sizeof(Fr)))) return st;
+      if ((st = pk_coset_combine(in(0), n, (int)blocks, mat, dout.as<Fr>(), s))) return st;
+      return finish(dout.as<Fr>(), blocks * n);
+    }
+    case kStEval: {  // in: the polynomials; sc: one point each
+      if (c.n_in > (size_t)kMaxEval || c.n_sc != c.n_in || c.n_par != 0) return PLK_E_ARG;
+      const uint32_t count = (uint32_t)c.n_in;
+      if (count == 0) return PLK_OK;
+      if (c.out_cap < count) return PLK_E_ARG;
+      EvalBatch eb{};
+      uint64_t max_len = 0;
+      for (uint32_t k = 0; k < count; ++k) {
+        eb.poly[k] = in(k);
+        eb.len[k] = c.len[k];
+        eb.x[k] = sc(k);
+        max_len = std::max<uint64_t>(max_len, c.len[k]);
+      }
+      DevBuf partial;
+      const size_t mb = pk_eval_max_blocks(max_len ? max_len : 1);
+      if ((st = partial.alloc(mb * count * sizeof(Fr))) || (st = dout.alloc(count * sizeof(Fr))))
+        return st;
+      if ((st = pk_eval(eb, count, max_len, partial.as<Fr>(), dout.as<Fr>(), s))) return st;
+      return finish(dout.as<Fr>(), count);
+    }
+    case kStLinComb: {  // in: the terms; sc: one scalar each; par: len_out
+      if (c.n_in > (size_t)kMaxTerms || c.n_sc != c.n_in || c.n_par != 1) return PLK_E_ARG;
+      const uint64_t len_out = c.par[0];
+      if (len_out == 0) return PLK_OK;
+      if (c.out_cap < len_out) return PLK_E_ARG;
+      LinComb lc{};
+      lc.terms = (uint32_t)c.n_in;
+      for (uint32_t t = 0; t < lc.terms; ++t) {
+        lc.p[t] = in(t);
+        lc.len[t] = c.len[t];
+        lc.s[t] = sc(t);
+      }
+      if ((st = dout.alloc(len_out * sizeof(Fr)))) return st;
+      if ((st = pk_lincomb(lc, dout.as<Fr>(), len_out, s))) return st;
+      return finish(dout.as<Fr>(), len_out);
+    }
+    case kStScalePowers: {  // in: c; sc: x; par: shift
+      if (c.n_in != 1 || c.n_sc != 1 || c.n_par != 1) return PLK_E_ARG;
+      const uint64_t len = c.len[0];
+      if (len == 0) return PLK_OK;
+      if (c.out_cap < len) return PLK_E_ARG;
+      if ((st = dout.alloc(len * sizeof(Fr)))) return st;
+      if ((st = pk_scale_powers(in(0), len, sc(0), c.par[0], dout.as<Fr>(), s))) return st;
+      return finish(dout.as<Fr>(), len);
+    }
+    case kStRuffini: {  // in: c; sc: z (not 0); out: len - 1 quotient coefficients
+      if (c.n_in != 1 || c.n_sc != 1 || c.n_par != 0) return PLK_E_ARG;
+      const uint64_t len = c.len[0];
+      if (len <= 1) return PLK_OK;
+      if (c.out_cap < len - 1 || fe_is_zero(sc(0))) return PLK_E_ARG;
+      DevBuf tmp, scan;  // as the prover: tmp_a and scan_tmp beside the aggregate and w
+      if ((st = dout.alloc((len - 1) * sizeof(Fr))) || (st = tmp.alloc(len * sizeof(Fr))) ||
+          (st = scan.alloc(pk_scan_tmp_elems(len) * sizeof(Fr))))
+        return st;
+      if ((st = pk_ruffini(in(0), len, sc(0), dout.as<Fr>(), tmp.as<Fr>(), scan.as<Fr>(), s))) return st;
+      return finish(dout.as<Fr>(), len - 1);
+    }
+    default: return PLK_E_ARG;
+  }
+}
+
 }  // namespace
 }  // namespace plk
 
@@ -378,6 +593,26 @@ extern "C" int plk_debug_block_eval(plk_key* key, const uint64_t* coef, size_t l
     PLK_HIP_TRY(hipMemcpyAsync(out, dout.ptr, total * sizeof(plk::Fr), hipMemcpyDeviceToHost, s));
     PLK_HIP_TRY(plk::stream_wait(s));
     return PLK_OK;
+  } catch (...) {
+    return PLK_E_DEVICE;
+  }
+}
+
+// the pk_* launcher the prover calls for `stage`, on device copies of the caller's arrays
+extern "C" int plk_debug_prover_stage(plk_ctx* ctx, int stage, const uint64_t* const* in,
+                                      const size_t* in_len, size_t n_in, const plk_fr* scalars,
+                                      size_t n_scalars, const uint64_t* params, size_t n_params,
+                                      uint64_t* out, size_t out_cap) {
+  try {
+    if (!ctx || stage < 0 || stage >= plk::kStCount) return PLK_E_ARG;
+    if ((n_in && (!in || !in_len)) || (n_scalars && !scalars) || (n_params && !params) ||
+        (out_cap && !out) || n_in > 32)
+      return PLK_E_ARG;
+    for (size_t k = 0; k < n_in; ++k)
+      if (in_len[k] > ((size_t)1 << 28) || (in_len[k] && !in[k])) return PLK_E_ARG;
+    const plk::StageCall c{stage, in, in_len, n_in, scalars, n_scalars, params, n_params, out, out_cap};
+    plk::DeviceGuard g(ctx->device);
+    return plk::run_stage(ctx, c);
   } catch (...) {
     return PLK_E_DEVICE;
   }

@@ -455,6 +455,60 @@ Fr d2h_fr(const Fr* p, hipStream_t s) {
 
 }  // namespace
 
+namespace plk {
+void quotient_constants(QuotientArgs& qa, const QuotientChallenges& ch, const Fr* s_m,
+                        const Fr* vh_inv, int blocks, bool has_range, bool has_logic,
+                        bool has_fixed, bool has_var) {
+  const Fr alpha2 = fe_sqr(ch.alpha);
+  qa.alpha2 = alpha2;
+  qa.alpha = ch.alpha;
+  qa.beta = ch.beta;
+  qa.gamma = ch.gamma;
+  qa.k1 = fr_u64(7);
+  qa.k2 = fr_u64(13);
+  qa.k3 = fr_u64(17);
+  qa.range_sep = ch.range_sep;
+  qa.kappa = fe_sqr(ch.range_sep);
+  qa.kappa2 = fe_sqr(qa.kappa);
+  qa.kappa3 = fe_mul(qa.kappa2, qa.kappa);
+  qa.has_range = has_range ? 1 : 0;
+  qa.logic_sep = ch.logic_sep;
+  qa.lk = fe_sqr(ch.logic_sep);
+  qa.lk2 = fe_sqr(qa.lk);
+  qa.lk3 = fe_mul(qa.lk2, qa.lk);
+  qa.lk4 = fe_mul(qa.lk3, qa.lk);
+  qa.has_logic = has_logic ? 1 : 0;
+  qa.fixed_sep = ch.fixed_sep;
+  qa.fk = fe_sqr(ch.fixed_sep);
+  qa.fk2 = fe_sqr(qa.fk);
+  qa.fk3 = fe_mul(qa.fk2, qa.fk);
+  qa.var_sep = ch.var_sep;
+  qa.vk = fe_sqr(ch.var_sep);
+  qa.vk2 = fe_sqr(qa.vk);
+  qa.edwards_d = edwards_d();
+  qa.has_fixed = has_fixed ? 1 : 0;
+  qa.has_var = has_var ? 1 : 0;
+  for (int j = 0; j < blocks; ++j) qa.vh_inv[j] = vh_inv[j];
+  // exponent-scaled constants for k_quotient (x[e] = x R 2^(-5e); [-1] = R' domain)
+  auto em1 = [](const Fr& x) { return fe_to_rx_domain(x); };
+  auto em2 = [](const Fr& x) { return fe_to_rx_domain(fe_to_rx_domain(x)); };
+  const Fr one = fe_one<FrCfg>(), two = fe_dbl(one);
+  for (int mb = 0; mb < blocks; ++mb) qa.rx_bg[mb] = em2(fe_mul(ch.beta, s_m[mb]));
+  qa.rx_beta = em2(ch.beta);
+  qa.rx_gamma = em1(ch.gamma);
+  qa.rx_one_w = em1(one);
+  qa.rx_two_w = em1(two);
+  qa.rx_three_w = em1(fe_add(two, one));
+  qa.rx_kappa = em1(qa.kappa);
+  qa.rx_kappa2 = em1(qa.kappa2);
+  qa.rx_kappa3 = em1(qa.kappa3);
+  qa.rx_alpha2 = em1(alpha2);
+  for (int j = 0; j < blocks; ++j) qa.rx_vh[j] = em2(vh_inv[j]);
+  qa.rx_32 = fr_u64(32);
+  qa.rx_inv32 = fe_inv(qa.rx_32);
+}
+}  // namespace plk
+
 // sigma values k_col(next) * w^gate(next) from wire codes (4*gate + col)
 namespace plk {
 namespace {
@@ -1304,7 +1358,6 @@ int plk_prover_prove(plk_prover* P, const plk_composer* cs, uint64_t seed, plk_p
     qa.d = ev + 4 * nq;
     qa.pi = pis.empty() ? nullptr : ev + 5 * nq;
     qa.l1 = key->l1q.as<Fr>();
-    qa.alpha2 = alpha2;
     qa.sel = key->selq.as<Fr>();
     qa.sigma = key->sigmaq.as<Fr>();
     qa.elements = key->dom->tw_fwd.as<Fr>();
@@ -1312,52 +1365,12 @@ int plk_prover_prove(plk_prover* P, const plk_composer* cs, uint64_t seed, plk_p
     qa.nq = nq;
     qa.log_blk = key->k;
     qa.g = key->dom->g;
-    qa.alpha = alpha;
-    qa.beta = beta;
-    qa.gamma = gamma;
-    qa.k1 = K1;
-    qa.k2 = K2;
-    qa.k3 = K3;
-    qa.range_sep = range_sep;
-    qa.kappa = fe_sqr(range_sep);
-    qa.kappa2 = fe_sqr(qa.kappa);
-    qa.kappa3 = fe_mul(qa.kappa2, qa.kappa);
-    qa.has_range = key->has_range ? 1 : 0;
-    qa.logic_sep = logic_sep;
-    qa.lk = fe_sqr(logic_sep);
-    qa.lk2 = fe_sqr(qa.lk);
-    qa.lk3 = fe_mul(qa.lk2, qa.lk);
-    qa.lk4 = fe_mul(qa.lk3, qa.lk);
-    qa.has_logic = key->has_logic ? 1 : 0;
-    qa.fixed_sep = fixed_sep;
-    qa.fk = fe_sqr(fixed_sep);
-    qa.fk2 = fe_sqr(qa.fk);
-    qa.fk3 = fe_mul(qa.fk2, qa.fk);
-    qa.var_sep = var_sep;
-    qa.vk = fe_sqr(var_sep);
-    qa.vk2 = fe_sqr(qa.vk);
-    qa.edwards_d = edwards_d();
-    qa.has_fixed = key->has_fixed ? 1 : 0;
-    qa.has_var = key->has_var ? 1 : 0;
-    for (int j = 0; j < QB; ++j) qa.vh_inv[j] = key->vh_inv[j];
-    {  // exponent-scaled constants for k_quotient (x[e] = x R 2^(-5e); [-1] = R' domain)
-      auto em1 = [](const Fr& x) { return fe_to_rx_domain(x); };
-      auto em2 = [](const Fr& x) { return fe_to_rx_domain(fe_to_rx_domain(x)); };
-      const Fr one = fe_one<FrCfg>(), two = fe_dbl(one);
-      for (int mb = 0; mb < QB; ++mb) qa.rx_bg[mb] = em2(fe_mul(beta, key->s_m[mb]));
-      qa.rx_beta = em2(beta);
-      qa.rx_gamma = em1(gamma);
-      qa.rx_one_w = em1(one);
-      qa.rx_two_w = em1(two);
-      qa.rx_three_w = em1(fe_add(two, one));
-      qa.rx_kappa = em1(qa.kappa);
-      qa.rx_kappa2 = em1(qa.kappa2);
-      qa.rx_kappa3 = em1(qa.kappa3);
-      qa.rx_alpha2 = em1(alpha2);
-      for (int j = 0; j < QB; ++j) qa.rx_vh[j] = em2(key->vh_inv[j]);
-      qa.rx_32 = fr_u64(32);
-      qa.rx_inv32 = fe_inv(qa.rx_32);
-    }
+    // the challenges, their powers and the exponent-scaled constants (shared with
+    // plk_debug_prover_stage, debug.hip)
+    quotient_constants(qa, QuotientChallenges{alpha, beta, gamma, range_sep, logic_sep, fixed_sep,
+                                              var_sep},
+                       key->s_m, key->vh_inv, QB, key->has_range, key->has_logic, key->has_fixed,
+                       key->has_var);
     TRY(pk_quotient(qa, s));
     Fr* tc = P->t_coef.as<Fr>();
     {  // t = coset_idft over the quotient domain (quotient_poly.rs:115): the QB blocks' inverse

@@ -100,6 +100,18 @@ struct QuotientArgs {
   Fr rx_inv32, rx_32;                   // 2^-5 and 2^5 (R domain): k_quotient_ext converts
 };
 
+// The transcript challenges k_quotient / k_quotient_ext take (R domain)
+struct QuotientChallenges {
+  Fr alpha, beta, gamma, range_sep, logic_sep, fixed_sep, var_sep;
+};
+// Every field of qa that is neither an array pointer nor a size (nq, log_blk, g): the
+// challenges, K1..K3, the kappa powers, the has_* flags, vh_inv[] and the exponent-scaled
+// constants, from the challenges and the key's s_m[] / vh_inv[] (`blocks` entries each).
+// Host code (prover.hip); the prover and plk_debug_prover_stage both fill QuotientArgs here.
+void quotient_constants(QuotientArgs& qa, const QuotientChallenges& ch, const Fr* s_m,
+                        const Fr* vh_inv, int blocks, bool has_range, bool has_logic,
+                        bool has_fixed, bool has_var);
+
 constexpr int kMaxEval = 28;  // 16 proof evaluations + the linearisation terms at z
 struct EvalBatch {
   const Fr* poly[kMaxEval];

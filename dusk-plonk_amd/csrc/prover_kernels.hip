@@ -42,6 +42,9 @@ __device__ __forceinline__ RFr ldr(const Fr* p) { return rx_unpack(ldf(p)); }
 // a + b + c limb by limb, no carries (a, b, c normalised, each below 2r): limbs below
 // 3 * 2^29, value below 6r. Only as a multiplicand of a normalised operand below 6r: columns
 // 9 * 1.5 * 2^59 + 9 * 2^58 < 2^64, product 36 r^2 / R' + r < 2r (R' / r > 70).
+// (Both callers add a canonical wire, a canonical gamma and one product below 2r: below 4r,
+// products at most 16 r^2. tests/prover_stage_ref.py propagates these bounds through
+// k_perm_numden and k_quotient and asserts each of them.)
 __device__ __forceinline__ RFr add3_u(const RFr& a, const RFr& b, const RFr& c) {
   RFr r;
 #pragma unroll
@@ -340,7 +343,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))
   const RFr z = ldr(&q.z[i]), z_next = ldr(&q.z[nx]);
   // arithmetic widget: q_arith (q_m a b + q_l a + q_r b + q_o c + q_4 d + q_c), terms [0]
   // (pairs of products share one reduction, rx_mul_add; the four terms summed carry-free:
-  // limbs below 2^31, value below 8r, times the normalised q_arith: 16 r^2 / R' + r < 2r)
+  // limbs below 2^31, value below 7r (three products below 2r and the canonical q_c), times the
+  // canonical q_arith: 7 r^2 / R' + r < 2r, columns 9 * 2^60 + 9 * 2^58 < 2^64)
   RFr t = rx_mul(ldr(&q.sel[SEL_QM * N + i]), rx_mul(a, b));
   const RFr lr = rx_mul_add(ldr(&q.sel[SEL_QL * N + i]), a, ldr(&q.sel[SEL_QR * N + i]), b);
   const RFr o4 = rx_mul_add(ldr(&q.sel[SEL_QO * N + i]), c, ldr(&q.sel[SEL_Q4 * N + i]), d);
@@ -388,11 +392,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))
   cp = rx_mul(cp, z_next);  // [0]
   // alpha^2 L1(X): coset_dft is linear, so alpha^2 * coset_dft(idft(e_0)) equals the
   // reference's coset_dft(idft(alpha^2 e_0)) exactly. alpha (id - cp) + alpha^2 (z - 1) L1
-  // with one reduction: (id - cp + 3r) carry-free, (5r * 2r + 2r * 2r) / R' + r < 2r
+  // with one reduction: (id - cp + 3r) carry-free (limbs below 3 * 2^29, value below 5r), alpha
+  // and alpha^2 canonical: (5r * r + 2r * r) / R' + r < 2r, columns 9 * (3 + 1 + 1) * 2^58 < 2^64
   const RFr zm1l1 = rx_mul(rx_sub_u<FrCfg, 3>(z, rx_unpack(fe_one<FrCfg>())), ldr(&q.l1[i]));
   const RFr perm = rx_mul_add(rx_sub_u<FrCfg, 3>(id, cp), rx_unpack(q.alpha), zm1l1,
                               rx_unpack(q.rx_alpha2));  // [1]
-  if (FINAL) {  // t + perm carry-free (below 4r) times the normalised 1 / v_h
+  if (FINAL) {  // t + perm carry-free (limbs below 2^30, below 4r) times the canonical 1 / v_h
     RFr num = t;
 #pragma unroll
     for (int l = 0; l < RxShape<FrCfg>::L; ++l) num.v[l] += perm.v[l];

@@ -40,7 +40,8 @@ ABI_SYMBOLS = (
     "plk_ntt_dev", "plk_ntt_batch_dev", "plk_srs_setup", "plk_srs_load", "plk_srs_destroy",
     "plk_srs_len", "plk_srs_points", "plk_msm", "plk_commit", "plk_commit_dev",
     "plk_srs_last_msm_stats", "plk_debug_field_op", "plk_debug_rx_op", "plk_debug_g1r_op",
-    "plk_debug_block_eval", "plk_debug_ntt_lazy_op", "plk_commit_batch_dev",
+    "plk_debug_block_eval", "plk_debug_ntt_lazy_op", "plk_debug_prover_stage",
+    "plk_commit_batch_dev",
     "plk_commit_batch_dev_part",
     "plk_srs_setup_range", "plk_g1_sum", "plk_msm_sharded", "plk_srs_msm_stats_reset",
     "plk_srs_cum_msm_stats", "plk_ntt_stream", "plk_aggregate_witness",
@@ -133,6 +134,7 @@ def _lib():
             "plk_debug_ntt_lazy_op": (i32, [vp, i32, vp, vp, sz]),
             "plk_debug_g1r_op": (i32, [vp, i32, vp, vp, vp, vp, sz]),
             "plk_debug_block_eval": (i32, [vp, vp, sz, vp, sz, C.POINTER(i32)]),
+            "plk_debug_prover_stage": (i32, [vp, i32, vp, vp, sz, vp, sz, vp, sz, vp, sz]),
             "plk_commit_batch_dev": (i32, [vp, vp, vp, sz, vp, vp, vp]),
             "plk_commit_batch_dev_part": (i32, [vp, vp, vp, sz, u32, u32, vp, vp, vp]),
             "plk_srs_setup_range": (i32, [vp, vp, u64, sz, vp, pp]),
@@ -323,6 +325,27 @@ class Context:
                                        None if q is None else _ptr(q),
                                        None if flags is None else _ptr(flags), _ptr(out), n),
                "plk_debug_g1r_op")
+        return out
+
+    # stage -> code of plk_debug_prover_stage (include/plk.h)
+    PROVER_STAGES = {"perm_numden": 0, "scan": 1, "quotient": 2, "pi_sparse": 3, "pi_coef": 4,
+                     "coset_combine": 5, "eval": 6, "lincomb": 7, "scale_powers": 8, "ruffini": 9}
+
+    def prover_stage(self, stage, arrays=(), scalars=(), params=(), out_len: int = 0) -> np.ndarray:
+        """One pk_* launcher of the prover (csrc/prover_kernels.hip) on host arrays (test
+        support): stage a key of PROVER_STAGES (or a raw code), arrays uint64[len, 4] Montgomery
+        words each, scalars uint64[k, 4], params integers; returns uint64[out_len, 4]."""
+        code = self.PROVER_STAGES[stage] if isinstance(stage, str) else int(stage)
+        arrs = [np.ascontiguousarray(np.asarray(a, dtype=np.uint64).reshape(-1, 4)) for a in arrays]
+        ptrs = (C.c_void_p * max(len(arrs), 1))(*[a.ctypes.data if a.shape[0] else None for a in arrs])
+        lens = (C.c_size_t * max(len(arrs), 1))(*[a.shape[0] for a in arrs])
+        sc = np.ascontiguousarray(np.asarray(scalars, dtype=np.uint64).reshape(-1, 4))
+        par = np.ascontiguousarray(np.asarray(list(params), dtype=np.uint64).reshape(-1))
+        out = np.zeros((out_len, 4), dtype=np.uint64)
+        _check(_lib().plk_debug_prover_stage(
+            self.handle, code, ptrs if arrs else None, lens if arrs else None, len(arrs),
+            _ptr(sc) if sc.shape[0] else None, sc.shape[0], _ptr(par) if par.shape[0] else None,
+            par.shape[0], _ptr(out) if out_len else None, out_len), "plk_debug_prover_stage")
         return out
 
     def domain(self, k: int) -> C.c_void_p:

@@ -581,6 +581,36 @@ int plk_debug_g1r_op(plk_ctx* ctx, int op, const uint32_t* p, const uint32_t* q,
  * receives the block count. out == NULL only reports the block count. */
 int plk_debug_block_eval(plk_key* key, const uint64_t* coef, size_t len, uint64_t* out,
                          size_t out_cap, int* blocks_out);
+/* One stage of the prover's rounds on caller arrays: the arrays are copied to the device, the
+ * pk_* launcher the prover calls for that stage runs on them (csrc/prover_kernels.hip; nothing is
+ * computed on the host beyond what the launcher itself does), and the result is copied back.
+ * in[k] holds in_len[k] field elements (4 uint64 each, Montgomery form unless noted), scalars are
+ * Montgomery-form plk_fr, out takes out_cap elements. Stages (inputs; scalars; params -> out):
+ *   0 pk_perm_numden: wires (4 columns of `stride`), sigmas (4 x n), elements (n); beta gamma k1
+ *     k2 k3; n, stride >= n -> num (n) then den (n)
+ *   1 pk_scan: data (n); -; flags 1 multiply (else add) | 2 suffix | 4 exclusive | 8 in place ->
+ *     the n outputs, then the grand total the prover reads at tmp[blocks]
+ *   2 pk_quotient: a b c d z pi l1 sel sigma elements exactly as k_quotient reads them: nq =
+ *     blocks * n points each, sel 11 rows and sigma 4 rows of nq, elements n; the wires at exponent
+ *     -1 (the values times 2^5), pi at +1 (times 2^-5; length 0: no public inputs), the rest plain;
+ *     alpha beta gamma range_sep logic_sep fixed_sep var_sep, s_m[blocks], vh_inv[blocks];
+ *     log2 n, blocks (5 or 6), 1 has_range | 2 has_logic | 4 has_fixed | 8 has_var -> t (nq).
+ *     The constants come from the function the prover fills its QuotientArgs with.
+ *   3 pk_pi_sparse: l1 (nq); the values; log2 n, then one gate index per value -> the PI row (nq)
+ *   4 pk_pi_coef: tw_inv (n; w^-e times 2^261, the domain's inverse table); value / n per input;
+ *     one gate index per input -> the coefficients (n)
+ *   5 pk_coset_combine: blocks x n coefficients; the blocks^2 matrix entries (times 2^5, row
+ *     major); blocks -> blocks x n
+ *   6 pk_eval: up to 28 polynomials; one point each; - -> one value each
+ *   7 pk_lincomb: up to 24 terms; one scalar each; len_out -> len_out
+ *   8 pk_scale_powers: c; x; shift -> c_j x^(j + shift)
+ *   9 pk_ruffini: c (len); z (not 0); - -> the len - 1 coefficients of (c(X) - c(z)) / (X - z)
+ * PLK_E_ARG: an unknown stage, a NULL array of non-zero length, lengths that do not fit together,
+ * out_cap too small, and whatever the launcher itself refuses. A zero-length problem is PLK_OK and
+ * writes nothing. */
+int plk_debug_prover_stage(plk_ctx* ctx, int stage, const uint64_t* const* in, const size_t* in_len,
+                           size_t n_in, const plk_fr* scalars, size_t n_scalars,
+                           const uint64_t* params, size_t n_params, uint64_t* out, size_t out_cap);
 /* The device-mode fold weights (plk_verifier_set_replay) from given entropy and u challenges
  * (Montgomery form): out[j] = rho_j, j < count. ctx = NULL: the host mirror, no GPU; otherwise
  * the kernel the fold runs. PLK_E_ARG: a NULL argument, count = 0, a non-canonical u. */
