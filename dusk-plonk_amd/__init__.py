@@ -7,12 +7,13 @@ in include/plk.h. See DESIGN.md.
 from .plonk import (  # noqa: F401
     ABI_SYMBOLS, Coefficients, Commitment, Context, Fft, OpeningKey, PLK_E_ARG, PLK_E_DEGREE,
     PLK_E_DEVICE, PLK_E_NODEV, PLK_E_OOM, PLK_OK, PlonkError, PlonkParams, PointsValue, build_info, check_build,
-    debug_pairing, device_count, g1_sum, msm_points, msm_points_ranges, msm_sharded,
+    debug_pairing, device_count, g1_decompress, g1_subgroup_check, g1_sum, ingest_last_ms, msm_points, msm_points_ranges, msm_sharded,
 )
 
 __all__ = [
     "ABI_SYMBOLS", "Coefficients", "Commitment", "Context", "Fft", "OpeningKey", "PlonkError",
     "PlonkParams",
-    "PointsValue", "build_info", "check_build", "debug_pairing", "device_count", "g1_sum", "msm_points",
+    "PointsValue", "build_info", "check_build", "debug_pairing", "device_count", "g1_decompress",
+    "g1_subgroup_check", "g1_sum", "ingest_last_ms", "msm_points",
     "msm_points_ranges", "msm_sharded",
 ]

@@ -94,6 +94,7 @@ int plk_ctx_destroy(plk_ctx* ctx) {
     (void)stream_wait(ctx->stream);
     ctx->domains.clear();
     msm_var_ws_delete(ctx->var_ws);
+    ingest_ws_delete(ctx->ingest_ws);
     (void)hipStreamDestroy(ctx->stream);
   }
   delete ctx;

@@ -1,0 +1,625 @@
+// ingest.hip — the ingest stage in front of the batch verifier (include/plk.h "Compact proofs
+// and the ingest stage"): compact proof bytes in, decoded proofs and one status per proof out.
+//
+//  - The compact format: 11 commitments as zkcrypto's 48-byte compressed G1 (exactly what
+//    Transcript::g1_compress writes), then 16 scalars as 32 canonical little-endian bytes.
+//    ASSUMED, parity unpinned: the element crates are not vendored.
+//  - k_g1_decompress, one point per lane: parse, range-check x, y = (x^3 + 4)^((p+1)/4)
+//    (p = 3 mod 4), verify y^2 = x^3 + 4, pick the root by the sort bit.
+//  - k_g1_subgroup, one point per lane: P in G1  <=>  (beta x, y) == -[x0^2] P with
+//    x0 = 0xd201000000010000 (Scott, eprint 2021/1130 section 6; zkcrypto's is_torsion_free).
+//  - k_fr_decode, one scalar per lane: range check and Montgomery form.
+//
+// The math is PLK_HD code on the packed field of ff.hpp / g1.hpp, so the host decode
+// (plk_proof_decode_compact, the single-proof path) and the kernels run the same functions; the
+// tests hold both against a pure-Python reference. The packed form, not the redundant-limb one
+// (ffr.hpp): both kernels are one long dependent chain of products per lane with canonical
+// comparisons in between (y^2 == x^3 + 4, the group law's P == Q tests on adversarial low-order
+// inputs), which the packed field's always-canonical values give for free, and g1.hpp's group
+// law handles doubling and the identity explicitly.
+//
+// The square root's exponent is fixed: a sliding window of 3 bits over it with the odd powers
+// x, x^3, x^5, x^7 held in registers (48 VGPRs) costs 379 squarings and about 100 products. The
+// exponent's bits are wave-uniform, so the window logic is scalar control flow and the table is
+// selected with compile-time indices: no stack array, no LDS, no scratch.
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "internal.hpp"
+
+using namespace plk;
+
+namespace plk {
+namespace {
+
+constexpr size_t kG1Bytes = 48, kFrBytes = 32, kComms = 11, kEvals = 16, kFields = kComms + kEvals;
+static_assert(PLK_PROOF_COMPACT_BYTES == kComms * kG1Bytes + kEvals * kFrBytes, "layout");
+static_assert(sizeof(plk_proof) == kComms * sizeof(plk_g1) + kEvals * sizeof(plk_fr), "no padding");
+static_assert(sizeof(plk_g1) == 104 && sizeof(plk_fr) == 32, "ABI");
+
+// ---- shared math (host and device) ----------------------------------------------------
+
+// word i (little-endian) of (p + 1) / 4: 379 bits, Hamming weight 229
+PLK_HD uint32_t sqrt_exp_word(int i) {
+  switch (i) {
+    case 0: return 0xffffeaabu;
+    case 1: return 0xee7fbfffu;
+    case 2: return 0xac54ffffu;
+    case 3: return 0x07aaffffu;
+    case 4: return 0x3dac3d89u;
+    case 5: return 0xd9cc34a8u;
+    case 6: return 0x3ce144afu;
+    case 7: return 0xd91dd2e1u;
+    case 8: return 0x90d2eb35u;
+    case 9: return 0x92c6e9edu;
+    case 10: return 0x8e5ff9a6u;
+    default: return 0x0680447au;
+  }
+}
+constexpr int kSqrtExpBits = 379;
+PLK_HD uint32_t sqrt_exp_bit(int i) { return (sqrt_exp_word(i >> 5) >> (i & 31)) & 1u; }
+
+PLK_HD Fp fp_const(const uint32_t (&w)[12]) {
+  Fp r;
+#pragma unroll
+  for (int i = 0; i < 12; ++i) r.v[i] = w[i];
+  return r;
+}
+// 4 and beta in Montgomery form; beta = 0x5f19672f...fffefffe, the cube root of unity with
+// (beta x, y) = [-x0^2] (x, y) on G1
+PLK_HD Fp fp_four() {
+  const uint32_t w[12] = {0x000cfff3u, 0xaa270000u, 0xfc34000au, 0x53cc0032u, 0x6b0a807fu, 0x478fe97au,
+                          0xe6ba24d7u, 0xb1d37ebeu, 0xbf78ab2fu, 0x8ec9733bu, 0x3d83de7eu, 0x09d64551u};
+  return fp_const(w);
+}
+PLK_HD Fp fp_beta() {
+  const uint32_t w[12] = {0x798a64e8u, 0x30f1361bu, 0x7ece5a2au, 0xf3b8ddabu, 0xc61577f7u, 0x16a8ca3au,
+                          0x74fd029bu, 0xc26a2ff8u, 0x60701c6eu, 0x3636b766u, 0x241b6160u, 0x051ba4abu};
+  return fp_const(w);
+}
+
+// a < modulus, for a value in plain 32-bit words
+template <class C>
+PLK_HD bool fe_canonical(const Fe<C>& a) {
+  uint32_t borrow = 0;
+#pragma unroll
+  for (int i = 0; i < C::N; ++i) {
+    const uint64_t t = (uint64_t)a.v[i] - C::P[i] - borrow;
+    borrow = (uint32_t)(t >> 63);
+  }
+  return borrow != 0;
+}
+
+// a > b as integers
+PLK_HD bool fp_gt(const Fp& a, const Fp& b) {
+  uint32_t borrow = 0;
+#pragma unroll
+  for (int i = 0; i < 12; ++i) {
+    const uint64_t t = (uint64_t)b.v[i] - a.v[i] - borrow;
+    borrow = (uint32_t)(t >> 63);
+  }
+  return borrow != 0;  // b - a < 0
+}
+
+// one of the four odd powers by a wave-uniform index (compile-time indices into t)
+PLK_HD Fp fp_sel4(const Fp (&t)[4], uint32_t k) {
+  Fp r = t[0];
+#pragma unroll
+  for (int j = 1; j < 4; ++j) {
+#pragma unroll
+    for (int i = 0; i < 12; ++i) r.v[i] = k == (uint32_t)j ? t[j].v[i] : r.v[i];
+  }
+  return r;
+}
+
+// a^((p+1)/4): the square root of a when a is a square (the caller verifies). Sliding window of
+// up to 3 bits, MSB first, over the fixed exponent.
+PLK_HD Fp fp_sqrt_candidate(const Fp& a) {
+  Fp t[4];
+  const Fp a2 = fe_sqr(a);
+  t[0] = a;
+  t[1] = fe_mul(t[0], a2);
+  t[2] = fe_mul(t[1], a2);
+  t[3] = fe_mul(t[2], a2);
+  Fp r = a;
+  bool started = false;
+  int i = kSqrtExpBits - 1;
+  while (i >= 0) {
+    if (!sqrt_exp_bit(i)) {  // the top bit is set, so r has started here
+      r = fe_sqr(r);
+      --i;
+      continue;
+    }
+    int len = i >= 2 ? 3 : i + 1;
+    while (!sqrt_exp_bit(i - len + 1)) --len;  // the window ends on a set bit
+    uint32_t val = 0;
+    for (int k = 0; k < len; ++k) val = (val << 1) | sqrt_exp_bit(i - k);
+    const Fp m = fp_sel4(t, val >> 1);
+    if (started) {
+      for (int k = 0; k < len; ++k) r = fe_sqr(r);
+      r = fe_mul(r, m);
+    } else {
+      r = m;
+      started = true;
+    }
+    i -= len;
+  }
+  return r;
+}
+
+// 48 compressed bytes as the 12 words read little-endian from memory -> Montgomery (x, y) or
+// the identity. Returns a PLK_INGEST_* code; x, y are zero unless it is OK and finite.
+PLK_HD uint8_t g1_decompress_words(const uint32_t (&w)[12], Fp& x, Fp& y, bool& inf) {
+  x = fe_zero<FpCfg>();
+  y = fe_zero<FpCfg>();
+  inf = false;
+  const uint32_t b0 = w[0] & 0xffu;
+  if (!(b0 & 0x80u)) return PLK_INGEST_ENCODING;
+  if (b0 & 0x40u) {  // infinity: 0xc0 and 47 zero bytes, nothing else
+    uint32_t rest = w[0] ^ 0xc0u;
+#pragma unroll
+    for (int i = 1; i < 12; ++i) rest |= w[i];
+    if (rest) return PLK_INGEST_ENCODING;
+    inf = true;
+    return PLK_INGEST_OK;
+  }
+  const bool sort = (b0 & 0x20u) != 0;
+  Fp xc;  // x is big-endian over the 48 bytes: word i of x is the byte-swapped word 11 - i
+#pragma unroll
+  for (int i = 0; i < 12; ++i) {
+    const uint32_t v = w[11 - i];
+    xc.v[i] = (v >> 24) | ((v >> 8) & 0xff00u) | ((v << 8) & 0xff0000u) | (v << 24);
+  }
+  xc.v[11] &= 0x1fffffffu;
+  if (!fe_canonical(xc)) return PLK_INGEST_RANGE;
+  const Fp xm = fe_to_mont(xc);
+  const Fp rhs = fe_add(fe_mul(fe_sqr(xm), xm), fp_four());
+  Fp ym = fp_sqrt_candidate(rhs);
+  if (!fe_eq(fe_sqr(ym), rhs)) return PLK_INGEST_OFF_CURVE;
+  // the sort bit: y is the larger of (y, p - y) as integers. y = 0 does not occur: the curve's
+  // order is odd, so it has no point of order 2.
+  const Fp yc = fe_from_mont(ym);
+  const Fp nyc = fe_neg(yc);
+  if (fp_gt(yc, nyc) != sort) ym = fe_neg(ym);
+  x = xm;
+  y = ym;
+  return PLK_INGEST_OK;
+}
+
+// acc = [x0] base for x0 = 0xd201000000010000, MSB first: 63 doublings and 5 additions; Add is
+// the complete addition of the base (g1.hpp handles P = +-Q and the identity explicitly)
+constexpr uint64_t kX0 = 0xd201000000010000ull;
+template <class Add>
+PLK_HD G1xyzz g1_mul_x0(G1xyzz acc, Add add_base) {
+  for (int b = 62; b >= 0; --b) {
+    acc = xyzz_dbl(acc);
+    if ((kX0 >> b) & 1ull) acc = add_base(acc);
+  }
+  return acc;
+}
+
+// (x, y): a finite point on the curve, Montgomery form. True iff it has order r.
+PLK_HD bool g1_in_subgroup(const Fp& x, const Fp& y) {
+  G1Affine p;
+  p.x = x;
+  p.y = y;
+  const G1xyzz q1 = g1_mul_x0(xyzz_from_affine(p), [&](const G1xyzz& a) { return xyzz_add_affine(a, x, y); });
+  const G1xyzz q2 = g1_mul_x0(q1, [&](const G1xyzz& a) { return xyzz_add(a, q1); });
+  if (xyzz_is_inf(q2)) return false;  // (beta x, y) is finite
+  // -q2 == (beta x, y):  X2 == beta x ZZ2  and  Y2 + y ZZZ2 == 0
+  const Fp bx = fe_mul(fp_beta(), x);
+  return fe_eq(q2.X, fe_mul(bx, q2.ZZ)) && fe_is_zero(fe_add(q2.Y, fe_mul(y, q2.ZZZ)));
+}
+
+// 32 little-endian bytes as 8 words -> Montgomery scalar
+PLK_HD uint8_t fr_decode_words(const uint32_t (&w)[8], Fr& out) {
+  Fr c;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) c.v[i] = w[i];
+  out = fe_zero<FrCfg>();
+  if (!fe_canonical(c)) return PLK_INGEST_RANGE;
+  out = fe_to_mont(c);
+  return PLK_INGEST_OK;
+}
+
+template <class C>
+PLK_HD Fe<C> fe_of_abi(const uint64_t* l) {
+  Fe<C> r;
+#pragma unroll
+  for (int i = 0; i < C::N / 2; ++i) {
+    r.v[2 * i] = (uint32_t)l[i];
+    r.v[2 * i + 1] = (uint32_t)(l[i] >> 32);
+  }
+  return r;
+}
+template <class C>
+PLK_HD void fe_to_abi(const Fe<C>& a, uint64_t* l) {
+#pragma unroll
+  for (int i = 0; i < C::N / 2; ++i) l[i] = (uint64_t)a.v[2 * i] | ((uint64_t)a.v[2 * i + 1] << 32);
+}
+
+PLK_HD bool g1_on_curve(const Fp& x, const Fp& y) {
+  return fe_eq(fe_sqr(y), fe_add(fe_mul(fe_sqr(x), x), fp_four()));
+}
+
+// ---- kernels --------------------------------------------------------------------------
+// Items are addressed in groups so that the same kernels serve a flat array of points (per = 1)
+// and the fields of an array of proofs (per = 11 points / 16 scalars per proof): item t is field
+// t % per of group t / per, its input at in + group * in_stride + field * item bytes, its output
+// at out + group * out_stride + field * item size, its status at status + group * st_stride +
+// field. All strides in bytes.
+struct Layout {
+  uint32_t per;
+  uint64_t in_stride, out_stride, st_stride;
+};
+
+constexpr int kBlock = 64;  // one wave: a small batch still spreads over the CUs
+
+__global__ void __launch_bounds__(kBlock) k_g1_decompress(const uint8_t* __restrict__ in, uint64_t n, Layout L,
+                                                          uint8_t* __restrict__ out,
+                                                          uint8_t* __restrict__ status) {
+  const uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (t >= n) return;
+  const uint64_t g = t / L.per, f = t % L.per;
+  const uint4* src = reinterpret_cast<const uint4*>(in + g * L.in_stride + f * kG1Bytes);  // 16-B aligned
+  uint32_t w[12];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const uint4 q = src[i];
+    w[4 * i] = q.x;
+    w[4 * i + 1] = q.y;
+    w[4 * i + 2] = q.z;
+    w[4 * i + 3] = q.w;
+  }
+  Fp x, y;
+  bool inf;
+  const uint8_t st = g1_decompress_words(w, x, y, inf);
+  uint64_t* dst = reinterpret_cast<uint64_t*>(out + g * L.out_stride + f * sizeof(plk_g1));
+  fe_to_abi(x, dst);
+  fe_to_abi(y, dst + 6);
+  dst[12] = inf ? 1 : 0;
+  status[g * L.st_stride + f] = st;
+}
+
+// points in ABI form (canonical, on the curve) with status 0: a non-member gets
+// PLK_INGEST_SUBGROUP; identities and items with a status stay as they are
+__global__ void __launch_bounds__(kBlock) k_g1_subgroup(const uint8_t* __restrict__ pts, uint64_t n, Layout L,
+                                                        uint8_t* __restrict__ status) {
+  const uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (t >= n) return;
+  const uint64_t g = t / L.per, f = t % L.per;
+  uint8_t* st = status + g * L.st_stride + f;
+  const uint64_t* src = reinterpret_cast<const uint64_t*>(pts + g * L.out_stride + f * sizeof(plk_g1));
+  if (*st != PLK_INGEST_OK || src[12] != 0) return;
+  const Fp x = fe_of_abi<FpCfg>(src), y = fe_of_abi<FpCfg>(src + 6);
+  if (!g1_in_subgroup(x, y)) *st = PLK_INGEST_SUBGROUP;
+}
+
+// ABI points from the caller: status 0xff for a non-canonical or off-curve finite point or an
+// infinity word other than 0 / 1 (plk_g1_subgroup_check_batch refuses the call), else 0
+constexpr uint8_t kBadPoint = 0xff;
+__global__ void __launch_bounds__(kBlock) k_g1_validate(const plk_g1* __restrict__ pts, uint64_t n,
+                                                        uint8_t* __restrict__ status) {
+  const uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (t >= n) return;
+  const uint64_t* src = reinterpret_cast<const uint64_t*>(pts + t);
+  uint8_t st = PLK_INGEST_OK;
+  if (src[12] > 1) {
+    st = kBadPoint;
+  } else if (src[12] == 0) {
+    const Fp x = fe_of_abi<FpCfg>(src), y = fe_of_abi<FpCfg>(src + 6);
+    if (!fe_canonical(x) || !fe_canonical(y) || !g1_on_curve(x, y)) st = kBadPoint;
+  }
+  status[t] = st;
+}
+
+__global__ void __launch_bounds__(kBlock) k_fr_decode(const uint8_t* __restrict__ in, uint64_t n, Layout L,
+                                                      uint8_t* __restrict__ out, uint8_t* __restrict__ status) {
+  const uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (t >= n) return;
+  const uint64_t g = t / L.per, f = t % L.per;
+  const uint4* src = reinterpret_cast<const uint4*>(in + g * L.in_stride + f * kFrBytes);  // 16-B aligned
+  uint32_t w[8];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const uint4 q = src[i];
+    w[4 * i] = q.x;
+    w[4 * i + 1] = q.y;
+    w[4 * i + 2] = q.z;
+    w[4 * i + 3] = q.w;
+  }
+  Fr s;
+  const uint8_t st = fr_decode_words(w, s);
+  fe_to_abi(s, reinterpret_cast<uint64_t*>(out + g * L.out_stride + f * sizeof(plk_fr)));
+  status[g * L.st_stride + f] = st;
+}
+
+inline uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + kBlock - 1) / kBlock); }
+
+// ---- host codec -----------------------------------------------------------------------
+// field order of proof.rs:39-66 / plk_proof: the 11 commitments, then the 16 evaluations
+const plk_g1* comm(const plk_proof* p, size_t i) { return &p->a_comm + i; }
+plk_g1* comm(plk_proof* p, size_t i) { return &p->a_comm + i; }
+const plk_fr* eval(const plk_proof* p, size_t i) { return &p->a_eval + i; }
+plk_fr* eval(plk_proof* p, size_t i) { return &p->a_eval + i; }
+
+template <int N>
+void words_of_bytes(const uint8_t* b, uint32_t (&w)[N]) {
+  for (int i = 0; i < N; ++i)
+    w[i] = (uint32_t)b[4 * i] | ((uint32_t)b[4 * i + 1] << 8) | ((uint32_t)b[4 * i + 2] << 16) |
+           ((uint32_t)b[4 * i + 3] << 24);
+}
+
+// the 48 bytes Transcript::g1_compress writes, for a canonical point
+bool g1_compress_host(const plk_g1& p, uint8_t* out) {
+  std::memset(out, 0, kG1Bytes);
+  if (p.infinity > 1) return false;
+  if (p.infinity) {
+    out[0] = 0xc0;
+    return true;
+  }
+  Fp x = fe_of_abi<FpCfg>(p.x), y = fe_of_abi<FpCfg>(p.y);
+  if (!fe_canonical(x) || !fe_canonical(y)) return false;
+  x = fe_from_mont(x);
+  y = fe_from_mont(y);
+  for (int i = 0; i < 12; ++i)
+    for (int k = 0; k < 4; ++k) out[47 - (4 * i + k)] = (uint8_t)(x.v[i] >> (8 * k));
+  out[0] |= 0x80 | (fp_gt(y, fe_neg(y)) ? 0x20 : 0);
+  return true;
+}
+
+// one compressed point on the host: the kernels' math. Returns a PLK_INGEST_* code.
+uint8_t g1_decompress_host(const uint8_t* in, int check_subgroup, plk_g1* out) {
+  uint32_t w[12];
+  words_of_bytes(in, w);
+  Fp x, y;
+  bool inf;
+  uint8_t st = g1_decompress_words(w, x, y, inf);
+  if (st == PLK_INGEST_OK && !inf && check_subgroup && !g1_in_subgroup(x, y)) st = PLK_INGEST_SUBGROUP;
+  std::memset(out, 0, sizeof *out);
+  if (st != PLK_INGEST_OK) return st;
+  fe_to_abi(x, out->x);
+  fe_to_abi(y, out->y);
+  out->infinity = inf ? 1 : 0;
+  return st;
+}
+
+}  // namespace
+
+struct IngestWs {
+  DevBuf d_in, d_out, d_status;
+  hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+  float decompress_ms = 0.f, subgroup_ms = 0.f;
+  ~IngestWs() {
+    for (hipEvent_t ev : e)
+      if (ev) (void)hipEventDestroy(ev);
+  }
+};
+void ingest_ws_delete(IngestWs* w) { delete w; }
+
+namespace {
+
+int ingest_ws(plk_ctx* ctx, IngestWs** out) {
+  if (!ctx->ingest_ws) ctx->ingest_ws = new IngestWs();
+  IngestWs& w = *ctx->ingest_ws;
+  for (hipEvent_t& ev : w.e)
+    if (!ev) PLK_HIP_TRY(hipEventCreate(&ev));
+  *out = &w;
+  return PLK_OK;
+}
+
+// the timed kernels of one batched call on the context's stream: decompression of n_pts points
+// (skipped when `decompress` is false: the points are already in d_out) and the subgroup test
+int run_point_kernels(plk_ctx* ctx, IngestWs& w, uint64_t n_pts, const Layout& L, bool decompress,
+                      bool subgroup) {
+  hipStream_t s = ctx->stream;
+  if (decompress) {
+    PLK_HIP_TRY(hipEventRecord(w.e[0], s));
+    hipLaunchKernelGGL(k_g1_decompress, dim3(blocks_for(n_pts)), dim3(kBlock), 0, s,
+                       (const uint8_t*)w.d_in.as<uint8_t>(), n_pts, L, w.d_out.as<uint8_t>(),
+                       w.d_status.as<uint8_t>());
+    PLK_HIP_TRY(hipEventRecord(w.e[1], s));
+  }
+  if (subgroup) {
+    PLK_HIP_TRY(hipEventRecord(w.e[2], s));
+    hipLaunchKernelGGL(k_g1_subgroup, dim3(blocks_for(n_pts)), dim3(kBlock), 0, s,
+                       (const uint8_t*)w.d_out.as<uint8_t>(), n_pts, L, w.d_status.as<uint8_t>());
+    PLK_HIP_TRY(hipEventRecord(w.e[3], s));
+  }
+  PLK_HIP_TRY(hipGetLastError());
+  return PLK_OK;
+}
+
+void read_timings(IngestWs& w, bool decompress, bool subgroup) {
+  w.decompress_ms = w.subgroup_ms = 0.f;
+  if (decompress) (void)hipEventElapsedTime(&w.decompress_ms, w.e[0], w.e[1]);
+  if (subgroup) (void)hipEventElapsedTime(&w.subgroup_ms, w.e[2], w.e[3]);
+}
+
+}  // namespace
+}  // namespace plk
+
+#define PLK_I_BEGIN try {
+#define PLK_I_END                 \
+  }                               \
+  catch (const std::bad_alloc&) { \
+    return PLK_E_OOM;             \
+  }                               \
+  catch (...) {                   \
+    return PLK_E_DEVICE;          \
+  }
+
+extern "C" {
+
+int plk_proof_encode_compact(const plk_proof* proof, uint8_t* out, size_t cap, size_t* len) {
+  if (!proof) return PLK_E_ARG;
+  if (len) *len = PLK_PROOF_COMPACT_BYTES;
+  if (!out) return PLK_OK;  // size query
+  if (cap < PLK_PROOF_COMPACT_BYTES) return PLK_E_ARG;
+  uint8_t buf[PLK_PROOF_COMPACT_BYTES];
+  uint8_t* o = buf;
+  for (size_t i = 0; i < kComms; ++i, o += kG1Bytes)
+    if (!g1_compress_host(*comm(proof, i), o)) return PLK_E_ARG;
+  for (size_t i = 0; i < kEvals; ++i, o += kFrBytes) {
+    const Fr m = fe_of_abi<FrCfg>(eval(proof, i)->l);
+    if (!fe_canonical(m)) return PLK_E_ARG;
+    const Fr c = fe_from_mont(m);
+    for (int k = 0; k < 8; ++k)
+      for (int b = 0; b < 4; ++b) o[4 * k + b] = (uint8_t)(c.v[k] >> (8 * b));
+  }
+  std::memcpy(out, buf, sizeof buf);
+  return PLK_OK;
+}
+
+int plk_proof_decode_compact(const uint8_t* in, size_t len, plk_proof* out, int check_subgroup) {
+  if (!in || !out || len != PLK_PROOF_COMPACT_BYTES) return PLK_E_ARG;
+  plk_proof p;
+  std::memset(&p, 0, sizeof p);
+  const uint8_t* q = in;
+  for (size_t i = 0; i < kComms; ++i, q += kG1Bytes)
+    if (g1_decompress_host(q, check_subgroup, comm(&p, i)) != PLK_INGEST_OK) return PLK_E_ARG;
+  for (size_t i = 0; i < kEvals; ++i, q += kFrBytes) {
+    uint32_t w[8];
+    words_of_bytes(q, w);
+    Fr s;
+    if (fr_decode_words(w, s) != PLK_INGEST_OK) return PLK_E_ARG;
+    fe_to_abi(s, eval(&p, i)->l);
+  }
+  *out = p;
+  return PLK_OK;
+}
+
+int plk_g1_decompress_batch(plk_ctx* ctx, const uint8_t* in48, size_t n, int check_subgroup, plk_g1* out,
+                            uint8_t* status) {
+  PLK_I_BEGIN
+  if (!ctx || !in48 || !out || !status || n == 0 || n > (1u << 28)) return PLK_E_ARG;
+  DeviceGuard g(ctx->device);
+  IngestWs* w;
+  int st;
+  if ((st = ingest_ws(ctx, &w))) return st;
+  if ((st = w->d_in.alloc(n * kG1Bytes))) return st;
+  if ((st = w->d_out.alloc(n * sizeof(plk_g1)))) return st;
+  if ((st = w->d_status.alloc(n))) return st;
+  hipStream_t s = ctx->stream;
+  PLK_HIP_TRY(hipMemcpyAsync(w->d_in.ptr, in48, n * kG1Bytes, hipMemcpyHostToDevice, s));
+  const Layout L = {1, kG1Bytes, sizeof(plk_g1), 1};
+  if ((st = run_point_kernels(ctx, *w, n, L, true, check_subgroup != 0))) return st;
+  std::vector<plk_g1> pts(n);
+  std::vector<uint8_t> sts(n);
+  PLK_HIP_TRY(hipMemcpyAsync(pts.data(), w->d_out.ptr, n * sizeof(plk_g1), hipMemcpyDeviceToHost, s));
+  PLK_HIP_TRY(hipMemcpyAsync(sts.data(), w->d_status.ptr, n, hipMemcpyDeviceToHost, s));
+  PLK_HIP_TRY(stream_wait(s));
+  read_timings(*w, true, check_subgroup != 0);
+  for (size_t i = 0; i < n; ++i)
+    if (sts[i] != PLK_INGEST_OK) std::memset(&pts[i], 0, sizeof(plk_g1));
+  std::memcpy(out, pts.data(), n * sizeof(plk_g1));
+  std::memcpy(status, sts.data(), n);
+  return PLK_OK;
+  PLK_I_END
+}
+
+int plk_g1_subgroup_check_batch(plk_ctx* ctx, const plk_g1* points, size_t n, uint8_t* ok) {
+  PLK_I_BEGIN
+  if (!ctx || !points || !ok || n == 0 || n > (1u << 28)) return PLK_E_ARG;
+  DeviceGuard g(ctx->device);
+  IngestWs* w;
+  int st;
+  if ((st = ingest_ws(ctx, &w))) return st;
+  if ((st = w->d_out.alloc(n * sizeof(plk_g1)))) return st;
+  if ((st = w->d_status.alloc(n))) return st;
+  hipStream_t s = ctx->stream;
+  PLK_HIP_TRY(hipMemcpyAsync(w->d_out.ptr, points, n * sizeof(plk_g1), hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(k_g1_validate, dim3(blocks_for(n)), dim3(kBlock), 0, s,
+                     (const plk_g1*)w->d_out.as<plk_g1>(), (uint64_t)n, w->d_status.as<uint8_t>());
+  const Layout L = {1, kG1Bytes, sizeof(plk_g1), 1};
+  if ((st = run_point_kernels(ctx, *w, n, L, false, true))) return st;
+  std::vector<uint8_t> sts(n);
+  PLK_HIP_TRY(hipMemcpyAsync(sts.data(), w->d_status.ptr, n, hipMemcpyDeviceToHost, s));
+  PLK_HIP_TRY(stream_wait(s));
+  read_timings(*w, false, true);
+  for (size_t i = 0; i < n; ++i)
+    if (sts[i] == kBadPoint) return PLK_E_ARG;
+  for (size_t i = 0; i < n; ++i) ok[i] = sts[i] == PLK_INGEST_OK ? 1 : 0;
+  return PLK_OK;
+  PLK_I_END
+}
+
+int plk_proofs_ingest(plk_ctx* ctx, const uint8_t* in, size_t count, int check_subgroup, plk_proof* out,
+                      uint8_t* status) {
+  PLK_I_BEGIN
+  if (!ctx || !in || !out || !status || count == 0 || count > (1u << 24)) return PLK_E_ARG;
+  DeviceGuard g(ctx->device);
+  IngestWs* w;
+  int st;
+  if ((st = ingest_ws(ctx, &w))) return st;
+  if ((st = w->d_in.alloc(count * PLK_PROOF_COMPACT_BYTES))) return st;
+  if ((st = w->d_out.alloc(count * sizeof(plk_proof)))) return st;
+  if ((st = w->d_status.alloc(count * kFields))) return st;
+  hipStream_t s = ctx->stream;
+  PLK_HIP_TRY(hipMemcpyAsync(w->d_in.ptr, in, count * PLK_PROOF_COMPACT_BYTES, hipMemcpyHostToDevice, s));
+  // the points of proof j: fields 0..10 of group j; its scalars: the 16 fields after them
+  const Layout LP = {(uint32_t)kComms, PLK_PROOF_COMPACT_BYTES, sizeof(plk_proof), kFields};
+  if ((st = run_point_kernels(ctx, *w, count * kComms, LP, true, check_subgroup != 0))) return st;
+  const Layout LS = {(uint32_t)kEvals, PLK_PROOF_COMPACT_BYTES, sizeof(plk_proof), kFields};
+  hipLaunchKernelGGL(k_fr_decode, dim3(blocks_for(count * kEvals)), dim3(kBlock), 0, s,
+                     (const uint8_t*)w->d_in.as<uint8_t>() + kComms * kG1Bytes, (uint64_t)(count * kEvals), LS,
+                     w->d_out.as<uint8_t>() + kComms * sizeof(plk_g1), w->d_status.as<uint8_t>() + kComms);
+  PLK_HIP_TRY(hipGetLastError());
+  std::vector<plk_proof> res(count);
+  std::vector<uint8_t> sts(count * kFields);
+  PLK_HIP_TRY(hipMemcpyAsync(res.data(), w->d_out.ptr, count * sizeof(plk_proof), hipMemcpyDeviceToHost, s));
+  PLK_HIP_TRY(hipMemcpyAsync(sts.data(), w->d_status.ptr, count * kFields, hipMemcpyDeviceToHost, s));
+  PLK_HIP_TRY(stream_wait(s));
+  read_timings(*w, true, check_subgroup != 0);
+  for (size_t j = 0; j < count; ++j) {
+    uint8_t code = PLK_INGEST_OK;  // the first failing field's code
+    for (size_t f = 0; f < kFields && code == PLK_INGEST_OK; ++f) code = sts[j * kFields + f];
+    if (code != PLK_INGEST_OK) std::memset(&res[j], 0, sizeof(plk_proof));
+    status[j] = code;
+  }
+  std::memcpy(out, res.data(), count * sizeof(plk_proof));
+  return PLK_OK;
+  PLK_I_END
+}
+
+int plk_ingest_last_ms(plk_ctx* ctx, float* decompress_ms, float* subgroup_ms) {
+  if (!ctx) return PLK_E_ARG;
+  const IngestWs* w = ctx->ingest_ws;
+  if (decompress_ms) *decompress_ms = w ? w->decompress_ms : 0.f;
+  if (subgroup_ms) *subgroup_ms = w ? w->subgroup_ms : 0.f;
+  return PLK_OK;
+}
+
+int plk_verifier_verify_each_bytes(plk_ctx* ctx, plk_verifier* v, plk_opening_key* key, const uint8_t* in,
+                                   const plk_fr* public_inputs, size_t count, int check_subgroup,
+                                   uint8_t* verdict) {
+  PLK_I_BEGIN
+  if (!ctx || !v || !key || !in || !verdict || count == 0 || count > (1u << 24)) return PLK_E_ARG;
+  const size_t npi = verifier_pi_count(v);
+  if (npi && !public_inputs) return PLK_E_ARG;
+  std::vector<plk_proof> proofs(count);
+  std::vector<uint8_t> status(count);
+  int st;
+  if ((st = plk_proofs_ingest(ctx, in, count, check_subgroup, proofs.data(), status.data()))) return st;
+  // compact the accepted proofs and their public inputs (through host memory)
+  std::vector<size_t> where;
+  for (size_t j = 0; j < count; ++j)
+    if (status[j] == PLK_INGEST_OK) where.push_back(j);
+  std::vector<plk_fr> pis(where.size() * npi);
+  for (size_t k = 0; k < where.size(); ++k) {
+    if (where[k] != k) proofs[k] = proofs[where[k]];
+    if (npi) std::memcpy(&pis[k * npi], public_inputs + where[k] * npi, npi * sizeof(plk_fr));
+  }
+  std::vector<uint8_t> ok(where.size());
+  if (!where.empty() &&
+      (st = plk_verifier_verify_each(ctx, v, key, proofs.data(), npi ? pis.data() : nullptr, where.size(),
+                                     ok.data())))
+    return st;
+  for (size_t j = 0; j < count; ++j) verdict[j] = (uint8_t)(0x10 | status[j]);
+  for (size_t k = 0; k < where.size(); ++k) verdict[where[k]] = ok[k];
+  return PLK_OK;
+  PLK_I_END
+}
+
+}  // extern "C"

@@ -139,6 +139,7 @@ struct plk_srs {
 
 namespace plk {
 struct VarMsmWs;
+struct IngestWs;
 }
 
 struct plk_ctx {
@@ -148,6 +149,8 @@ struct plk_ctx {
   std::mutex mu;
   // workspace of the variable-base MSM (msm_var.hip), made on first use, freed with the context
   plk::VarMsmWs* var_ws = nullptr;
+  // buffers, events and timings of the ingest stage (ingest.hip), made on first use
+  plk::IngestWs* ingest_ws = nullptr;
 };
 
 namespace plk {
@@ -277,6 +280,9 @@ int msm_var_run(plk_ctx* ctx, const plk_g1* d_points, const Fr* d_scalars, size_
                 const size_t* starts, const size_t* lens, size_t count, plk_g1* outs,
                 hipStream_t stream);
 void msm_var_ws_delete(VarMsmWs* w);
+void ingest_ws_delete(IngestWs* w);
+// the number of public inputs a verifier was created with (verifier.hip)
+size_t verifier_pi_count(const plk_verifier* v);
 // The batched pairing check (pairing.hip) on device buffers, stream-ordered on the context's
 // stream: d_ok[j] = 1 iff e(d_pairs[j].c, H) == e(d_pairs[j].w, beta_h). The points must be
 // canonical and on the curve (the caller's check). pairing_last_ms: the kernel's time once the

@@ -407,6 +407,8 @@ struct plk_verifier {
 };
 
 namespace plk {
+size_t verifier_pi_count(const plk_verifier* v) { return v->pi_idx.size(); }
+
 namespace {
 
 // The transcript replay of Proof::verify for one proof: the 11 challenges and what the scalar

@@ -71,7 +71,15 @@ ABI_SYMBOLS = (
     "plk_opening_key_destroy", "plk_pairing_check", "plk_pairing_check_batch",
     "plk_opening_key_last_pairing_ms", "plk_debug_pairing", "plk_verifier_pairs",
     "plk_verifier_verify", "plk_verifier_verify_each", "plk_verifier_last_each_stats",
+    # compact proofs and the ingest stage (g1_decompress / g1_subgroup_check here, the rest in
+    # prover.py)
+    "plk_proof_encode_compact", "plk_proof_decode_compact", "plk_g1_decompress_batch",
+    "plk_g1_subgroup_check_batch", "plk_proofs_ingest", "plk_ingest_last_ms",
+    "plk_verifier_verify_each_bytes",
 )
+
+# per-item status of the ingest calls (include/plk.h PLK_INGEST_*)
+INGEST_OK, INGEST_ENCODING, INGEST_RANGE, INGEST_OFF_CURVE, INGEST_SUBGROUP = range(5)
 
 
 class PlonkError(RuntimeError):
@@ -153,6 +161,9 @@ def _lib():
             "plk_pairing_check_batch": (i32, [vp, vp, vp, sz, vp]),
             "plk_opening_key_last_pairing_ms": (i32, [vp, C.POINTER(C.c_float)]),
             "plk_debug_pairing": (i32, [vp, vp, vp, sz, vp]),
+            "plk_g1_decompress_batch": (i32, [vp, vp, sz, i32, vp, vp]),
+            "plk_g1_subgroup_check_batch": (i32, [vp, vp, sz, vp]),
+            "plk_ingest_last_ms": (i32, [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
         }
         for name, (res, args) in sig.items():
             f = getattr(lib, name)
@@ -541,6 +552,41 @@ def msm_points(points, scalars, ctx: "Context | None" = None) -> Commitment:
     _check(_lib().plk_msm_points(ctx.handle, _ptr(pts), _ptr(vals), pts.shape[0], _ptr(out)),
            "msm_points")
     return Commitment(out)
+
+
+def g1_decompress(blob, subgroup: bool = True, ctx: "Context | None" = None):
+    """n zkcrypto-compressed G1 points (48 n bytes) -> (points uint64[n, 13], status uint8[n]),
+    decoded on the GPU (plk_g1_decompress_batch). status[i] is an INGEST_* code; a rejected
+    point's row is zero. subgroup=False skips the membership test."""
+    ctx = ctx or Context.default()
+    raw = np.frombuffer(bytes(blob), dtype=np.uint8)
+    if raw.size == 0 or raw.size % 48:
+        raise PlonkError(PLK_E_ARG, "g1_decompress: a positive multiple of 48 bytes")
+    n = raw.size // 48
+    pts = np.zeros((n, 13), dtype=np.uint64)
+    status = np.zeros(n, dtype=np.uint8)
+    _check(_lib().plk_g1_decompress_batch(ctx.handle, _ptr(raw), n, int(bool(subgroup)), _ptr(pts),
+                                          _ptr(status)), "g1_decompress")
+    return pts, status
+
+
+def g1_subgroup_check(points, ctx: "Context | None" = None) -> np.ndarray:
+    """bool[n]: whether each ABI point uint64[n, 13] has order r (the identity does), on the GPU
+    (plk_g1_subgroup_check_batch). PlonkError(PLK_E_ARG) for a non-canonical or off-curve point."""
+    ctx = ctx or Context.default()
+    pts = np.ascontiguousarray(np.asarray(points, dtype=np.uint64).reshape(-1, 13))
+    ok = np.zeros(max(1, pts.shape[0]), dtype=np.uint8)
+    _check(_lib().plk_g1_subgroup_check_batch(ctx.handle, _ptr(pts), pts.shape[0], _ptr(ok)),
+           "g1_subgroup_check")
+    return ok[:pts.shape[0]].astype(bool)
+
+
+def ingest_last_ms(ctx: "Context | None" = None):
+    """(decompress kernel ms, subgroup kernel ms) of the most recent ingest call on the context."""
+    ctx = ctx or Context.default()
+    a, b = C.c_float(), C.c_float()
+    _check(_lib().plk_ingest_last_ms(ctx.handle, C.byref(a), C.byref(b)), "plk_ingest_last_ms")
+    return a.value, b.value
 
 
 class PlonkParams:

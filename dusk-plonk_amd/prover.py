@@ -54,6 +54,7 @@ class PlkProof(C.Structure):
 # plk_allgather_fn (include/plk.h): (user, send, bytes, recv) -> 0 on success
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 PROOF_SCALE_BYTES = 11 * 97 + 16 * 32  # PLK_PROOF_SCALE_BYTES
+PROOF_COMPACT_BYTES = 11 * 48 + 16 * 32  # PLK_PROOF_COMPACT_BYTES
 
 
 def _bind():
@@ -103,6 +104,10 @@ def _bind():
         "plk_verifier_verify": [vp, vp, vp, vp, vp, sz, vp, C.POINTER(i32)],
         "plk_verifier_verify_each": [vp, vp, vp, vp, vp, sz, vp],
         "plk_verifier_last_each_stats": [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)],
+        "plk_proof_encode_compact": [vp, vp, sz, C.POINTER(sz)],
+        "plk_proof_decode_compact": [vp, sz, vp, i32],
+        "plk_proofs_ingest": [vp, vp, sz, i32, vp, vp],
+        "plk_verifier_verify_each_bytes": [vp, vp, vp, vp, vp, sz, i32, vp],
     }
     for name, args in sig.items():
         f = getattr(lib, name)
@@ -551,6 +556,26 @@ class Proof:
         _check(_bind().plk_proof_decode(buf, len(data), C.byref(raw)), "Proof::decode")
         return Proof(raw)
 
+    def to_compact(self) -> bytes:
+        """The compact form (plk_proof_encode_compact): 11 zkcrypto-compressed commitments of 48
+        bytes, then the 16 evaluations as 32 canonical little-endian bytes; 1 040 bytes."""
+        out = (C.c_uint8 * PROOF_COMPACT_BYTES)()
+        n = C.c_size_t()
+        _check(_bind().plk_proof_encode_compact(C.byref(self.raw), out, PROOF_COMPACT_BYTES,
+                                                C.byref(n)), "Proof::to_compact")
+        return bytes(out[: n.value])
+
+    @staticmethod
+    def from_compact(data: bytes, subgroup: bool = True) -> "Proof":
+        """The host decode of :meth:`to_compact` output (plk_proof_decode_compact), strict:
+        PlonkError(PLK_E_ARG) on a wrong length, malformed flags, x >= p, a point off the curve, a
+        scalar >= r and, with subgroup=True, a point outside G1."""
+        raw = PlkProof()
+        buf = (C.c_uint8 * len(data)).from_buffer_copy(data) if data else None
+        _check(_bind().plk_proof_decode_compact(buf, len(data), C.byref(raw), int(bool(subgroup))),
+               "Proof::from_compact")
+        return Proof(raw)
+
     @staticmethod
     def from_words(comms, evals) -> "Proof":
         """A Proof from uint64 arrays: comms (11, 13) ABI points, evals (16, 4) Montgomery."""
@@ -565,6 +590,25 @@ class Proof:
 
     def __eq__(self, other) -> bool:
         return isinstance(other, Proof) and self.raw_bytes() == other.raw_bytes()
+
+
+def ingest_proofs(blob, subgroup: bool = True, ctx=None):
+    """`count` compact proofs (count * 1 040 bytes) decoded and screened on the GPU
+    (plk_proofs_ingest): (list of Proof, None where rejected; status uint8[count] of INGEST_*
+    codes)."""
+    from .plonk import Context
+    ctx = ctx or Context.default()
+    data = bytes(blob)
+    if not data or len(data) % PROOF_COMPACT_BYTES:
+        raise PlonkError(2, "ingest_proofs: a positive multiple of 1040 bytes")
+    count = len(data) // PROOF_COMPACT_BYTES
+    raw = (PlkProof * count)()
+    status = np.zeros(count, dtype=np.uint8)
+    _check(_bind().plk_proofs_ingest(ctx.handle, data, count, int(bool(subgroup)), raw,
+                                     _ptr(status)), "ingest_proofs")
+    proofs = [Proof(PlkProof.from_buffer_copy(raw[j])) if status[j] == 0 else None
+              for j in range(count)]
+    return proofs, status
 
 
 class VerifierData:
@@ -733,6 +777,23 @@ class Verifier:
         _check(_bind().plk_verifier_verify_each(ctx.handle, self._h, opening_key._h, raw, pis, count,
                                                 _ptr(ok)), "Verifier::verify_each")
         return ok[:count].astype(bool)
+
+    def verify_each_bytes(self, blob, public_inputs, opening_key, subgroup: bool = True) -> np.ndarray:
+        """One verdict per compact proof of `blob`, uint8[n] (plk_verifier_verify_each_bytes):
+        1 valid, 0 well-formed but the pairing check fails, 0x10 | INGEST_* code when ingest
+        rejected the proof. A malformed proof never fails the call."""
+        from .plonk import Context
+        data = bytes(blob)
+        if not data or len(data) % PROOF_COMPACT_BYTES:
+            raise PlonkError(2, "Verifier.verify_each_bytes: a positive multiple of 1040 bytes")
+        count = len(data) // PROOF_COMPACT_BYTES
+        pis = self._pis(list(public_inputs), count)
+        verdict = np.zeros(count, dtype=np.uint8)
+        ctx = self.ctx or Context.default()
+        _check(_bind().plk_verifier_verify_each_bytes(ctx.handle, self._h, opening_key._h, data, pis,
+                                                      count, int(bool(subgroup)), _ptr(verdict)),
+               "Verifier::verify_each_bytes")
+        return verdict
 
     def last_each_stats(self):
         """(pairs kernel ms, pairing kernel ms) of the most recent pairs / verify_each."""

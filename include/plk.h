@@ -199,8 +199,9 @@ int plk_msm_sharded(plk_srs* const* per_gpu, int n_gpu, const plk_fr* scalars, s
  * affine out. Variable-base Pippenger (csrc/msm_var.hip): no precomputed window table, the
  * points are used once. Host buffers; n = 0 gives the identity. Identity inputs (infinity = 1)
  * are legal and skipped; a finite point with a coordinate >= p or off y^2 = x^3 + 4, or an
- * infinity word other than 0 / 1, gives PLK_E_ARG. Subgroup membership is not checked.
- * One call at a time per context. */
+ * infinity word other than 0 / 1, gives PLK_E_ARG. Subgroup membership is not checked here:
+ * screen points with plk_g1_subgroup_check_batch (or decode them with plk_g1_decompress_batch /
+ * plk_proofs_ingest, which check it). One call at a time per context. */
 int plk_msm_points(plk_ctx* ctx, const plk_g1* points, const plk_fr* scalars, size_t n, plk_g1* out);
 /* Several sums over disjoint index ranges of ONE point array as one GPU batch:
  * outs[k] = sum_{i in [starts[k], starts[k] + lens[k])} scalars[i] * points[i], k < count <= 16,
@@ -367,7 +368,10 @@ int plk_prover_shard_buckets(plk_prover* p, int rank, int world, plk_allgather_f
  * Points are checked to be on the curve (identity commitments are legal: selector commitments
  * of unused widgets, w_z_chall_w_comm of trivial circuits). Subgroup membership is NOT checked
  * here: as in the reference (proof.rs:77, Proof holds decoded G1Affine values) it is the duty
- * of whoever decoded the proof bytes into points. */
+ * of whoever decoded the proof bytes into points. The ingest stage below is that decoder:
+ * plk_proofs_ingest / plk_proof_decode_compact check it for compact proofs,
+ * plk_g1_subgroup_check_batch for points that arrived through the SCALE route, and
+ * plk_verifier_verify_each_bytes runs ingest and the verdicts in one call. */
 typedef struct plk_verifier plk_verifier;
 typedef struct { plk_g1 c, w; } plk_kzg_pair;
 
@@ -459,7 +463,8 @@ int plk_opening_key_destroy(plk_opening_key* key);
 /* *ok = 1 iff e(pair.c, H) == e(pair.w, beta_h): ML(c, H) ML(-w, beta_h) final-exponentiates
  * to 1 (one shared Miller loop, as the reference's multi_miller_loop). Host only, needs no GPU.
  * Finite points must be canonical and on the curve (PLK_E_ARG otherwise, as in plk_msm_points);
- * subgroup membership is not checked (plk_verifier_fold's contract). A point at infinity
+ * subgroup membership is not checked (plk_verifier_fold's contract; plk_g1_subgroup_check_batch
+ * is the screen). A point at infinity
  * contributes the factor 1: (inf, inf) is accepted, (finite, inf) and (inf, finite) rejected. */
 int plk_pairing_check(const plk_opening_key* key, const plk_kzg_pair* pair, int* ok);
 /* The same check for `count` pairs on the GPU, one pair per lane (csrc/pairing.hip): ok[j] =
@@ -488,7 +493,8 @@ int plk_verifier_verify(plk_ctx* ctx, plk_verifier* v, const plk_opening_key* ke
  * pairs where they lie (no host round trip): ok[j] = 0 / 1. A malformed proof anywhere in the
  * batch makes the whole call PLK_E_ARG and leaves ok untouched — it never hides as ok = 0 and
  * never lets the other verdicts pass silently; decode and screen proofs first
- * (plk_proof_decode) when single malformed ones must be told apart. */
+ * (plk_proof_decode, or the batched plk_proofs_ingest) when single malformed ones must be told
+ * apart; plk_verifier_verify_each_bytes does both and gives one verdict per proof. */
 int plk_verifier_verify_each(plk_ctx* ctx, plk_verifier* v, plk_opening_key* key,
                              const plk_proof* proofs, const plk_fr* public_inputs, size_t count,
                              uint8_t* ok);
@@ -515,6 +521,66 @@ int plk_verifier_last_each_stats(const plk_verifier* v, float* pairs_ms, float* 
 #define PLK_PROOF_SCALE_BYTES (11 * 97 + 16 * 32)
 int plk_proof_encode(const plk_proof* proof, uint8_t* out, size_t cap, size_t* len);
 int plk_proof_decode(const uint8_t* in, size_t len, plk_proof* proof);
+
+/* ---- Compact proofs and the ingest stage (csrc/ingest.hip) -------------------------------
+ * The compact form of a proof, the shape of upstream dusk-plonk's Proof::to_bytes: the 11
+ * commitments in plk_proof order as zkcrypto's 48-byte compressed G1, then the 16 evaluations as
+ * 32 canonical little-endian bytes each (NOT Montgomery), PLK_PROOF_COMPACT_BYTES in all. ASSUMED,
+ * parity unpinned, as the SCALE codec above: the element crates are not vendored. A point is
+ * exactly what the transcript hashes (csrc/transcript.hpp g1_compress): x big-endian, and in byte
+ * 0 bit 7 = compressed (always set), bit 6 = infinity, bit 5 = y is the larger root (y > (p-1)/2);
+ * infinity is 0xc0 and 47 zero bytes. A scalar is what the transcript's append_scalar writes.
+ * Decoding is strict, so that one proof has one byte string. It rejects: bit 7 clear; the
+ * infinity bit with any other bit or byte set; x >= p; x^3 + 4 not a square; a scalar >= r; and,
+ * with check_subgroup != 0, a curve point outside G1 (not of order r). Reading a point back costs
+ * one Fp square root, y = (x^3 + 4)^((p+1)/4), and the subgroup check two multiplications by
+ * x0 = 0xd201000000010000 (the endomorphism test of Scott, eprint 2021/1130 section 6, what
+ * zkcrypto's is_torsion_free does): P in G1  <=>  (beta x, y) == -[x0^2]P. */
+#define PLK_PROOF_COMPACT_BYTES (11 * 48 + 16 * 32)
+/* Host only. out = NULL: a size query. PLK_E_ARG: cap too small, a non-canonical field. */
+int plk_proof_encode_compact(const plk_proof* proof, uint8_t* out, size_t cap, size_t* len);
+/* Host only, one proof: the single-proof path, and the independent check of the kernels below.
+ * PLK_E_ARG for a wrong length and for every rejection listed above; *out is then untouched. */
+int plk_proof_decode_compact(const uint8_t* in, size_t len, plk_proof* out, int check_subgroup);
+
+/* Per-item status of the batched calls, one byte each; the first failure wins (for a point in
+ * the order of the list; for a proof over its 27 fields in order). */
+#define PLK_INGEST_OK 0
+#define PLK_INGEST_ENCODING 1   /* flag bits / infinity form */
+#define PLK_INGEST_RANGE 2      /* x >= p or a scalar >= r */
+#define PLK_INGEST_OFF_CURVE 3  /* x^3 + 4 has no square root */
+#define PLK_INGEST_SUBGROUP 4   /* on the curve, not of order r */
+
+/* The batched calls below run on the GPU, one point per lane. Host buffers. The content of the
+ * bytes never makes them fail: only a NULL pointer or a zero count is PLK_E_ARG (and
+ * plk_g1_subgroup_check_batch's malformed points, see there). One call at a time per context. */
+/* n compressed points (48 n bytes) -> out[i] (canonical; all zero bytes when status[i] != 0) and
+ * status[i]. check_subgroup = 0 skips the membership test. */
+int plk_g1_decompress_batch(plk_ctx* ctx, const uint8_t* in48, size_t n, int check_subgroup,
+                            plk_g1* out, uint8_t* status);
+/* ok[i] = 1 iff points[i] is in G1 (the identity is), for points already in ABI form, e.g. of
+ * proofs that arrived through the SCALE route. PLK_E_ARG for a non-canonical or off-curve finite
+ * point or an infinity word other than 0 / 1, as plk_msm_points. */
+int plk_g1_subgroup_check_batch(plk_ctx* ctx, const plk_g1* points, size_t n, uint8_t* ok);
+/* `count` compact proofs (count * PLK_PROOF_COMPACT_BYTES bytes) -> out[j], status[j]. An accepted
+ * proof is byte for byte what plk_proof_decode_compact gives. out[j] of a rejected proof is all
+ * zero bytes: finite points off the curve, which plk_verifier_fold refuses should it ever be
+ * passed on by mistake. */
+int plk_proofs_ingest(plk_ctx* ctx, const uint8_t* in, size_t count, int check_subgroup,
+                      plk_proof* out, uint8_t* status);
+/* Milliseconds of the two kernels of the most recent batched call above on this context (HIP
+ * events around each; measurement only). subgroup_ms is 0 when that kernel did not run. */
+int plk_ingest_last_ms(plk_ctx* ctx, float* decompress_ms, float* subgroup_ms);
+/* plk_proofs_ingest, then plk_verifier_verify_each on the accepted proofs and their public
+ * inputs (compacted through host memory), verdicts scattered back: verdict[j] = 1 valid, 0
+ * well-formed but the pairing check fails, 0x10 | status when ingest rejected proof j.
+ * public_inputs holds count * pi_count values, those of rejected proofs are skipped. When every
+ * proof is rejected, plk_verifier_verify_each is not called. Both replay modes work. What
+ * plk_verifier_verify_each still refuses in a well-formed proof (a non-canonical public input,
+ * z_h(z) = 0) is PLK_E_ARG for the call, as there. */
+int plk_verifier_verify_each_bytes(plk_ctx* ctx, plk_verifier* v, plk_opening_key* key,
+                                   const uint8_t* in, const plk_fr* public_inputs, size_t count,
+                                   int check_subgroup, uint8_t* verdict);
 
 /* ---- test support ---------------------------------------------------------------- */
 /* Elementwise device field arithmetic on host arrays (used by the parity tests to pin the
