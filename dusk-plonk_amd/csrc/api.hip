@@ -545,3 +545,9 @@ int plk_srs_last_msm_stats(const plk_srs* s, float* accumulate_ms, uint64_t* poi
 }
 
 }  // extern "C"
+
+// the SRS loaders' two ends, for loaders in other units (srs_io.hip)
+namespace plk {
+int srs_new(plk_ctx* ctx, size_t n, std::unique_ptr<plk_srs>& s) { return srs_alloc(ctx, n, s); }
+int srs_complete(plk_srs* s) { return srs_finish(s); }
+}  // namespace plk

@@ -129,6 +129,11 @@ struct plk_srs {
   plk::DevBuf table;         // precomputed 2^(c*w) * P_i, affine, windows * n entries
   plk::DevBuf table_inf;     // uint8, windows * n
   bool has_inf = false;      // any point at infinity in the SRS (slow-path flag checks)
+  // what is known of the points (srs_io.hip): canonical and on the curve / of order r. Set by
+  // plk_srs_load_bytes and by a plk_srs_verify that got past the step; plk_srs_load and
+  // plk_srs_setup leave both false, so plk_srs_verify runs every step on their SRS
+  bool points_checked = false, subgroup_checked = false;
+  double verify_fold_ms = 0.0, verify_pairing_ms = 0.0;  // the most recent plk_srs_verify
   plk::DevBuf staging;       // host-scalar entry points stage through it
   // the workspace of the SRS's own entry points (plk_msm / plk_commit*: one thread at a
   // time); concurrent provers sharing this SRS each bring their own (plk_prover)
@@ -151,6 +156,8 @@ struct plk_ctx {
   plk::VarMsmWs* var_ws = nullptr;
   // buffers, events and timings of the ingest stage (ingest.hip), made on first use
   plk::IngestWs* ingest_ws = nullptr;
+  // kernel times of the most recent plk_srs_load_bytes (srs_io.hip; measurement only)
+  float srs_decode_ms = 0.f, srs_subgroup_ms = 0.f;
 };
 
 namespace plk {
@@ -242,6 +249,10 @@ int ntt_run_batch(plk_domain* d, const Fr* in, Fr* out, size_t len_in, int dir, 
 // in place of the domain's g^j table — a scaled table (c g^j) yields the evaluations of c p
 int ntt_run(plk_domain* d, const Fr* in, Fr* out, size_t len_in, int dir, int coset,
             Fr* scratch, hipStream_t stream, uint32_t count, const Fr* pre_table = nullptr);
+// An SRS object with its point and infinity arrays allocated (api.hip srs_alloc), and what every
+// loader ends with once they are filled: the has_inf scan and the MSM table (srs_finish).
+int srs_new(plk_ctx* ctx, size_t n, std::unique_ptr<plk_srs>& s);
+int srs_complete(plk_srs* s);
 int msm_prepare_srs(plk_srs* s, hipStream_t stream, uint32_t force_c = 0, bool own_ws = true);
 // The Lagrange-basis SRS of `dom` from the first dom->n + 3 points of `src` (lagrange.hip):
 // [L_i(tau)]_1 for i < n, then [tau^(n+t)]_1 - [tau^t]_1 for t < 3; an ordinary SRS with src's

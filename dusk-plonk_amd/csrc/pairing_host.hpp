@@ -167,6 +167,127 @@ inline void g2_to_abi(const G2Aff& q, plk_g2* o) {
   fp_to_abi(q.y.c1, o->y + 6);
 }
 
+// ---- zkcrypto's G2 byte forms (include/plk.h "An SRS from bytes") -----------------------------
+// a^e for a little-endian exponent of 12 words (a plain integer)
+inline Fp2 f2_pow(const Fp2& a, const uint32_t* e) {
+  Fp2 r = f2_one();
+  for (int w = 11; w >= 0; --w)
+    for (int b = 31; b >= 0; --b) {
+      r = f2_sqr(r);
+      if ((e[w] >> b) & 1u) r = f2_mul(r, a);
+    }
+  return r;
+}
+
+// A square root of a in Fp2, p = 3 mod 4 (Adj, Rodriguez-Henriquez, eprint 2012/685 algorithm 9,
+// two exponentiations): a1 = a^((p-3)/4), x0 = a1 a, alpha = a1 x0 = a^((p-1)/2). alpha = -1:
+// the root is u x0; else (1 + alpha)^((p-1)/2) x0. The candidate is verified by squaring, so a
+// non-square gives false whatever the branches computed.
+inline bool f2_sqrt(const Fp2& a, Fp2& out) {
+  out = f2_zero();
+  if (f2_is_zero(a)) return true;
+  uint32_t e1[12], e2[12];  // (p - 3) / 4 and (p - 1) / 2
+  for (int i = 0; i < 12; ++i) {
+    const uint32_t hi = i < 11 ? FpCfg::P[i + 1] : 0u;
+    e1[i] = (FpCfg::P[i] >> 2) | (hi << 30);  // p = 3 mod 4: floor(p / 4) = (p - 3) / 4
+    e2[i] = (FpCfg::P[i] >> 1) | (hi << 31);  // p odd: floor(p / 2) = (p - 1) / 2
+  }
+  const Fp2 a1 = f2_pow(a, e1);
+  const Fp2 x0 = f2_mul(a1, a);
+  const Fp2 alpha = f2_mul(a1, x0);
+  Fp2 x;
+  if (f2_eq(alpha, f2_neg(f2_one()))) {
+    x = {fe_neg(x0.c1), x0.c0};  // u x0
+  } else {
+    x = f2_mul(f2_pow(f2_add(f2_one(), alpha), e2), x0);
+  }
+  if (!f2_eq(f2_sqr(x), a)) return false;
+  out = x;
+  return true;
+}
+
+// 48 big-endian bytes -> a plain (not Montgomery) value; the caller masks flag bits first
+inline Fp fp_from_be(const uint8_t* b) {
+  Fp r;
+  for (int i = 0; i < 12; ++i) {
+    const uint8_t* q = b + 44 - 4 * i;
+    r.v[i] = ((uint32_t)q[0] << 24) | ((uint32_t)q[1] << 16) | ((uint32_t)q[2] << 8) | q[3];
+  }
+  return r;
+}
+
+// Montgomery value -> 48 big-endian bytes
+inline void fp_to_be(const Fp& a_mont, uint8_t* b) {
+  const Fp a = fe_from_mont(a_mont);
+  for (int i = 0; i < 12; ++i)
+    for (int k = 0; k < 4; ++k) b[47 - (4 * i + k)] = (uint8_t)(a.v[i] >> (8 * k));
+}
+
+// a > (p - 1) / 2 for a Montgomery value, i.e. a > -a as integers
+inline bool fp_is_larger_half(const Fp& a_mont) {
+  const Fp a = fe_from_mont(a_mont), na = fe_from_mont(fe_neg(a_mont));
+  for (int i = 11; i >= 0; --i)
+    if (a.v[i] != na.v[i]) return a.v[i] > na.v[i];
+  return false;
+}
+
+// the sort bit of a G2 point: y is the lexicographically larger of +-y, c1 first
+inline bool g2_y_is_larger(const Fp2& y) {
+  return fe_is_zero(y.c1) ? fp_is_larger_half(y.c0) : fp_is_larger_half(y.c1);
+}
+
+// compressed (96 B) or uncompressed (192 B) -> a point on the twist or the identity. PLK_E_ARG
+// for every strict rejection; the subgroup check is the caller's.
+inline int g2_from_bytes(const uint8_t* in, bool compressed, G2Aff& o) {
+  const size_t len = compressed ? 96 : 192;
+  const uint8_t flags = in[0] & 0xe0;
+  o = g2_infinity();
+  if (((flags & 0x80) != 0) != compressed) return PLK_E_ARG;
+  if (flags & 0x40) {  // infinity: the flag byte alone
+    if (in[0] != (compressed ? 0xc0 : 0x40)) return PLK_E_ARG;
+    for (size_t i = 1; i < len; ++i)
+      if (in[i]) return PLK_E_ARG;
+    return PLK_OK;
+  }
+  if (!compressed && (flags & 0x20)) return PLK_E_ARG;
+  uint8_t first[48];
+  memcpy(first, in, 48);
+  first[0] &= 0x1f;
+  const Fp xc1 = fp_from_be(first), xc0 = fp_from_be(in + 48);
+  if (!fp_canonical(xc1) || !fp_canonical(xc0)) return PLK_E_ARG;
+  o.x = {fe_to_mont(xc0), fe_to_mont(xc1)};
+  o.inf = false;
+  if (compressed) {
+    const Fp four = fe_dbl(fe_dbl(fe_one<FpCfg>()));
+    const Fp2 rhs = f2_add(f2_mul(f2_sqr(o.x), o.x), f2_mul_xi({four, fe_zero<FpCfg>()}));
+    Fp2 y;
+    if (!f2_sqrt(rhs, y)) return PLK_E_ARG;
+    if (g2_y_is_larger(y) != ((flags & 0x20) != 0)) y = f2_neg(y);
+    o.y = y;
+    return PLK_OK;
+  }
+  const Fp yc1 = fp_from_be(in + 96), yc0 = fp_from_be(in + 144);
+  if (!fp_canonical(yc1) || !fp_canonical(yc0)) return PLK_E_ARG;
+  o.y = {fe_to_mont(yc0), fe_to_mont(yc1)};
+  return g2_on_curve(o) ? PLK_OK : PLK_E_ARG;
+}
+
+inline void g2_to_bytes(const G2Aff& q, bool compressed, uint8_t* out) {
+  memset(out, 0, compressed ? 96 : 192);
+  if (q.inf) {
+    out[0] = compressed ? 0xc0 : 0x40;
+    return;
+  }
+  fp_to_be(q.x.c1, out);
+  fp_to_be(q.x.c0, out + 48);
+  if (compressed) {
+    out[0] |= 0x80 | (g2_y_is_larger(q.y) ? 0x20 : 0);
+    return;
+  }
+  fp_to_be(q.y.c1, out + 96);
+  fp_to_be(q.y.c0, out + 144);
+}
+
 // e(c, Q0) == e(w, Q1), as ML(c, Q0) ML(-w, Q1) -> final exponentiation == 1. lines0 / lines1:
 // the prepared tables of Q0 / Q1; frob: frob_table.
 inline bool pairing_check_host(const Fp2* lines0, const Fp2* lines1, const Fp2* frob, const G1In& c,

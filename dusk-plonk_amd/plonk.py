@@ -32,6 +32,14 @@ _LIB_PATH = Path(os.environ["PLK_LIB"]) if os.environ.get("PLK_LIB") else _PKG /
 
 PLK_OK, PLK_E_DEGREE, PLK_E_ARG, PLK_E_DEVICE, PLK_E_OOM, PLK_E_NODEV = range(6)
 
+# the entry points of csrc/srs_io.hip: an SRS and an opening key from bytes, the SRS fold and its
+# verification (bound only when the loaded library has them: a PLK_LIB build may be older)
+_SRS_IO_SYMBOLS = (
+    "plk_srs_load_bytes", "plk_srs_export_bytes", "plk_srs_last_load_ms", "plk_srs_fold",
+    "plk_srs_verify", "plk_srs_last_verify_ms", "plk_opening_key_load_bytes",
+    "plk_opening_key_to_bytes", "plk_debug_srs_weights", "plk_debug_f2_sqrt",
+)
+
 # Symbols declared in include/plk.h (checked by tests/test_abi.py)
 ABI_SYMBOLS = (
     "plk_abi_version", "plk_status_str", "plk_build_info", "plk_device_count", "plk_ctx_create",
@@ -76,15 +84,23 @@ ABI_SYMBOLS = (
     "plk_proof_encode_compact", "plk_proof_decode_compact", "plk_g1_decompress_batch",
     "plk_g1_subgroup_check_batch", "plk_proofs_ingest", "plk_ingest_last_ms",
     "plk_verifier_verify_each_bytes",
+    *_SRS_IO_SYMBOLS,
 )
 
 # per-item status of the ingest calls (include/plk.h PLK_INGEST_*)
 INGEST_OK, INGEST_ENCODING, INGEST_RANGE, INGEST_OFF_CURVE, INGEST_SUBGROUP = range(5)
+# verdicts of PlonkParams.verify (include/plk.h PLK_SRS_*)
+SRS_OK, SRS_POINT, SRS_SUBGROUP, SRS_INFINITY, SRS_GENERATOR, SRS_CHAIN = range(6)
+# byte forms of points (include/plk.h PLK_G1_COMPRESSED / PLK_G1_UNCOMPRESSED)
+_FORMATS = {"compressed": 0, "uncompressed": 1}
 
 
 class PlonkError(RuntimeError):
-    def __init__(self, status: int, what: str = ""):
+    def __init__(self, status: int, what: str = "", bad_index: int | None = None,
+                 bad_status: int | None = None):
         self.status = status
+        # PlonkParams.from_bytes: the smallest rejected index and its INGEST_* code
+        self.bad_index, self.bad_status = bad_index, bad_status
         msg = _lib().plk_status_str(status).decode() if _LIB is not None else str(status)
         super().__init__(f"{what}: {msg} (status {status})" if what else msg)
 
@@ -164,8 +180,20 @@ def _lib():
             "plk_g1_decompress_batch": (i32, [vp, vp, sz, i32, vp, vp]),
             "plk_g1_subgroup_check_batch": (i32, [vp, vp, sz, vp]),
             "plk_ingest_last_ms": (i32, [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+            "plk_srs_load_bytes": (i32, [vp, vp, sz, i32, i32, pp, C.POINTER(u64), C.POINTER(C.c_uint8)]),
+            "plk_srs_export_bytes": (i32, [vp, sz, sz, i32, vp]),
+            "plk_srs_last_load_ms": (i32, [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+            "plk_srs_fold": (i32, [vp, vp, vp]),
+            "plk_srs_verify": (i32, [vp, vp, vp, vp, C.POINTER(i32), C.POINTER(u64)]),
+            "plk_srs_last_verify_ms": (i32, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+            "plk_opening_key_load_bytes": (i32, [vp, vp, i32, pp]),
+            "plk_opening_key_to_bytes": (i32, [vp, i32, vp, vp]),
+            "plk_debug_srs_weights": (i32, [vp, vp, sz, vp]),
+            "plk_debug_f2_sqrt": (i32, [vp, vp, C.POINTER(i32)]),
         }
         for name, (res, args) in sig.items():
+            if name in _SRS_IO_SYMBOLS and not hasattr(lib, name):
+                continue  # a PLK_LIB build from before srs_io.hip still loads; a use fails loudly
             f = getattr(lib, name)
             f.restype, f.argtypes = res, args
         _LIB = lib
@@ -589,6 +617,44 @@ def ingest_last_ms(ctx: "Context | None" = None):
     return a.value, b.value
 
 
+def _seed32(seed) -> np.ndarray:
+    raw = np.frombuffer(bytes(seed), dtype=np.uint8)
+    if raw.size != 32:
+        raise ValueError("a seed is 32 bytes")
+    return raw
+
+
+class SrsVerdict:
+    """Result of PlonkParams.verify: ok, verdict (an SRS_* class) and bad_index (the smallest
+    offending index for SRS_POINT / SRS_SUBGROUP / SRS_INFINITY, else None)."""
+
+    def __init__(self, ok: bool, verdict: int, bad_index: int | None):
+        self.ok, self.verdict, self.bad_index = ok, verdict, bad_index
+
+    def __bool__(self):
+        return self.ok
+
+    def __repr__(self):
+        return f"SrsVerdict(ok={self.ok}, verdict={self.verdict}, bad_index={self.bad_index})"
+
+
+def srs_last_load_ms(ctx: "Context | None" = None):
+    """(decode kernel ms, subgroup kernel ms) of the most recent PlonkParams.from_bytes on the context."""
+    ctx = ctx or Context.default()
+    a, b = C.c_float(), C.c_float()
+    _check(_lib().plk_srs_last_load_ms(ctx.handle, C.byref(a), C.byref(b)), "plk_srs_last_load_ms")
+    return a.value, b.value
+
+
+def debug_srs_weights(seed, n: int, ctx: "Context | None" = None) -> np.ndarray:
+    """Test support (plk_debug_srs_weights): the n - 1 fold weights of an n-point SRS for `seed`,
+    uint64[n - 1, 4] Montgomery limbs. ctx = None: the host mirror; otherwise the kernel."""
+    out = np.zeros((max(1, n - 1), 4), dtype=np.uint64)
+    _check(_lib().plk_debug_srs_weights(ctx.handle if ctx is not None else None, _ptr(_seed32(seed)), n,
+                                        _ptr(out)), "plk_debug_srs_weights")
+    return out[:n - 1]
+
+
 class PlonkParams:
     """zksnarks::plonk::PlonkParams<TatePairing> (the G1 side used by the prover).
 
@@ -630,6 +696,63 @@ class PlonkParams:
         h = C.c_void_p()
         _check(_lib().plk_srs_load(ctx.handle, _ptr(pts), pts.shape[0], C.byref(h)), "plk_srs_load")
         return cls(h, pts.shape[0], ctx)
+
+    @classmethod
+    def from_bytes(cls, blob, fmt: str = "compressed", subgroup: bool = True,
+                   ctx: Context | None = None) -> "PlonkParams":
+        """An SRS from a bare array of zkcrypto-encoded points (48 bytes each compressed, 96
+        uncompressed), decoded and checked on the GPU (plk_srs_load_bytes). One rejected point
+        raises PlonkError(PLK_E_ARG) carrying bad_index (the smallest rejected index) and
+        bad_status (its INGEST_* code). subgroup=False skips the membership test; verify() then
+        runs it."""
+        ctx = ctx or Context.default()
+        size = 48 if _FORMATS[fmt] == 0 else 96
+        raw = np.frombuffer(bytes(blob), dtype=np.uint8)
+        if raw.size == 0 or raw.size % size:
+            raise PlonkError(PLK_E_ARG, f"PlonkParams.from_bytes: a positive multiple of {size} bytes")
+        n = raw.size // size
+        h, idx, code = C.c_void_p(), C.c_uint64(0), C.c_uint8(0)
+        st = _lib().plk_srs_load_bytes(ctx.handle, _ptr(raw), n, _FORMATS[fmt], int(bool(subgroup)),
+                                       C.byref(h), C.byref(idx), C.byref(code))
+        if st == PLK_E_ARG and code.value != INGEST_OK:
+            raise PlonkError(st, f"plk_srs_load_bytes: point {idx.value} rejected (status {code.value})",
+                             bad_index=idx.value, bad_status=code.value)
+        _check(st, "plk_srs_load_bytes")
+        return cls(h, n, ctx)
+
+    def to_bytes(self, fmt: str = "compressed", start: int = 0, count: int | None = None) -> bytes:
+        """Points [start, start + count) in zkcrypto's byte form, encoded on the GPU
+        (plk_srs_export_bytes); from_bytes of the result reproduces points() bit for bit."""
+        count = self.n - start if count is None else count
+        out = np.zeros(max(1, count * (48 if _FORMATS[fmt] == 0 else 96)), dtype=np.uint8)
+        _check(_lib().plk_srs_export_bytes(self._h, start, count, _FORMATS[fmt], _ptr(out)),
+               "plk_srs_export_bytes")
+        return out[:count * (48 if _FORMATS[fmt] == 0 else 96)].tobytes()
+
+    def fold_chain(self, seed: bytes | None = None) -> np.ndarray:
+        """(C, W) as uint64[2, 13]: C = sum rho_i g1[i+1], W = sum rho_i g1[i] over weights drawn
+        from `seed` (None: OS entropy, the sound form) — plk_srs_fold. The SRS is a chain of powers
+        of the opening key's tau iff OpeningKey.check((C, W)) holds, up to 2^-128."""
+        out = np.zeros((2, 13), dtype=np.uint64)
+        sd = None if seed is None else _ptr(_seed32(seed))
+        _check(_lib().plk_srs_fold(self._h, sd, _ptr(out)), "plk_srs_fold")
+        return out
+
+    def verify(self, opening_key: "OpeningKey", seed: bytes | None = None) -> "SrsVerdict":
+        """Is this SRS ([tau^i]G)_i for the tau of `opening_key`? (plk_srs_verify.) A bad SRS is a
+        verdict, never an exception."""
+        verdict, idx = C.c_int(-1), C.c_uint64(0xFFFFFFFFFFFFFFFF)
+        sd = None if seed is None else _ptr(_seed32(seed))
+        _check(_lib().plk_srs_verify(self.ctx.handle, self._h, opening_key._h, sd, C.byref(verdict),
+                                     C.byref(idx)), "plk_srs_verify")
+        bad = idx.value if verdict.value in (SRS_POINT, SRS_SUBGROUP, SRS_INFINITY) else None
+        return SrsVerdict(verdict.value == SRS_OK, verdict.value, bad)
+
+    def last_verify_ms(self):
+        """(fold ms, pairing ms) of the most recent verify() that reached the fold (host wall time)."""
+        a, b = C.c_double(), C.c_double()
+        _check(_lib().plk_srs_last_verify_ms(self._h, C.byref(a), C.byref(b)), "plk_srs_last_verify_ms")
+        return a.value, b.value
 
     def lagrange(self, k: int) -> "PlonkParams":
         """The Lagrange-basis SRS of the 2^k domain (plk_srs_lagrange): 2^k + 3 points, the
@@ -798,6 +921,27 @@ class OpeningKey:
         _check(_lib().plk_opening_key_load(_ptr(a), _ptr(b), C.byref(out)), "OpeningKey::load")
         return cls(out)
 
+    @classmethod
+    def from_bytes(cls, h: bytes, beta_h: bytes, fmt: str = "compressed") -> "OpeningKey":
+        """A key from zkcrypto's G2 byte forms (96 bytes per point compressed, 192 uncompressed;
+        plk_opening_key_load_bytes). Strict decoding, then every check of load()."""
+        size = 96 if _FORMATS[fmt] == 0 else 192
+        a, b = np.frombuffer(bytes(h), dtype=np.uint8), np.frombuffer(bytes(beta_h), dtype=np.uint8)
+        if a.size != size or b.size != size:
+            raise PlonkError(PLK_E_ARG, f"OpeningKey.from_bytes: {size} bytes per point")
+        out = C.c_void_p()
+        _check(_lib().plk_opening_key_load_bytes(_ptr(a), _ptr(b), _FORMATS[fmt], C.byref(out)),
+               "OpeningKey::from_bytes")
+        return cls(out)
+
+    def to_bytes(self, fmt: str = "compressed"):
+        """(H, beta_h) in zkcrypto's G2 byte form (plk_opening_key_to_bytes)."""
+        size = 96 if _FORMATS[fmt] == 0 else 192
+        a, b = np.zeros(size, dtype=np.uint8), np.zeros(size, dtype=np.uint8)
+        _check(_lib().plk_opening_key_to_bytes(self._h, _FORMATS[fmt], _ptr(a), _ptr(b)),
+               "plk_opening_key_to_bytes")
+        return a.tobytes(), b.tobytes()
+
     def points(self):
         """(H, beta_h) as uint64[25] rows."""
         a, b = np.zeros(G2_WORDS, dtype=np.uint64), np.zeros(G2_WORDS, dtype=np.uint64)
@@ -834,6 +978,15 @@ class OpeningKey:
         except Exception:
             pass
         self._h = None
+
+
+def debug_f2_sqrt(a):
+    """Test support (plk_debug_f2_sqrt): the host Fp2 square root. a: uint64[12] (c0, c1 Montgomery
+    limbs) -> (root uint64[12], is_square)."""
+    v = np.ascontiguousarray(np.asarray(a, dtype=np.uint64).reshape(12))
+    out, ok = np.zeros(12, dtype=np.uint64), C.c_int(0)
+    _check(_lib().plk_debug_f2_sqrt(_ptr(v), _ptr(out), C.byref(ok)), "plk_debug_f2_sqrt")
+    return out, bool(ok.value)
 
 
 def debug_pairing(points, q, ctx: "Context | None" = None) -> np.ndarray:

@@ -117,7 +117,8 @@ int plk_srs_setup(plk_ctx* ctx, const plk_fr* tau, size_t n_points, plk_g1* out_
  * range): the per-GPU shard of a sharded MSM. */
 int plk_srs_setup_range(plk_ctx* ctx, const plk_fr* tau, uint64_t start, size_t n_points,
                         plk_g1* out_points, plk_srs** out);
-/* Load an existing SRS (e.g. a trimmed PlonkParams) from host affine points. */
+/* Load an existing SRS (e.g. a trimmed PlonkParams) from host affine points. The points are
+ * taken on faith: plk_srs_verify (below) checks them and their structure against an opening key. */
 int plk_srs_load(plk_ctx* ctx, const plk_g1* points, size_t n_points, plk_srs** out);
 /* The Lagrange-basis SRS of the 2^log_n-point domain, computed from the first 2^log_n + 3
  * points of `srs` alone (an inverse DFT over G1): point i < n is [L_i(tau)]G1, and points
@@ -582,7 +583,83 @@ int plk_verifier_verify_each_bytes(plk_ctx* ctx, plk_verifier* v, plk_opening_ke
                                    const uint8_t* in, const plk_fr* public_inputs, size_t count,
                                    int check_subgroup, uint8_t* verdict);
 
+/* ---- An SRS from bytes, and its verification (csrc/srs_io.hip) ---------------------------
+ * A ceremony's SRS comes as bare arrays of points in zkcrypto's byte forms. ASSUMED, parity
+ * unpinned, as the compact proof above: the element crates are not vendored.
+ *  - PLK_G1_COMPRESSED, 48 B: exactly the form of plk_g1_decompress_batch (and of the compact
+ *    proof's commitments), with its strict rules.
+ *  - PLK_G1_UNCOMPRESSED, 96 B: x big-endian then y big-endian; in byte 0 bit 7 = 0 (not
+ *    compressed), bit 6 = infinity, bit 5 = 0. Infinity is 0x40 and 95 zero bytes. Decoding is
+ *    strict: bit 7 or bit 5 set, or any other bit or byte under the infinity bit, is
+ *    PLK_INGEST_ENCODING; x >= p or y >= p PLK_INGEST_RANGE; y^2 != x^3 + 4 PLK_INGEST_OFF_CURVE.
+ *  - G2 (the opening key): compressed 96 B = x.c1 big-endian then x.c0, the G1 flag bits in byte
+ *    0, the sort bit set when y is the lexicographically larger of +-y (y.c1 > (p-1)/2, or y.c1 =
+ *    0 and y.c0 > (p-1)/2); uncompressed 192 B = x.c1, x.c0, y.c1, y.c0. */
+#define PLK_G1_COMPRESSED 0
+#define PLK_G1_UNCOMPRESSED 1
+/* n_points points in `format` (48 n / 96 n bytes, a host buffer) -> an SRS, as plk_srs_load gives
+ * for the same points. The bytes are uploaded and decoded on the GPU, one point per lane,
+ * straight into the SRS's device arrays; with check_subgroup != 0 every point is also tested for
+ * order r. Infinity encodings are accepted (a Lagrange-basis SRS holds them legitimately). One
+ * rejected point makes the call PLK_E_ARG with *out = NULL and no table built; *bad_index
+ * (nullable) is then the smallest rejected index and *bad_status (nullable) its PLK_INGEST_*
+ * code, found by a reduction on the device. The SRS remembers that its points are canonical and
+ * on the curve and whether they passed the subgroup test (plk_srs_verify skips what is known). */
+int plk_srs_load_bytes(plk_ctx* ctx, const uint8_t* in, size_t n_points, int format,
+                       int check_subgroup, plk_srs** out, uint64_t* bad_index, uint8_t* bad_status);
+/* Points [start, start + count) in `format` (48 / 96 bytes each), encoded on the GPU: out of
+ * Montgomery form, big-endian, the sort bit from y > (p-1)/2. A compressed export followed by
+ * plk_srs_load_bytes reproduces plk_srs_points bit for bit. PLK_E_ARG for a range outside the SRS
+ * or an unknown format. */
+int plk_srs_export_bytes(const plk_srs* srs, size_t start, size_t count, int format, uint8_t* out);
+/* Milliseconds of the decode and subgroup kernels of the most recent plk_srs_load_bytes on this
+ * context (HIP events around each; measurement only; 0 for a kernel that did not run). */
+int plk_srs_last_load_ms(plk_ctx* ctx, float* decode_ms, float* subgroup_ms);
+
+/* The structure check's fold. With weights rho_i, i < n - 1 (rho_0 = 1, the others independent
+ * 128-bit values):  out.c = sum rho_i g1[i+1],  out.w = sum rho_i g1[i].  On points of order r,
+ * g1[i+1] = tau g1[i] for every i  <=>  e(c, H) = e(w, [tau]H), except with probability 2^-128
+ * over the weights. The weights are derived on the device, one lane per index, from
+ * one merlin root over a domain label, n and the seed: rho_i = challenge_bytes("rho", 16) of a
+ * clone after append_u64("index", i), the pattern of the verifier's fold. seed = NULL takes 32
+ * bytes from getrandom and is the sound form; an explicit seed is for tests. Both sums run as one
+ * batch of two MSMs on the SRS's own table. n = 1 gives (inf, inf), which plk_pairing_check
+ * accepts. One call at a time per SRS. */
+int plk_srs_fold(plk_srs* srs, const uint8_t seed[32], plk_kzg_pair* out);
+#define PLK_SRS_OK 0
+#define PLK_SRS_POINT 1     /* non-canonical limb or off the curve (an SRS from plk_srs_load) */
+#define PLK_SRS_SUBGROUP 2  /* a point not of order r */
+#define PLK_SRS_INFINITY 3  /* a power of tau is never the identity */
+#define PLK_SRS_GENERATOR 4 /* g1[0] is not the standard generator */
+#define PLK_SRS_CHAIN 5     /* the pairing check of the fold fails */
+/* Is this SRS ([tau^i]G)_i for the tau of `key`? In order: the canonical / on-curve pass over the
+ * device points (skipped for an SRS from plk_srs_load_bytes), the subgroup kernel (skipped when
+ * already passed), the infinity scan, g1[0] == G, plk_srs_fold, one host plk_pairing_check.
+ * *verdict is the first failing class or PLK_SRS_OK; *bad_index (nullable) the smallest offending
+ * index for PLK_SRS_POINT / _SUBGROUP / _INFINITY, untouched otherwise. Without the generator
+ * test a uniformly scaled SRS would pass. A bad SRS is a verdict, not an error: only NULL
+ * pointers or an SRS of another context are PLK_E_ARG. seed as in plk_srs_fold. */
+int plk_srs_verify(plk_ctx* ctx, plk_srs* srs, const plk_opening_key* key, const uint8_t seed[32],
+                   int* verdict, uint64_t* bad_index);
+/* Milliseconds of the most recent plk_srs_verify on this SRS that reached the fold: the fold
+ * (weights and both MSMs, host wall time) and the host pairing check (measurement only). */
+int plk_srs_last_verify_ms(const plk_srs* srs, double* fold_ms, double* pairing_ms);
+
+/* The opening key in zkcrypto's G2 byte forms (above): `format` PLK_G1_COMPRESSED = 96 bytes per
+ * point, PLK_G1_UNCOMPRESSED = 192. Host only. Decoding is strict and mirrors the G1 rules (flag
+ * bits, every coefficient < p, x^3 + 4 (1 + u) a square in Fp2 / the twist equation); then every
+ * check of plk_opening_key_load applies: order r, not infinity. PLK_E_ARG otherwise. */
+int plk_opening_key_load_bytes(const uint8_t* h, const uint8_t* beta_h, int format,
+                               plk_opening_key** out);
+int plk_opening_key_to_bytes(const plk_opening_key* key, int format, uint8_t* h, uint8_t* beta_h);
+
 /* ---- test support ---------------------------------------------------------------- */
+/* out[i] = the weight rho_i of plk_srs_fold for an SRS of n points and this seed, i < n - 1
+ * (canonical Montgomery). ctx = NULL: computed on the host (the mirror of the kernel). */
+int plk_debug_srs_weights(plk_ctx* ctx, const uint8_t seed[32], size_t n, plk_fr* out);
+/* One host Fp2 square root (csrc/pairing_host.hpp f2_sqrt): a = (c0, c1) as 12 Montgomery limbs;
+ * *is_square = 1 and out = a root, or *is_square = 0. Needs no GPU. */
+int plk_debug_f2_sqrt(const uint64_t* a, uint64_t* out, int* is_square);
 /* Elementwise device field arithmetic on host arrays (used by the parity tests to pin the
  * gfx950 multiplier against the oracle): field 0 = Fr (4 limbs), 1 = Fp (6 limbs);
  * op 0 = a*b, 1 = a+b, 2 = a-b, 3 = a^2, 4 = a^-1 (Montgomery form in and out). */
