@@ -8,6 +8,7 @@ from .plonk import (  # noqa: F401
     ABI_SYMBOLS, Coefficients, Commitment, Context, Fft, OpeningKey, PLK_E_ARG, PLK_E_DEGREE,
     PLK_E_DEVICE, PLK_E_NODEV, PLK_E_OOM, PLK_OK, PlonkError, PlonkParams, PointsValue, build_info, check_build,
     debug_pairing, device_count, g1_decompress, g1_subgroup_check, g1_sum, ingest_last_ms, msm_points, msm_points_ranges, msm_sharded,
+    SrsVerdict, debug_glv_split, g1_mul, g1_mul_last_ms, g2_from_bytes, g2_to_bytes,
 )
 
 __all__ = [
@@ -16,4 +17,5 @@ __all__ = [
     "PointsValue", "build_info", "check_build", "debug_pairing", "device_count", "g1_decompress",
     "g1_subgroup_check", "g1_sum", "ingest_last_ms", "msm_points",
     "msm_points_ranges", "msm_sharded",
+    "SrsVerdict", "debug_glv_split", "g1_mul", "g1_mul_last_ms", "g2_from_bytes", "g2_to_bytes",
 ]

@@ -158,6 +158,8 @@ struct plk_ctx {
   plk::IngestWs* ingest_ws = nullptr;
   // kernel times of the most recent plk_srs_load_bytes (srs_io.hip; measurement only)
   float srs_decode_ms = 0.f, srs_subgroup_ms = 0.f;
+  // kernel time of the most recent scalar multiplication batch (g1_mul.hip; measurement only)
+  float g1_mul_ms = 0.f;
 };
 
 namespace plk {
@@ -313,4 +315,11 @@ int ntt_lazy_op(plk_ctx* ctx, int op, const uint32_t* in, uint32_t* out, size_t 
 int ntt_power_table(Fr* out, const Fr& base, const Fr& scale, uint64_t n, bool to_rx,
                     hipStream_t s);
 int srs_generate(plk_srs* s, const Fr& tau_mont, uint64_t start, hipStream_t stream);
+// Batched scalar multiplication (g1_mul.hip): out[i] = [scal[i]] pts[i] in canonical affine form
+// with identity flags; device arrays of n entries, the points in G1 (the caller's check), the
+// scalars canonical Montgomery. Waits for the stream.
+int g1_mul_dev(plk_ctx* ctx, const G1Affine* pts, const uint8_t* inf, const Fr* scal, uint64_t n,
+               G1Affine* out, uint8_t* out_inf, hipStream_t s);
+// d_out[i] = s^i, i < n (Montgomery), stream-ordered
+int fr_powers_dev(const Fr& s_mont, uint64_t n, Fr* d_out, hipStream_t s);
 }  // namespace plk

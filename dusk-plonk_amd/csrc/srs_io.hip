@@ -15,6 +15,10 @@
 //    SRS's own table (msm_run_batch), one host pairing check. No new MSM or pairing kernel.
 //  - The opening key from bytes: host only, pairing_host.hpp g2_from_bytes / g2_to_bytes, then
 //    plk_opening_key_load with all its checks.
+//  - plk_srs_update / plk_srs_verify_update (include/plk.h "Updating an SRS"): the powers s^i on
+//    the device, one scalar multiplication per point (g1_mul.hip), the opening key and the witness
+//    [s]H on the host (g2_mul); the verification is plk_srs_verify plus one host pairing check on
+//    the temporary key (H, witness).
 #include <sys/random.h>
 
 #include <chrono>
@@ -318,6 +322,86 @@ double ms_since(std::chrono::steady_clock::time_point t0) {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
+// ---- updating an SRS --------------------------------------------------------------------------
+// s: canonical Montgomery, not zero
+bool update_scalar_ok(const Fr& s) { return fe_canonical(s) && !fe_is_zero(s); }
+
+// 64 bytes of OS entropy reduced mod r (Montgomery form), redrawn on zero
+void fr_from_entropy(Fr& out) {
+  uint8_t buf[64];
+  Fr lo, hi;
+  do {
+    srs_entropy(buf);
+    srs_entropy(buf + 32);
+    for (int i = 0; i < 8; ++i) {
+      std::memcpy(&lo.v[i], buf + 4 * i, 4);
+      std::memcpy(&hi.v[i], buf + 32 + 4 * i, 4);
+    }
+    fe_reduce_once(lo);  // 2^256 < 3 r: two subtractions bring a 256-bit value below r
+    fe_reduce_once(lo);
+    fe_reduce_once(hi);
+    fe_reduce_once(hi);
+    // lo + hi 2^256: fe_one's words are 2^256 mod r as a plain value
+    out = fe_add(fe_to_mont(lo), fe_mul(fe_to_mont(hi), fe_to_mont(fe_one<FrCfg>())));
+  } while (fe_is_zero(out));
+  explicit_bzero(buf, sizeof buf);
+  explicit_bzero(&lo, sizeof lo);
+  explicit_bzero(&hi, sizeof hi);
+}
+
+// a device array that held secrets: overwritten before it is freed (best effort)
+struct SecretDevBuf {
+  DevBuf d;
+  hipStream_t s = nullptr;
+  ~SecretDevBuf() {
+    if (!d.ptr) return;
+    (void)hipMemsetAsync(d.ptr, 0, d.bytes, s);
+    (void)stream_wait(s);
+  }
+};
+
+struct KeyHolder {  // destroys the key unless it was released
+  plk_opening_key* k = nullptr;
+  ~KeyHolder() {
+    if (k) (void)plk_opening_key_destroy(k);
+  }
+  plk_opening_key* release() {
+    plk_opening_key* r = k;
+    k = nullptr;
+    return r;
+  }
+};
+
+// the canonical / on-curve pass and the subgroup kernel over an SRS not yet known to be in G1
+// (plk_srs_verify's first two steps): *any with the smallest offending index, flags set on success
+int srs_ensure_g1(plk_srs* srs, bool* any, uint64_t* idx) {
+  hipStream_t s = srs->ctx->stream;
+  const uint64_t n = srs->n;
+  const G1Affine* pts = srs->points.as<G1Affine>();
+  const uint8_t* inf = srs->inf.as<uint8_t>();
+  BadWord bad;
+  uint8_t code;
+  int st;
+  *any = false;
+  if (!srs->points_checked) {
+    if ((st = bad.reset(s))) return st;
+    hipLaunchKernelGGL(k_srs_validate, dim3(blocks_for(n)), dim3(kBlock), 0, s, pts, inf, n, bad.dev());
+    PLK_HIP_TRY(hipGetLastError());
+    if ((st = bad.read(s, any, idx, &code))) return st;
+    if (*any) return PLK_OK;
+    srs->points_checked = true;
+  }
+  if (!srs->subgroup_checked) {
+    if ((st = bad.reset(s))) return st;
+    hipLaunchKernelGGL(k_srs_subgroup, dim3(blocks_for(n)), dim3(kBlock), 0, s, pts, inf, n, bad.dev());
+    PLK_HIP_TRY(hipGetLastError());
+    if ((st = bad.read(s, any, idx, &code))) return st;
+    if (*any) return PLK_OK;
+    srs->subgroup_checked = true;
+  }
+  return PLK_OK;
+}
+
 }  // namespace
 }  // namespace plk
 
@@ -571,6 +655,147 @@ int plk_debug_f2_sqrt(const uint64_t* a, uint64_t* out, int* is_square) {
   *is_square = f2_sqrt(v, r) ? 1 : 0;
   fp_to_abi(r.c0, out);
   fp_to_abi(r.c1, out + 6);
+  return PLK_OK;
+  PLK_S_END
+}
+
+// ---- updating an SRS --------------------------------------------------------------------------
+int plk_opening_key_update(const plk_opening_key* key, const plk_fr* s, plk_opening_key** out, plk_g2* witness) {
+  PLK_S_BEGIN
+  if (!out) return PLK_E_ARG;
+  *out = nullptr;
+  if (!key || !s || !witness) return PLK_E_ARG;
+  const Fr sm = fe_of_abi<FrCfg>(s->l);
+  if (!update_scalar_ok(sm)) return PLK_E_ARG;
+  plk_g2 ph, pb;
+  G2Aff h, bh;
+  int st;
+  if ((st = plk_opening_key_points(key, &ph, &pb))) return st;
+  if ((st = g2_from_abi(ph, h)) || (st = g2_from_abi(pb, bh))) return st;
+  Fr plain = fe_from_mont(sm);
+  const G2Aff nb = g2_mul(bh, plain.v, 8), w = g2_mul(h, plain.v, 8);
+  explicit_bzero(&plain, sizeof plain);
+  plk_g2 pnb;
+  g2_to_abi(nb, &pnb);
+  if ((st = plk_opening_key_load(&ph, &pnb, out))) return st;
+  g2_to_abi(w, witness);
+  return PLK_OK;
+  PLK_S_END
+}
+
+int plk_srs_update(plk_srs* srs, const plk_opening_key* key, const plk_fr* s, plk_srs** out_srs,
+                   plk_opening_key** out_key, plk_g2* witness, uint64_t* bad_index) {
+  PLK_S_BEGIN
+  if (!out_srs || !out_key) return PLK_E_ARG;
+  *out_srs = nullptr;
+  *out_key = nullptr;
+  if (!srs || !key || !witness || srs->n < 2) return PLK_E_ARG;
+  Fr sm;
+  if (s) {
+    sm = fe_of_abi<FrCfg>(s->l);
+    if (!update_scalar_ok(sm)) return PLK_E_ARG;
+  } else {
+    fr_from_entropy(sm);
+  }
+  struct Wipe {  // the host copies of the secret, on every way out
+    Fr& a;
+    plk_fr& b;
+    ~Wipe() {
+      explicit_bzero(&a, sizeof a);
+      explicit_bzero(&b, sizeof b);
+    }
+  };
+  plk_fr s_abi;
+  Wipe wipe{sm, s_abi};
+  fe_to_abi(sm, s_abi.l);
+  plk_ctx* ctx = srs->ctx;
+  DeviceGuard g(ctx->device);
+  hipStream_t st = ctx->stream;
+  const uint64_t n = srs->n;
+  int r;
+  bool any;
+  uint64_t idx;
+  if ((r = srs_ensure_g1(srs, &any, &idx))) return r;  // the split of g1_mul.hip holds on G1 only
+  if (any) {
+    if (bad_index) *bad_index = idx;
+    return PLK_E_ARG;
+  }
+  KeyHolder nk;
+  if ((r = plk_opening_key_update(key, &s_abi, &nk.k, witness))) return r;
+  std::unique_ptr<plk_srs> ns;
+  if ((r = srs_new(ctx, srs->n, ns))) return r;
+  {
+    SecretDevBuf pow;  // s^i, i < n
+    pow.s = st;
+    if ((r = pow.d.alloc(n * sizeof(Fr)))) return r;
+    if ((r = fr_powers_dev(sm, n, pow.d.as<Fr>(), st))) return r;
+    if ((r = g1_mul_dev(ctx, srs->points.as<G1Affine>(), srs->inf.as<uint8_t>(), pow.d.as<Fr>(), n,
+                        ns->points.as<G1Affine>(), ns->inf.as<uint8_t>(), st)))
+      return r;
+  }
+  ns->points_checked = ns->subgroup_checked = true;  // multiples of points of G1
+  if ((r = srs_complete(ns.get()))) return r;
+  *out_srs = ns.release();
+  *out_key = nk.release();
+  return PLK_OK;
+  PLK_S_END
+}
+
+int plk_srs_verify_update(plk_ctx* ctx, const plk_g1* prev_tau_g1, plk_srs* new_srs, const plk_opening_key* new_key,
+                          const plk_g2* witness, const uint8_t seed[32], int* verdict, uint64_t* bad_index) {
+  PLK_S_BEGIN
+  if (!ctx || !prev_tau_g1 || !new_srs || !new_key || !witness || !verdict) return PLK_E_ARG;
+  if (new_srs->ctx != ctx || new_srs->n < 2) return PLK_E_ARG;
+  // the witness as the beta_h of a temporary key on the same H: plk_opening_key_load refuses what
+  // is not canonical, off the twist, outside the r-torsion or the identity
+  plk_g2 ph;
+  KeyHolder tk;
+  int st;
+  if ((st = plk_opening_key_points(new_key, &ph, nullptr))) return st;
+  st = plk_opening_key_load(&ph, witness, &tk.k);
+  if (st == PLK_E_ARG) {
+    *verdict = PLK_SRS_WITNESS;
+    return PLK_OK;
+  }
+  if (st) return st;
+  int v = PLK_SRS_OK;
+  if ((st = plk_srs_verify(ctx, new_srs, new_key, seed, &v, bad_index))) return st;
+  if (v != PLK_SRS_OK) {
+    *verdict = v;
+    return PLK_OK;
+  }
+  // e(new g1[1], H) == e(prev g1[1], [s]H)
+  *verdict = PLK_SRS_LINK;
+  G1In prev;
+  if (g1_from_abi(*prev_tau_g1, prev) != PLK_OK || prev.inf || !g1_in_subgroup(prev.x, prev.y)) return PLK_OK;
+  plk_kzg_pair pair;
+  if ((st = plk_srs_points(new_srs, 1, 1, &pair.c))) return st;
+  pair.w = *prev_tau_g1;
+  int ok = 0;
+  if ((st = plk_pairing_check(tk.k, &pair, &ok))) return st;
+  if (ok) *verdict = PLK_SRS_OK;
+  return PLK_OK;
+  PLK_S_END
+}
+
+int plk_g2_to_bytes(const plk_g2* q, int format, uint8_t* out) {
+  PLK_S_BEGIN
+  if (!q || !out || (format != PLK_G1_COMPRESSED && format != PLK_G1_UNCOMPRESSED)) return PLK_E_ARG;
+  G2Aff a = g2_infinity();
+  int st;
+  if (q->infinity != 1 && (st = g2_from_abi(*q, a))) return st;
+  g2_to_bytes(a, format == PLK_G1_COMPRESSED, out);
+  return PLK_OK;
+  PLK_S_END
+}
+
+int plk_g2_from_bytes(const uint8_t* in, int format, plk_g2* out) {
+  PLK_S_BEGIN
+  if (!in || !out || (format != PLK_G1_COMPRESSED && format != PLK_G1_UNCOMPRESSED)) return PLK_E_ARG;
+  G2Aff a;
+  int st;
+  if ((st = g2_from_bytes(in, format == PLK_G1_COMPRESSED, a))) return st;
+  g2_to_abi(a, out);
   return PLK_OK;
   PLK_S_END
 }

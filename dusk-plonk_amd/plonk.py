@@ -40,6 +40,13 @@ _SRS_IO_SYMBOLS = (
     "plk_opening_key_to_bytes", "plk_debug_srs_weights", "plk_debug_f2_sqrt",
 )
 
+# the entry points of csrc/g1_mul.hip and the SRS update of csrc/srs_io.hip (bound only when the
+# loaded library has them, as above)
+_SRS_UPDATE_SYMBOLS = (
+    "plk_g1_mul_batch", "plk_g1_mul_last_ms", "plk_opening_key_update", "plk_srs_update",
+    "plk_srs_verify_update", "plk_g2_to_bytes", "plk_g2_from_bytes", "plk_debug_glv_split",
+)
+
 # Symbols declared in include/plk.h (checked by tests/test_abi.py)
 ABI_SYMBOLS = (
     "plk_abi_version", "plk_status_str", "plk_build_info", "plk_device_count", "plk_ctx_create",
@@ -85,12 +92,15 @@ ABI_SYMBOLS = (
     "plk_g1_subgroup_check_batch", "plk_proofs_ingest", "plk_ingest_last_ms",
     "plk_verifier_verify_each_bytes",
     *_SRS_IO_SYMBOLS,
+    *_SRS_UPDATE_SYMBOLS,
 )
 
 # per-item status of the ingest calls (include/plk.h PLK_INGEST_*)
 INGEST_OK, INGEST_ENCODING, INGEST_RANGE, INGEST_OFF_CURVE, INGEST_SUBGROUP = range(5)
 # verdicts of PlonkParams.verify (include/plk.h PLK_SRS_*)
 SRS_OK, SRS_POINT, SRS_SUBGROUP, SRS_INFINITY, SRS_GENERATOR, SRS_CHAIN = range(6)
+# and of PlonkParams.verify_update (PLK_SRS_WITNESS / PLK_SRS_LINK)
+SRS_WITNESS, SRS_LINK = 6, 7
 # byte forms of points (include/plk.h PLK_G1_COMPRESSED / PLK_G1_UNCOMPRESSED)
 _FORMATS = {"compressed": 0, "uncompressed": 1}
 
@@ -190,9 +200,17 @@ def _lib():
             "plk_opening_key_to_bytes": (i32, [vp, i32, vp, vp]),
             "plk_debug_srs_weights": (i32, [vp, vp, sz, vp]),
             "plk_debug_f2_sqrt": (i32, [vp, vp, C.POINTER(i32)]),
+            "plk_g1_mul_batch": (i32, [vp, vp, vp, sz, i32, vp]),
+            "plk_g1_mul_last_ms": (i32, [vp, C.POINTER(C.c_float)]),
+            "plk_opening_key_update": (i32, [vp, vp, pp, vp]),
+            "plk_srs_update": (i32, [vp, vp, vp, pp, pp, vp, C.POINTER(u64)]),
+            "plk_srs_verify_update": (i32, [vp, vp, vp, vp, vp, vp, C.POINTER(i32), C.POINTER(u64)]),
+            "plk_g2_to_bytes": (i32, [vp, i32, vp]),
+            "plk_g2_from_bytes": (i32, [vp, i32, vp]),
+            "plk_debug_glv_split": (i32, [vp, vp, sz, vp]),
         }
         for name, (res, args) in sig.items():
-            if name in _SRS_IO_SYMBOLS and not hasattr(lib, name):
+            if name in _SRS_IO_SYMBOLS + _SRS_UPDATE_SYMBOLS and not hasattr(lib, name):
                 continue  # a PLK_LIB build from before srs_io.hip still loads; a use fails loudly
             f = getattr(lib, name)
             f.restype, f.argtypes = res, args
@@ -609,6 +627,75 @@ def g1_subgroup_check(points, ctx: "Context | None" = None) -> np.ndarray:
     return ok[:pts.shape[0]].astype(bool)
 
 
+def g1_mul(points, scalars, assume_subgroup: bool = False, ctx: "Context | None" = None) -> np.ndarray:
+    """out[i] = [scalars[i]] points[i] as uint64[n, 13], one point and one scalar per GPU lane
+    (plk_g1_mul_batch). points: ABI rows uint64[n, 13], scalars: Montgomery Fr uint64[n, 4].
+    assume_subgroup=False tests every point for order r first and raises PlonkError(PLK_E_ARG)
+    for a non-member; True: the caller vouches for membership. PLK_E_ARG also for a non-canonical
+    or off-curve point, an infinity word other than 0 / 1 and a scalar >= r."""
+    ctx = ctx or Context.default()
+    pts = np.ascontiguousarray(np.asarray(points, dtype=np.uint64).reshape(-1, 13))
+    vals = np.ascontiguousarray(np.asarray(scalars, dtype=np.uint64).reshape(-1, 4))
+    if pts.shape[0] != vals.shape[0]:
+        raise ValueError("g1_mul: as many scalars as points")
+    out = np.zeros((max(1, pts.shape[0]), 13), dtype=np.uint64)
+    _check(_lib().plk_g1_mul_batch(ctx.handle, _ptr(pts), _ptr(vals), pts.shape[0],
+                                   int(bool(assume_subgroup)), _ptr(out)), "g1_mul")
+    return out[:pts.shape[0]]
+
+
+def g1_mul_last_ms(ctx: "Context | None" = None) -> float:
+    """Milliseconds of the multiplication kernel of the most recent g1_mul / PlonkParams.update
+    on the context (HIP events)."""
+    ctx = ctx or Context.default()
+    a = C.c_float()
+    _check(_lib().plk_g1_mul_last_ms(ctx.handle, C.byref(a)), "plk_g1_mul_last_ms")
+    return a.value
+
+
+def debug_glv_split(scalars, ctx: "Context | None" = None) -> np.ndarray:
+    """Test support (plk_debug_glv_split): uint64[n, 4] rows a_lo, a_hi, b_lo, b_hi of the split of
+    each Montgomery scalar uint64[n, 4]. ctx = None: the host mirror; otherwise the device function."""
+    vals = np.ascontiguousarray(np.asarray(scalars, dtype=np.uint64).reshape(-1, 4))
+    out = np.zeros((max(1, vals.shape[0]), 4), dtype=np.uint64)
+    _check(_lib().plk_debug_glv_split(ctx.handle if ctx is not None else None, _ptr(vals), vals.shape[0],
+                                      _ptr(out)), "plk_debug_glv_split")
+    return out[:vals.shape[0]]
+
+
+def g2_to_bytes(point, fmt: str = "compressed") -> bytes:
+    """One G2 point uint64[25] (a witness) in zkcrypto's byte form: 96 bytes compressed, 192
+    uncompressed (plk_g2_to_bytes, host only)."""
+    q = np.ascontiguousarray(np.asarray(point, dtype=np.uint64).reshape(G2_WORDS))
+    out = np.zeros(96 if _FORMATS[fmt] == 0 else 192, dtype=np.uint8)
+    _check(_lib().plk_g2_to_bytes(_ptr(q), _FORMATS[fmt], _ptr(out)), "plk_g2_to_bytes")
+    return out.tobytes()
+
+
+def g2_from_bytes(blob, fmt: str = "compressed") -> np.ndarray:
+    """The inverse: strict decoding to uint64[25] (plk_g2_from_bytes); the subgroup check is the
+    consumer's (PlonkParams.verify_update makes it)."""
+    size = 96 if _FORMATS[fmt] == 0 else 192
+    raw = np.frombuffer(bytes(blob), dtype=np.uint8)
+    if raw.size != size:
+        raise PlonkError(PLK_E_ARG, f"g2_from_bytes: {size} bytes")
+    out = np.zeros(G2_WORDS, dtype=np.uint64)
+    _check(_lib().plk_g2_from_bytes(_ptr(raw), _FORMATS[fmt], _ptr(out)), "plk_g2_from_bytes")
+    return out
+
+
+def _fr_limbs(s) -> np.ndarray:
+    """A canonical int or uint64[4] Montgomery limbs -> uint64[4] Montgomery limbs (an int is NOT
+    reduced: a value >= r reaches the library as it is and is refused there)."""
+    if isinstance(s, (int, np.integer)):
+        v = int(s)
+        m = v * (1 << 256) % _FR_MOD if 0 <= v < _FR_MOD else v
+        if m >> 256:
+            raise PlonkError(PLK_E_ARG, "a scalar is below 2^256")
+        return np.array([(m >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)], dtype=np.uint64)
+    return np.ascontiguousarray(np.asarray(s, dtype=np.uint64).reshape(4))
+
+
 def ingest_last_ms(ctx: "Context | None" = None):
     """(decompress kernel ms, subgroup kernel ms) of the most recent ingest call on the context."""
     ctx = ctx or Context.default()
@@ -625,8 +712,12 @@ def _seed32(seed) -> np.ndarray:
 
 
 class SrsVerdict:
-    """Result of PlonkParams.verify: ok, verdict (an SRS_* class) and bad_index (the smallest
-    offending index for SRS_POINT / SRS_SUBGROUP / SRS_INFINITY, else None)."""
+    """Result of PlonkParams.verify / verify_update: ok, verdict (an SRS_* class; SRS_WITNESS and
+    SRS_LINK come from verify_update alone) and bad_index (the smallest offending index for
+    SRS_POINT / SRS_SUBGROUP / SRS_INFINITY, else None)."""
+
+    NAMES = {SRS_OK: "ok", SRS_POINT: "point", SRS_SUBGROUP: "subgroup", SRS_INFINITY: "infinity",
+             SRS_GENERATOR: "generator", SRS_CHAIN: "chain", SRS_WITNESS: "witness", SRS_LINK: "link"}
 
     def __init__(self, ok: bool, verdict: int, bad_index: int | None):
         self.ok, self.verdict, self.bad_index = ok, verdict, bad_index
@@ -635,7 +726,8 @@ class SrsVerdict:
         return self.ok
 
     def __repr__(self):
-        return f"SrsVerdict(ok={self.ok}, verdict={self.verdict}, bad_index={self.bad_index})"
+        return (f"SrsVerdict(ok={self.ok}, verdict={self.verdict} "
+                f"({self.NAMES.get(self.verdict, '?')}), bad_index={self.bad_index})")
 
 
 def srs_last_load_ms(ctx: "Context | None" = None):
@@ -745,6 +837,40 @@ class PlonkParams:
         sd = None if seed is None else _ptr(_seed32(seed))
         _check(_lib().plk_srs_verify(self.ctx.handle, self._h, opening_key._h, sd, C.byref(verdict),
                                      C.byref(idx)), "plk_srs_verify")
+        bad = idx.value if verdict.value in (SRS_POINT, SRS_SUBGROUP, SRS_INFINITY) else None
+        return SrsVerdict(verdict.value == SRS_OK, verdict.value, bad)
+
+    def update(self, opening_key: "OpeningKey", s=None):
+        """Contribute to this SRS: (new PlonkParams, new OpeningKey, witness) with g1'[i] =
+        [s^i] g1[i], beta_h' = [s] beta_h and witness = [s]H as uint64[25] (plk_srs_update). s = None
+        draws the secret from OS entropy inside the library, which wipes it before returning
+        (best effort): the form meant for use. An explicit s (a canonical int or Montgomery limbs)
+        is for tests. PlonkError(PLK_E_ARG) for s = 0, s >= r, fewer than 2 points, or a point
+        that is not on the curve or not in G1 (bad_index then names the smallest such index)."""
+        sp = None if s is None else _ptr(_fr_limbs(s))
+        h, k, idx = C.c_void_p(), C.c_void_p(), C.c_uint64(0xFFFFFFFFFFFFFFFF)
+        wit = np.zeros(G2_WORDS, dtype=np.uint64)
+        st = _lib().plk_srs_update(self._h, opening_key._h, sp, C.byref(h), C.byref(k), _ptr(wit),
+                                   C.byref(idx))
+        if st == PLK_E_ARG and idx.value != 0xFFFFFFFFFFFFFFFF:
+            raise PlonkError(st, f"plk_srs_update: point {idx.value} is not a point of G1",
+                             bad_index=idx.value)
+        _check(st, "plk_srs_update")
+        return PlonkParams(h, self.n, self.ctx), OpeningKey(k), wit
+
+    def verify_update(self, prev_tau_g1, opening_key: "OpeningKey", witness,
+                      seed: bytes | None = None) -> "SrsVerdict":
+        """Is this SRS with `opening_key` a well-formed SRS whose tau is the previous string's
+        times the secret behind `witness`? prev_tau_g1: points()[1] of the string that was updated
+        (uint64[13]). plk_srs_verify_update: SRS_WITNESS, then every class of verify(), then
+        SRS_LINK. A bad update is a verdict, never an exception."""
+        prev = np.ascontiguousarray(np.asarray(prev_tau_g1, dtype=np.uint64).reshape(13))
+        wit = np.ascontiguousarray(np.asarray(witness, dtype=np.uint64).reshape(G2_WORDS))
+        verdict, idx = C.c_int(-1), C.c_uint64(0xFFFFFFFFFFFFFFFF)
+        sd = None if seed is None else _ptr(_seed32(seed))
+        _check(_lib().plk_srs_verify_update(self.ctx.handle, _ptr(prev), self._h, opening_key._h,
+                                            _ptr(wit), sd, C.byref(verdict), C.byref(idx)),
+               "plk_srs_verify_update")
         bad = idx.value if verdict.value in (SRS_POINT, SRS_SUBGROUP, SRS_INFINITY) else None
         return SrsVerdict(verdict.value == SRS_OK, verdict.value, bad)
 
@@ -933,6 +1059,15 @@ class OpeningKey:
         _check(_lib().plk_opening_key_load_bytes(_ptr(a), _ptr(b), _FORMATS[fmt], C.byref(out)),
                "OpeningKey::from_bytes")
         return cls(out)
+
+    def update(self, s):
+        """(new OpeningKey, witness): the same H with beta_h' = [s] beta_h, and witness = [s]H as
+        uint64[25] (plk_opening_key_update, host only). s: a canonical int or Montgomery limbs;
+        PlonkError(PLK_E_ARG) for 0 or a value >= r."""
+        out, wit = C.c_void_p(), np.zeros(G2_WORDS, dtype=np.uint64)
+        _check(_lib().plk_opening_key_update(self._h, _ptr(_fr_limbs(s)), C.byref(out), _ptr(wit)),
+               "plk_opening_key_update")
+        return OpeningKey(out), wit
 
     def to_bytes(self, fmt: str = "compressed"):
         """(H, beta_h) in zkcrypto's G2 byte form (plk_opening_key_to_bytes)."""

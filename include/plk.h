@@ -653,7 +653,71 @@ int plk_opening_key_load_bytes(const uint8_t* h, const uint8_t* beta_h, int form
                                plk_opening_key** out);
 int plk_opening_key_to_bytes(const plk_opening_key* key, int format, uint8_t* h, uint8_t* beta_h);
 
+/* ---- Updating an SRS (csrc/g1_mul.hip, csrc/srs_io.hip) ------------------------------------
+ * PLONK's reference string is updatable: anyone may multiply a fresh secret s into it, g1'[i] =
+ * [s^i] g1[i] and beta_h' = [s] beta_h, and the result is sound if one contributor was honest. The
+ * contributor publishes the witness [s]H (the shape of the Ethereum KZG ceremony's pot_pubkey),
+ * from which anyone can check that the new string is the old one times the witness's secret.
+ *
+ * The primitive under it is a batched variable-base scalar multiplication, one point and one
+ * scalar per lane: the scalar is split on the device into two positive 128-bit halves by the
+ * endomorphism of the subgroup test, and one chain of 128 doublings and at most 128
+ * mixed additions runs on the redundant-limb field. The split is only valid on G1. */
+/* out[i] = [scalars[i]] points[i], canonical affine; host buffers, one call at a time per context;
+ * n = 0 is PLK_OK. Scalars are Montgomery Fr, a scalar >= r is PLK_E_ARG. Points follow the rules
+ * of plk_msm_points: a non-canonical or off-curve finite point or an infinity word other than
+ * 0 / 1 is PLK_E_ARG. assume_subgroup = 0 runs the subgroup kernel first
+ * (plk_g1_subgroup_check_batch) and refuses a non-member with PLK_E_ARG; assume_subgroup = 1: the
+ * caller vouches for membership (for a point outside G1 the result is then unspecified). Identity
+ * inputs and zero scalars are legal and give the identity (x = y = 0, infinity = 1). */
+int plk_g1_mul_batch(plk_ctx* ctx, const plk_g1* points, const plk_fr* scalars, size_t n,
+                     int assume_subgroup, plk_g1* out);
+/* HIP events around the multiplication kernel of the last plk_g1_mul_batch or plk_srs_update on
+ * this context (milliseconds; measurement only). */
+int plk_g1_mul_last_ms(plk_ctx* ctx, float* kernel_ms);
+/* Host only. A new key with the same H and beta_h' = [s] beta_h; *witness = [s]H. s = 0 or s >= r
+ * (Montgomery form) is PLK_E_ARG. */
+int plk_opening_key_update(const plk_opening_key* key, const plk_fr* s, plk_opening_key** out,
+                           plk_g2* witness);
+/* A NEW SRS on the context of `srs` with g1'[0] = G and g1'[i] = [s^i] g1[i], MSM-ready as one from
+ * plk_srs_load, with the updated opening key and the witness; the input SRS and key are untouched.
+ * The powers s^i are formed on the device. s = NULL draws 64 bytes from getrandom, reduces them
+ * mod r and redraws on 0: the form meant for use, the secret never leaves the library. The secret
+ * and what is derived from it are wiped on a BEST EFFORT basis before the call returns: the host
+ * copies with explicit_bzero, the device array of powers with hipMemsetAsync before it is freed;
+ * registers, kernel arguments and the allocator's pages are beyond the library's reach. An
+ * explicit s is for tests and callers with their own entropy. The new SRS is known to be
+ * canonical, on the curve and in G1 (its plk_srs_verify skips those passes). When the input SRS
+ * is not known to be in G1 (one from plk_srs_load or plk_srs_setup), the canonical / on-curve pass
+ * and the subgroup kernel run first: a bad point is PLK_E_ARG with *out_srs = NULL and *bad_index
+ * (nullable) the smallest offending index, as plk_srs_load_bytes. PLK_E_ARG also for fewer than 2
+ * points, s = 0 and s >= r. One call at a time per context. */
+int plk_srs_update(plk_srs* srs, const plk_opening_key* key, const plk_fr* s, plk_srs** out_srs,
+                   plk_opening_key** out_key, plk_g2* witness, uint64_t* bad_index);
+#define PLK_SRS_WITNESS 6 /* the witness is malformed, outside the r-torsion or the identity */
+#define PLK_SRS_LINK 7    /* e(new g1[1], H) != e(prev g1[1], witness), or a bad prev g1[1] */
+/* Is new_srs with new_key a well-formed SRS whose tau is (the previous string's tau) * s for the s
+ * behind `witness`? prev_tau_g1 is g1[1] of the string that was updated. In order: the witness is
+ * canonical, on the twist, of order r and not the identity (else PLK_SRS_WITNESS); every class of
+ * plk_srs_verify(new_srs, new_key, seed) with its verdicts and *bad_index; one host
+ * plk_pairing_check of e(new g1[1], H) = e(prev_tau_g1, witness) on the temporary key (H,
+ * witness), where a malformed, non-member or identity prev_tau_g1 is PLK_SRS_LINK too. The first
+ * failing class wins. A bad update is a verdict, not an error: only NULL pointers, fewer than 2
+ * points or an SRS of another context are PLK_E_ARG. */
+int plk_srs_verify_update(plk_ctx* ctx, const plk_g1* prev_tau_g1, plk_srs* new_srs,
+                          const plk_opening_key* new_key, const plk_g2* witness,
+                          const uint8_t seed[32], int* verdict, uint64_t* bad_index);
+/* One bare G2 point (a witness) in zkcrypto's byte forms, as the opening key's: 96 bytes
+ * compressed, 192 uncompressed. Host only; decoding is strict (the subgroup check is the
+ * consumer's: plk_srs_verify_update makes it). */
+int plk_g2_to_bytes(const plk_g2* q, int format, uint8_t* out);
+int plk_g2_from_bytes(const uint8_t* in, int format, plk_g2* out);
+
 /* ---- test support ---------------------------------------------------------------- */
+/* The scalar split of csrc/g1_mul.hip: out[4 i .. 4 i + 3] = a_lo, a_hi, b_lo, b_hi of scalar i
+ * (canonical Montgomery; otherwise PLK_E_ARG) with a = z - (k mod z), b = floor(k / z) + 1.
+ * ctx = NULL: the host mirror; otherwise the device function the kernel calls. */
+int plk_debug_glv_split(plk_ctx* ctx, const plk_fr* s, size_t n, uint64_t* out);
 /* out[i] = the weight rho_i of plk_srs_fold for an SRS of n points and this seed, i < n - 1
  * (canonical Montgomery). ctx = NULL: computed on the host (the mirror of the kernel). */
 int plk_debug_srs_weights(plk_ctx* ctx, const uint8_t seed[32], size_t n, plk_fr* out);
