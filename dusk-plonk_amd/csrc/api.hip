@@ -3,10 +3,12 @@
 // exception or HIP abort crosses the boundary (the reference propagates commit errors
 // with `?`, prover.rs:133-452, and treats NTT as infallible).
 #include <hip/hip_runtime.h>
+#include <sys/random.h>
 
 #include <cstring>
 #include <algorithm>
 #include <new>
+#include <random>
 #include <thread>
 #include <vector>
 
@@ -20,30 +22,23 @@ hipError_t& last_hip_error() {
   static thread_local hipError_t e = hipSuccess;
   return e;
 }
+
+void os_entropy(uint8_t seed[32]) {
+  size_t got = 0;
+  while (got < 32) {
+    const ssize_t r = getrandom(seed + got, 32 - got, 0);
+    if (r <= 0) break;
+    got += (size_t)r;
+  }
+  if (got < 32) {
+    std::random_device rd;
+    for (size_t i = 0; i < 32; i += 4) {
+      const uint32_t x = rd();
+      std::memcpy(seed + i, &x, 4);
+    }
+  }
+}
 }  // namespace plk
-
-#define PLK_API_BEGIN try {
-#define PLK_API_END                 \
-  }                                 \
-  catch (const std::bad_alloc&) {   \
-    return PLK_E_OOM;               \
-  }                                 \
-  catch (...) {                     \
-    return PLK_E_DEVICE;            \
-  }
-
-static inline void fr_to_abi(const Fr& a, plk_fr* out) {
-  for (int i = 0; i < 4; ++i) out->l[i] = (uint64_t)a.v[2 * i] | ((uint64_t)a.v[2 * i + 1] << 32);
-}
-
-static inline Fr fr_from_abi(const plk_fr* a) {
-  Fr r;
-  for (int i = 0; i < 4; ++i) {
-    r.v[2 * i] = (uint32_t)a->l[i];
-    r.v[2 * i + 1] = (uint32_t)(a->l[i] >> 32);
-  }
-  return r;
-}
 
 extern "C" {
 
@@ -144,11 +139,11 @@ int plk_domain_info(const plk_domain* d, uint64_t* size, plk_fr* generator, plk_
                     plk_fr* size_inv, plk_fr* coset, plk_fr* coset_inv) {
   if (!d) return PLK_E_ARG;
   if (size) *size = d->n;
-  if (generator) fr_to_abi(d->omega, generator);
-  if (generator_inv) fr_to_abi(d->omega_inv, generator_inv);
-  if (size_inv) fr_to_abi(d->n_inv, size_inv);
-  if (coset) fr_to_abi(d->g, coset);
-  if (coset_inv) fr_to_abi(d->g_inv, coset_inv);
+  if (generator) *generator = fr_to_abi(d->omega);
+  if (generator_inv) *generator_inv = fr_to_abi(d->omega_inv);
+  if (size_inv) *size_inv = fr_to_abi(d->n_inv);
+  if (coset) *coset = fr_to_abi(d->g);
+  if (coset_inv) *coset_inv = fr_to_abi(d->g_inv);
   return PLK_OK;
 }
 
@@ -262,18 +257,6 @@ static int srs_alloc(plk_ctx* ctx, size_t n, std::unique_ptr<plk_srs>& s) {
   return PLK_OK;
 }
 
-static void g1_to_abi(const G1Affine& a, uint8_t inf, plk_g1* out) {
-  if (inf) {
-    std::memset(out, 0, sizeof(*out));
-    out->infinity = 1;
-    return;
-  }
-  for (int i = 0; i < 6; ++i) {
-    out->x[i] = (uint64_t)a.x.v[2 * i] | ((uint64_t)a.x.v[2 * i + 1] << 32);
-    out->y[i] = (uint64_t)a.y.v[2 * i] | ((uint64_t)a.y.v[2 * i + 1] << 32);
-  }
-  out->infinity = 0;
-}
 
 int plk_srs_points(const plk_srs* s, size_t start, size_t count, plk_g1* out) {
   PLK_API_BEGIN
@@ -287,7 +270,7 @@ int plk_srs_points(const plk_srs* s, size_t start, size_t count, plk_g1* out) {
                              hipMemcpyDeviceToHost, st));
   PLK_HIP_TRY(hipMemcpyAsync(inf.data(), s->inf.as<uint8_t>() + start, count, hipMemcpyDeviceToHost, st));
   PLK_HIP_TRY(stream_wait(st));
-  for (size_t i = 0; i < count; ++i) g1_to_abi(pts[i], inf[i], &out[i]);
+  for (size_t i = 0; i < count; ++i) g1_store(pts[i].x, pts[i].y, !inf[i], &out[i]);
   return PLK_OK;
   PLK_API_END
 }
@@ -314,7 +297,7 @@ int plk_srs_setup_range(plk_ctx* ctx, const plk_fr* tau, uint64_t start, size_t 
   std::unique_ptr<plk_srs> s;
   int st;
   if ((st = srs_alloc(ctx, n_points, s))) return st;
-  if ((st = srs_generate(s.get(), fr_from_abi(tau), start, ctx->stream))) return st;
+  if ((st = srs_generate(s.get(), fr_from_abi(*tau), start, ctx->stream))) return st;
   if ((st = srs_finish(s.get()))) return st;
   if (out_points && (st = plk_srs_points(s.get(), 0, n_points, out_points))) return st;
   *out = s.release();
@@ -332,15 +315,13 @@ int plk_srs_load(plk_ctx* ctx, const plk_g1* points, size_t n_points, plk_srs** 
   if ((st = srs_alloc(ctx, n_points, s))) return st;
   std::vector<G1Affine> pts(n_points);
   std::vector<uint8_t> inf(n_points);
+  // taken on faith (plk_srs_verify checks an SRS): any non-zero infinity word is the identity,
+  // stored as (0, 0)
   for (size_t i = 0; i < n_points; ++i) {
-    inf[i] = points[i].infinity ? 1 : 0;
-    for (int k = 0; k < 6; ++k) {
-      const uint64_t x = inf[i] ? 0 : points[i].x[k], y = inf[i] ? 0 : points[i].y[k];
-      pts[i].x.v[2 * k] = (uint32_t)x;
-      pts[i].x.v[2 * k + 1] = (uint32_t)(x >> 32);
-      pts[i].y.v[2 * k] = (uint32_t)y;
-      pts[i].y.v[2 * k + 1] = (uint32_t)(y >> 32);
-    }
+    const G1Abi p = g1_load<false>(&points[i]);
+    inf[i] = p.inf ? 1 : 0;
+    pts[i].x = p.inf ? fe_zero<FpCfg>() : p.x;
+    pts[i].y = p.inf ? fe_zero<FpCfg>() : p.y;
   }
   PLK_HIP_TRY(hipMemcpy(s->points.ptr, pts.data(), n_points * sizeof(G1Affine), hipMemcpyHostToDevice));
   PLK_HIP_TRY(hipMemcpy(s->inf.ptr, inf.data(), n_points, hipMemcpyHostToDevice));
@@ -464,19 +445,12 @@ int plk_g1_sum(const plk_g1* points, size_t n, plk_g1* out) {
   if (!out || (!points && n)) return PLK_E_ARG;
   G1xyzz acc = xyzz_infinity();
   for (size_t i = 0; i < n; ++i) {
-    if (points[i].infinity) continue;
-    Fp x, y;
-    for (int k = 0; k < 6; ++k) {
-      x.v[2 * k] = (uint32_t)points[i].x[k];
-      x.v[2 * k + 1] = (uint32_t)(points[i].x[k] >> 32);
-      y.v[2 * k] = (uint32_t)points[i].y[k];
-      y.v[2 * k + 1] = (uint32_t)(points[i].y[k] >> 32);
-    }
-    acc = xyzz_add_affine(acc, x, y);
+    const G1Abi p = g1_load<false>(&points[i]);
+    if (!p.inf) acc = xyzz_add_affine(acc, p.x, p.y);
   }
-  G1Affine r;
-  const bool fin = xyzz_to_affine(acc, r.x, r.y);
-  g1_to_abi(r, fin ? 0 : 1, out);
+  Fp x, y;
+  const bool fin = xyzz_to_affine(acc, x, y);
+  g1_store(x, y, fin, out);
   return PLK_OK;
   PLK_API_END
 }

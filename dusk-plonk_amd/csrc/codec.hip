@@ -34,43 +34,13 @@ uint64_t get_u64(const uint8_t* p) {
   return v;
 }
 
-// limbs (LE u64) < modulus (LE u32 words)
-template <class C>
-bool canonical(const uint64_t* l) {
-  for (int i = C::N - 1; i >= 0; --i) {
-    const uint32_t w = (uint32_t)(l[i / 2] >> (32 * (i % 2)));
-    if (w != C::P[i]) return w < C::P[i];
-  }
-  return false;  // equal to the modulus
-}
-
 bool is_zero6(const uint64_t* l) {
   for (int i = 0; i < 6; ++i)
     if (l[i]) return false;
   return true;
 }
 // Montgomery one of Fp (R mod p), as LE u64 limbs
-bool is_fp_one(const uint64_t* l) {
-  const Fp one = fe_one<FpCfg>();
-  for (int i = 0; i < 6; ++i)
-    if (l[i] != ((uint64_t)one.v[2 * i] | ((uint64_t)one.v[2 * i + 1] << 32))) return false;
-  return true;
-}
-
-template <class C>
-Fe<C> fe_of(const uint64_t* l) {
-  Fe<C> r;
-  for (int i = 0; i < C::N; ++i) r.v[i] = (uint32_t)(l[i / 2] >> (32 * (i % 2)));
-  return r;
-}
-
-bool on_curve(const plk_g1& g) {
-  const Fp x = fe_of<FpCfg>(g.x), y = fe_of<FpCfg>(g.y);
-  Fp four = fe_zero<FpCfg>();
-  four.v[0] = 4;
-  four = fe_to_mont(four);
-  return fe_eq(fe_sqr(y), fe_add(fe_mul(fe_sqr(x), x), four));
-}
+bool is_fp_one(const uint64_t* l) { return fe_eq(fe_of_abi<FpCfg>(l), fe_one<FpCfg>()); }
 
 // field order of proof.rs:39-66 / plk_proof
 plk_g1 plk_proof::* const kCommField[kComms] = {
@@ -126,7 +96,7 @@ int plk_proof_decode(const uint8_t* in, size_t len, plk_proof* proof) {
     for (int k = 0; k < 6; ++k) g->y[k] = get_u64(q + 48 + 8 * k);
     if (q[96] > 1) return PLK_E_ARG;
     g->infinity = q[96];
-    if (!canonical<FpCfg>(g->x) || !canonical<FpCfg>(g->y)) return PLK_E_ARG;
+    if (!abi_canonical<FpCfg>(g->x) || !abi_canonical<FpCfg>(g->y)) return PLK_E_ARG;
     if (g->infinity) {
       // the identity's two known encodings: (0, 0, true) (this encoder) and (0, one, true)
       // (zkcrypto-style crates); any other coordinates under the flag are rejected, so
@@ -134,7 +104,7 @@ int plk_proof_decode(const uint8_t* in, size_t len, plk_proof* proof) {
       if (!is_zero6(g->x) || !(is_zero6(g->y) || is_fp_one(g->y))) return PLK_E_ARG;
       std::memset(g->x, 0, sizeof g->x);
       std::memset(g->y, 0, sizeof g->y);
-    } else if (!on_curve(*g)) {
+    } else if (!g1_on_curve(fe_of_abi<FpCfg>(g->x), fe_of_abi<FpCfg>(g->y))) {
       return PLK_E_ARG;
     }
     q += kG1Bytes;
@@ -142,7 +112,7 @@ int plk_proof_decode(const uint8_t* in, size_t len, plk_proof* proof) {
   for (size_t i = 0; i < kEvals; ++i) {
     plk_fr* f = eval(&p, i);
     for (int k = 0; k < 4; ++k) f->l[k] = get_u64(q + 8 * k);
-    if (!canonical<FrCfg>(f->l)) return PLK_E_ARG;
+    if (!abi_canonical<FrCfg>(f->l)) return PLK_E_ARG;
     q += kFrBytes;
   }
   *proof = p;

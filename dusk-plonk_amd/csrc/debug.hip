@@ -293,15 +293,6 @@ enum : int {
   kStLinComb, kStScalePowers, kStRuffini, kStCount
 };
 
-Fr fr_from_abi(const plk_fr& a) {
-  Fr r;
-  for (int i = 0; i < 4; ++i) {
-    r.v[2 * i] = (uint32_t)a.l[i];
-    r.v[2 * i + 1] = (uint32_t)(a.l[i] >> 32);
-  }
-  return r;
-}
-
 struct StageCall {
   int stage;
   const uint64_t* const* in;

@@ -1,7 +1,8 @@
 // g1_mul.hip — batched variable-base scalar multiplication on G1, one point and one 255-bit
 // scalar per lane (include/plk.h "Updating an SRS"): out[i] = [k_i] P_i.
 //
-// The endomorphism of the subgroup test (ingest_math.hpp): psi(x, y) = (beta x, y) = [-z] P on G1
+// The endomorphism of the subgroup test (ingest_math.hpp g1_in_subgroup, beta from abi.hpp):
+// psi(x, y) = (beta x, y) = [-z] P on G1
 // with z = x0^2 = 0xac45a4010001a4020000000100000000 and r = z^2 - z + 1. For k in [0, r):
 //     a = z - (k mod z)  in [1, z],    b = floor(k / z) + 1  in [1, z]   ((r - 1) / z = z - 1),
 //     a - b z = -k,  so  [k] P = -(a P + b psi P) = a (-P) + b (-psi P).
@@ -34,7 +35,6 @@
 #include <vector>
 
 #include "g1r.hpp"
-#include "ingest_math.hpp"
 #include "internal.hpp"
 #include "msm_common.hpp"
 
@@ -50,8 +50,6 @@ namespace {
 constexpr int kBlock = 64;  // one wave per block, as the ingest kernels
 constexpr uint64_t kZLo = 0x0000000100000000ull, kZHi = 0xac45a4010001a402ull;  // z = x0^2
 constexpr size_t kMaxBatch = (size_t)1 << 26;
-
-inline uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + kBlock - 1) / kBlock); }
 
 // k: a canonical scalar in plain form (not Montgomery). a = z - (k mod z), b = floor(k / z) + 1,
 // each as (lo, hi) 64-bit words. k < r < 2^255 and z > 2^127, so the top 127 bits of k are already
@@ -91,15 +89,8 @@ __device__ __forceinline__ RFp rfp_select(bool c, const RFp& a, const RFp& b) {
   return r;
 }
 
-// an R'-domain value in [0, 2p) -> canonical packed R-domain: times 2^-(BL - 384) (msm.hip
-// fp_rx_to_r)
-__device__ __forceinline__ Fp rfp_to_r(const RFp& v) {
-  constexpr int SH = RxShape<FpCfg>::B * RxShape<FpCfg>::L - 32 * FpCfg::N;
-  static_assert(SH > 0 && SH < 32, "R' / R shift");
-  Fp k = fe_zero<FpCfg>();
-  k.v[11] = 1u << (32 - SH);  // 2^(384 - SH) (< p)
-  return fe_mul(rx_pack_canonical(v), k);
-}
+// an R'-domain value in [0, 2p) -> canonical packed R-domain
+__device__ __forceinline__ Fp rfp_to_r(const RFp& v) { return fp_rx_to_r(rx_pack_canonical(v)); }
 
 // temp[t] = [scalars[t]] pts[t] (XYZZ, canonical R-domain; ZZ = 0 for the identity). pts: affine
 // R-domain points of G1, inf their identity flags, scalars canonical Montgomery.
@@ -156,25 +147,16 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(2, 
   st_xyzz(&temp[t], o);
 }
 
-// ABI points -> the affine layout and identity flags; *bad = 1 for an infinity word other than
-// 0 / 1 or a finite point that is not canonical or not on the curve (plk_msm_points' rules)
+// ABI points -> the affine layout and identity flags; *bad = 1 for a point g1_load<true> refuses
 __global__ void __launch_bounds__(kBlock) k_g1_mul_load(const plk_g1* __restrict__ in, uint64_t n,
                                                         G1Affine* __restrict__ pts, uint8_t* __restrict__ inf,
                                                         uint32_t* __restrict__ bad) {
   const uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   if (t >= n) return;
-  const uint64_t* src = reinterpret_cast<const uint64_t*>(in + t);
-  Fp x = fe_zero<FpCfg>(), y = fe_zero<FpCfg>();
-  bool ok = src[12] <= 1;
-  const bool is_inf = src[12] != 0;
-  if (!is_inf) {
-    x = fe_of_abi<FpCfg>(src);
-    y = fe_of_abi<FpCfg>(src + 6);
-    ok = fe_canonical(x) && fe_canonical(y) && g1_on_curve(x, y);
-  }
-  st_aff(&pts[t], x, y);
-  inf[t] = is_inf ? 1 : 0;
-  if (!ok) *bad = 1;
+  const G1Abi p = g1_load<true>(in + t);
+  st_aff(&pts[t], p.x, p.y);
+  inf[t] = p.inf ? 1 : 0;
+  if (!p.ok) *bad = 1;
 }
 
 // out[i] = s^i (Montgomery), i < n
@@ -200,19 +182,6 @@ __global__ void __launch_bounds__(kBlock) k_glv_split(const Fr* __restrict__ sca
   out[4 * t + 3] = b[1];
 }
 
-struct EventPair {
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  int create() {
-    PLK_HIP_TRY(hipEventCreate(&e0));
-    PLK_HIP_TRY(hipEventCreate(&e1));
-    return PLK_OK;
-  }
-  ~EventPair() {
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-  }
-};
-
 }  // namespace
 
 // out[i] = [scal[i]] pts[i] in canonical affine form with identity flags; every pointer a device
@@ -221,19 +190,19 @@ struct EventPair {
 int g1_mul_dev(plk_ctx* ctx, const G1Affine* pts, const uint8_t* inf, const Fr* scal, uint64_t n,
                G1Affine* out, uint8_t* out_inf, hipStream_t s) {
   DevBuf temp, pref;
-  EventPair ev;
+  TimingEvents<2> ev;
   int st;
   if ((st = temp.alloc(n * sizeof(G1xyzz)))) return st;
   if ((st = pref.alloc(n * sizeof(Fp)))) return st;
   if ((st = ev.create())) return st;
   // the events are stamped by the dispatch itself (as k_accumulate's): the kernel alone
-  hipExtLaunchKernelGGL(k_g1_mul, dim3(blocks_for(n)), dim3(kBlock), 0, s, ev.e0, ev.e1, 0, pts, inf, scal, n,
+  hipExtLaunchKernelGGL(k_g1_mul, dim3(cdiv(n, kBlock)), dim3(kBlock), 0, s, ev.e[0], ev.e[1], 0, pts, inf, scal, n,
                         temp.as<G1xyzz>());
   PLK_HIP_TRY(hipGetLastError());
   if ((st = srs_batch_affine(temp.as<G1xyzz>(), n, pref.as<Fp>(), out, out_inf, s))) return st;
   PLK_HIP_TRY(stream_wait(s));
   ctx->g1_mul_ms = 0.f;
-  (void)hipEventElapsedTime(&ctx->g1_mul_ms, ev.e0, ev.e1);
+  (void)hipEventElapsedTime(&ctx->g1_mul_ms, ev.e[0], ev.e[1]);
   return PLK_OK;
 }
 
@@ -246,26 +215,16 @@ int fr_powers_dev(const Fr& s_mont, uint64_t n, Fr* d_out, hipStream_t s) {
 
 }  // namespace plk
 
-#define PLK_M_BEGIN try {
-#define PLK_M_END                 \
-  }                               \
-  catch (const std::bad_alloc&) { \
-    return PLK_E_OOM;             \
-  }                               \
-  catch (...) {                   \
-    return PLK_E_DEVICE;          \
-  }
-
 extern "C" {
 
 int plk_g1_mul_batch(plk_ctx* ctx, const plk_g1* points, const plk_fr* scalars, size_t n, int assume_subgroup,
                      plk_g1* out) {
-  PLK_M_BEGIN
+  PLK_API_BEGIN
   if (!ctx || n > kMaxBatch) return PLK_E_ARG;
   if (n == 0) return PLK_OK;
   if (!points || !scalars || !out) return PLK_E_ARG;
   for (size_t i = 0; i < n; ++i)
-    if (!fe_canonical(fe_of_abi<FrCfg>(scalars[i].l))) return PLK_E_ARG;
+    if (!abi_canonical<FrCfg>(scalars[i].l)) return PLK_E_ARG;
   int st;
   if (!assume_subgroup) {  // the split is only valid on G1
     std::vector<uint8_t> ok(n);
@@ -286,7 +245,7 @@ int plk_g1_mul_batch(plk_ctx* ctx, const plk_g1* points, const plk_fr* scalars, 
   PLK_HIP_TRY(hipMemcpyAsync(d_in.ptr, points, n * sizeof(plk_g1), hipMemcpyHostToDevice, s));
   PLK_HIP_TRY(hipMemcpyAsync(d_scal.ptr, scalars, n * sizeof(Fr), hipMemcpyHostToDevice, s));
   PLK_HIP_TRY(hipMemsetAsync(d_bad.ptr, 0, sizeof(uint32_t), s));
-  hipLaunchKernelGGL(k_g1_mul_load, dim3(blocks_for(n)), dim3(kBlock), 0, s, (const plk_g1*)d_in.as<plk_g1>(),
+  hipLaunchKernelGGL(k_g1_mul_load, dim3(cdiv(n, kBlock)), dim3(kBlock), 0, s, (const plk_g1*)d_in.as<plk_g1>(),
                      (uint64_t)n, d_pts.as<G1Affine>(), d_inf.as<uint8_t>(), d_bad.as<uint32_t>());
   PLK_HIP_TRY(hipGetLastError());
   uint32_t bad = 0;
@@ -301,17 +260,9 @@ int plk_g1_mul_batch(plk_ctx* ctx, const plk_g1* points, const plk_fr* scalars, 
   PLK_HIP_TRY(hipMemcpyAsync(res.data(), d_out.ptr, n * sizeof(G1Affine), hipMemcpyDeviceToHost, s));
   PLK_HIP_TRY(hipMemcpyAsync(rinf.data(), d_oinf.ptr, n, hipMemcpyDeviceToHost, s));
   PLK_HIP_TRY(stream_wait(s));
-  for (size_t i = 0; i < n; ++i) {
-    std::memset(&out[i], 0, sizeof(plk_g1));
-    if (rinf[i]) {
-      out[i].infinity = 1;
-      continue;
-    }
-    fe_to_abi(res[i].x, out[i].x);
-    fe_to_abi(res[i].y, out[i].y);
-  }
+  for (size_t i = 0; i < n; ++i) g1_store(res[i].x, res[i].y, !rinf[i], &out[i]);
   return PLK_OK;
-  PLK_M_END
+  PLK_API_END
 }
 
 int plk_g1_mul_last_ms(plk_ctx* ctx, float* kernel_ms) {
@@ -321,16 +272,16 @@ int plk_g1_mul_last_ms(plk_ctx* ctx, float* kernel_ms) {
 }
 
 int plk_debug_glv_split(plk_ctx* ctx, const plk_fr* s, size_t n, uint64_t* out) {
-  PLK_M_BEGIN
+  PLK_API_BEGIN
   if (n > kMaxBatch) return PLK_E_ARG;
   if (n == 0) return PLK_OK;
   if (!s || !out) return PLK_E_ARG;
   for (size_t i = 0; i < n; ++i)
-    if (!fe_canonical(fe_of_abi<FrCfg>(s[i].l))) return PLK_E_ARG;
+    if (!abi_canonical<FrCfg>(s[i].l)) return PLK_E_ARG;
   if (!ctx) {
     for (size_t i = 0; i < n; ++i) {
       uint64_t a[2], b[2];
-      glv_split(fe_from_mont(fe_of_abi<FrCfg>(s[i].l)), a, b);
+      glv_split(fe_from_mont(fr_from_abi(s[i])), a, b);
       out[4 * i] = a[0];
       out[4 * i + 1] = a[1];
       out[4 * i + 2] = b[0];
@@ -345,13 +296,13 @@ int plk_debug_glv_split(plk_ctx* ctx, const plk_fr* s, size_t n, uint64_t* out) 
   if ((r = d_s.alloc(n * sizeof(Fr)))) return r;
   if ((r = d_out.alloc(n * 4 * sizeof(uint64_t)))) return r;
   PLK_HIP_TRY(hipMemcpyAsync(d_s.ptr, s, n * sizeof(Fr), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(k_glv_split, dim3(blocks_for(n)), dim3(kBlock), 0, st, (const Fr*)d_s.as<Fr>(), (uint64_t)n,
+  hipLaunchKernelGGL(k_glv_split, dim3(cdiv(n, kBlock)), dim3(kBlock), 0, st, (const Fr*)d_s.as<Fr>(), (uint64_t)n,
                      d_out.as<uint64_t>());
   PLK_HIP_TRY(hipGetLastError());
   PLK_HIP_TRY(hipMemcpyAsync(out, d_out.ptr, n * 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
   PLK_HIP_TRY(stream_wait(st));
   return PLK_OK;
-  PLK_M_END
+  PLK_API_END
 }
 
 }  // extern "C"

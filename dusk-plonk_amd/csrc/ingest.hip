@@ -10,8 +10,9 @@
 //    x0 = 0xd201000000010000 (Scott, eprint 2021/1130 section 6; zkcrypto's is_torsion_free).
 //  - k_fr_decode, one scalar per lane: range check and Montgomery form.
 //
-// The math (ingest_math.hpp, shared with srs_io.hip) is PLK_HD code on the packed field of
-// ff.hpp / g1.hpp, so the host decode
+// The math (ingest_math.hpp, shared with srs_io.hip) and the conversions at the boundary (abi.hpp:
+// item loads, limbs, the byte serializer) are PLK_HD code on the packed field of ff.hpp / g1.hpp,
+// so the host decode
 // (plk_proof_decode_compact, the single-proof path) and the kernels run the same functions; the
 // tests hold both against a pure-Python reference. The packed form, not the redundant-limb one
 // (ffr.hpp): both kernels are one long dependent chain of products per lane with canonical
@@ -59,23 +60,15 @@ __global__ void __launch_bounds__(kBlock) k_g1_decompress(const uint8_t* __restr
   const uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   if (t >= n) return;
   const uint64_t g = t / L.per, f = t % L.per;
-  const uint4* src = reinterpret_cast<const uint4*>(in + g * L.in_stride + f * kG1Bytes);  // 16-B aligned
   uint32_t w[12];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const uint4 q = src[i];
-    w[4 * i] = q.x;
-    w[4 * i + 1] = q.y;
-    w[4 * i + 2] = q.z;
-    w[4 * i + 3] = q.w;
-  }
+  ld_words(in + g * L.in_stride + f * kG1Bytes, w);  // 16-B aligned
   Fp x, y;
   bool inf;
-  const uint8_t st = g1_decompress_words(w, x, y, inf);
-  uint64_t* dst = reinterpret_cast<uint64_t*>(out + g * L.out_stride + f * sizeof(plk_g1));
-  fe_to_abi(x, dst);
-  fe_to_abi(y, dst + 6);
-  dst[12] = inf ? 1 : 0;
+  const uint8_t st = g1_decompress_words(w, x, y, inf);  // x = y = 0 unless finite and accepted
+  plk_g1* dst = reinterpret_cast<plk_g1*>(out + g * L.out_stride + f * sizeof(plk_g1));
+  fe_to_abi(x, dst->x);
+  fe_to_abi(y, dst->y);
+  dst->infinity = inf ? 1 : 0;
   status[g * L.st_stride + f] = st;
 }
 
@@ -87,28 +80,20 @@ __global__ void __launch_bounds__(kBlock) k_g1_subgroup(const uint8_t* __restric
   if (t >= n) return;
   const uint64_t g = t / L.per, f = t % L.per;
   uint8_t* st = status + g * L.st_stride + f;
-  const uint64_t* src = reinterpret_cast<const uint64_t*>(pts + g * L.out_stride + f * sizeof(plk_g1));
-  if (*st != PLK_INGEST_OK || src[12] != 0) return;
-  const Fp x = fe_of_abi<FpCfg>(src), y = fe_of_abi<FpCfg>(src + 6);
-  if (!g1_in_subgroup(x, y)) *st = PLK_INGEST_SUBGROUP;
+  const plk_g1* src = reinterpret_cast<const plk_g1*>(pts + g * L.out_stride + f * sizeof(plk_g1));
+  if (*st != PLK_INGEST_OK || src->infinity != 0) return;
+  const G1Abi p = g1_load<false>(src);
+  if (!g1_in_subgroup(p.x, p.y)) *st = PLK_INGEST_SUBGROUP;
 }
 
-// ABI points from the caller: status 0xff for a non-canonical or off-curve finite point or an
-// infinity word other than 0 / 1 (plk_g1_subgroup_check_batch refuses the call), else 0
+// ABI points from the caller: status 0xff for a point g1_load<true> refuses
+// (plk_g1_subgroup_check_batch refuses the call), else 0
 constexpr uint8_t kBadPoint = 0xff;
 __global__ void __launch_bounds__(kBlock) k_g1_validate(const plk_g1* __restrict__ pts, uint64_t n,
                                                         uint8_t* __restrict__ status) {
   const uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   if (t >= n) return;
-  const uint64_t* src = reinterpret_cast<const uint64_t*>(pts + t);
-  uint8_t st = PLK_INGEST_OK;
-  if (src[12] > 1) {
-    st = kBadPoint;
-  } else if (src[12] == 0) {
-    const Fp x = fe_of_abi<FpCfg>(src), y = fe_of_abi<FpCfg>(src + 6);
-    if (!fe_canonical(x) || !fe_canonical(y) || !g1_on_curve(x, y)) st = kBadPoint;
-  }
-  status[t] = st;
+  status[t] = g1_load<true>(pts + t).ok ? PLK_INGEST_OK : kBadPoint;
 }
 
 __global__ void __launch_bounds__(kBlock) k_fr_decode(const uint8_t* __restrict__ in, uint64_t n, Layout L,
@@ -116,23 +101,13 @@ __global__ void __launch_bounds__(kBlock) k_fr_decode(const uint8_t* __restrict_
   const uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   if (t >= n) return;
   const uint64_t g = t / L.per, f = t % L.per;
-  const uint4* src = reinterpret_cast<const uint4*>(in + g * L.in_stride + f * kFrBytes);  // 16-B aligned
   uint32_t w[8];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const uint4 q = src[i];
-    w[4 * i] = q.x;
-    w[4 * i + 1] = q.y;
-    w[4 * i + 2] = q.z;
-    w[4 * i + 3] = q.w;
-  }
+  ld_words(in + g * L.in_stride + f * kFrBytes, w);  // 16-B aligned
   Fr s;
   const uint8_t st = fr_decode_words(w, s);
   fe_to_abi(s, reinterpret_cast<uint64_t*>(out + g * L.out_stride + f * sizeof(plk_fr)));
   status[g * L.st_stride + f] = st;
 }
-
-inline uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + kBlock - 1) / kBlock); }
 
 // ---- host codec -----------------------------------------------------------------------
 // field order of proof.rs:39-66 / plk_proof: the 11 commitments, then the 16 evaluations
@@ -141,28 +116,12 @@ plk_g1* comm(plk_proof* p, size_t i) { return &p->a_comm + i; }
 const plk_fr* eval(const plk_proof* p, size_t i) { return &p->a_eval + i; }
 plk_fr* eval(plk_proof* p, size_t i) { return &p->a_eval + i; }
 
-template <int N>
-void words_of_bytes(const uint8_t* b, uint32_t (&w)[N]) {
-  for (int i = 0; i < N; ++i)
-    w[i] = (uint32_t)b[4 * i] | ((uint32_t)b[4 * i + 1] << 8) | ((uint32_t)b[4 * i + 2] << 16) |
-           ((uint32_t)b[4 * i + 3] << 24);
-}
-
-// the 48 bytes Transcript::g1_compress writes, for a canonical point
+// the 48 bytes Transcript::g1_compress writes, for a point with canonical limbs (the curve
+// equation is not asked for: an encoder, not a validator)
 bool g1_compress_host(const plk_g1& p, uint8_t* out) {
-  std::memset(out, 0, kG1Bytes);
-  if (p.infinity > 1) return false;
-  if (p.infinity) {
-    out[0] = 0xc0;
-    return true;
-  }
-  Fp x = fe_of_abi<FpCfg>(p.x), y = fe_of_abi<FpCfg>(p.y);
-  if (!fe_canonical(x) || !fe_canonical(y)) return false;
-  x = fe_from_mont(x);
-  y = fe_from_mont(y);
-  for (int i = 0; i < 12; ++i)
-    for (int k = 0; k < 4; ++k) out[47 - (4 * i + k)] = (uint8_t)(x.v[i] >> (8 * k));
-  out[0] |= 0x80 | (fp_gt(y, fe_neg(y)) ? 0x20 : 0);
+  const G1Abi a = g1_load<false>(&p);
+  if (p.infinity > 1 || (!a.inf && !(fe_canonical(a.x) && fe_canonical(a.y)))) return false;
+  g1_compress_bytes(a.x, a.y, a.inf, out);
   return true;
 }
 
@@ -175,10 +134,7 @@ uint8_t g1_decompress_host(const uint8_t* in, int check_subgroup, plk_g1* out) {
   uint8_t st = g1_decompress_words(w, x, y, inf);
   if (st == PLK_INGEST_OK && !inf && check_subgroup && !g1_in_subgroup(x, y)) st = PLK_INGEST_SUBGROUP;
   std::memset(out, 0, sizeof *out);
-  if (st != PLK_INGEST_OK) return st;
-  fe_to_abi(x, out->x);
-  fe_to_abi(y, out->y);
-  out->infinity = inf ? 1 : 0;
+  if (st == PLK_INGEST_OK) g1_store(x, y, !inf, out);
   return st;
 }
 
@@ -186,12 +142,8 @@ uint8_t g1_decompress_host(const uint8_t* in, int check_subgroup, plk_g1* out) {
 
 struct IngestWs {
   DevBuf d_in, d_out, d_status;
-  hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+  TimingEvents<4> ev;
   float decompress_ms = 0.f, subgroup_ms = 0.f;
-  ~IngestWs() {
-    for (hipEvent_t ev : e)
-      if (ev) (void)hipEventDestroy(ev);
-  }
 };
 void ingest_ws_delete(IngestWs* w) { delete w; }
 
@@ -200,10 +152,8 @@ namespace {
 int ingest_ws(plk_ctx* ctx, IngestWs** out) {
   if (!ctx->ingest_ws) ctx->ingest_ws = new IngestWs();
   IngestWs& w = *ctx->ingest_ws;
-  for (hipEvent_t& ev : w.e)
-    if (!ev) PLK_HIP_TRY(hipEventCreate(&ev));
   *out = &w;
-  return PLK_OK;
+  return w.ev.create();
 }
 
 // the timed kernels of one batched call on the context's stream: decompression of n_pts points
@@ -212,17 +162,17 @@ int run_point_kernels(plk_ctx* ctx, IngestWs& w, uint64_t n_pts, const Layout& L
                       bool subgroup) {
   hipStream_t s = ctx->stream;
   if (decompress) {
-    PLK_HIP_TRY(hipEventRecord(w.e[0], s));
-    hipLaunchKernelGGL(k_g1_decompress, dim3(blocks_for(n_pts)), dim3(kBlock), 0, s,
+    PLK_HIP_TRY(hipEventRecord(w.ev.e[0], s));
+    hipLaunchKernelGGL(k_g1_decompress, dim3(cdiv(n_pts, kBlock)), dim3(kBlock), 0, s,
                        (const uint8_t*)w.d_in.as<uint8_t>(), n_pts, L, w.d_out.as<uint8_t>(),
                        w.d_status.as<uint8_t>());
-    PLK_HIP_TRY(hipEventRecord(w.e[1], s));
+    PLK_HIP_TRY(hipEventRecord(w.ev.e[1], s));
   }
   if (subgroup) {
-    PLK_HIP_TRY(hipEventRecord(w.e[2], s));
-    hipLaunchKernelGGL(k_g1_subgroup, dim3(blocks_for(n_pts)), dim3(kBlock), 0, s,
+    PLK_HIP_TRY(hipEventRecord(w.ev.e[2], s));
+    hipLaunchKernelGGL(k_g1_subgroup, dim3(cdiv(n_pts, kBlock)), dim3(kBlock), 0, s,
                        (const uint8_t*)w.d_out.as<uint8_t>(), n_pts, L, w.d_status.as<uint8_t>());
-    PLK_HIP_TRY(hipEventRecord(w.e[3], s));
+    PLK_HIP_TRY(hipEventRecord(w.ev.e[3], s));
   }
   PLK_HIP_TRY(hipGetLastError());
   return PLK_OK;
@@ -230,22 +180,12 @@ int run_point_kernels(plk_ctx* ctx, IngestWs& w, uint64_t n_pts, const Layout& L
 
 void read_timings(IngestWs& w, bool decompress, bool subgroup) {
   w.decompress_ms = w.subgroup_ms = 0.f;
-  if (decompress) (void)hipEventElapsedTime(&w.decompress_ms, w.e[0], w.e[1]);
-  if (subgroup) (void)hipEventElapsedTime(&w.subgroup_ms, w.e[2], w.e[3]);
+  if (decompress) (void)hipEventElapsedTime(&w.decompress_ms, w.ev.e[0], w.ev.e[1]);
+  if (subgroup) (void)hipEventElapsedTime(&w.subgroup_ms, w.ev.e[2], w.ev.e[3]);
 }
 
 }  // namespace
 }  // namespace plk
-
-#define PLK_I_BEGIN try {
-#define PLK_I_END                 \
-  }                               \
-  catch (const std::bad_alloc&) { \
-    return PLK_E_OOM;             \
-  }                               \
-  catch (...) {                   \
-    return PLK_E_DEVICE;          \
-  }
 
 extern "C" {
 
@@ -259,11 +199,8 @@ int plk_proof_encode_compact(const plk_proof* proof, uint8_t* out, size_t cap, s
   for (size_t i = 0; i < kComms; ++i, o += kG1Bytes)
     if (!g1_compress_host(*comm(proof, i), o)) return PLK_E_ARG;
   for (size_t i = 0; i < kEvals; ++i, o += kFrBytes) {
-    const Fr m = fe_of_abi<FrCfg>(eval(proof, i)->l);
-    if (!fe_canonical(m)) return PLK_E_ARG;
-    const Fr c = fe_from_mont(m);
-    for (int k = 0; k < 8; ++k)
-      for (int b = 0; b < 4; ++b) o[4 * k + b] = (uint8_t)(c.v[k] >> (8 * b));
+    if (!abi_canonical<FrCfg>(eval(proof, i)->l)) return PLK_E_ARG;
+    bytes_of_words(fe_from_mont(fr_from_abi(*eval(proof, i))).v, o);
   }
   std::memcpy(out, buf, sizeof buf);
   return PLK_OK;
@@ -281,7 +218,7 @@ int plk_proof_decode_compact(const uint8_t* in, size_t len, plk_proof* out, int 
     words_of_bytes(q, w);
     Fr s;
     if (fr_decode_words(w, s) != PLK_INGEST_OK) return PLK_E_ARG;
-    fe_to_abi(s, eval(&p, i)->l);
+    *eval(&p, i) = fr_to_abi(s);
   }
   *out = p;
   return PLK_OK;
@@ -289,7 +226,7 @@ int plk_proof_decode_compact(const uint8_t* in, size_t len, plk_proof* out, int 
 
 int plk_g1_decompress_batch(plk_ctx* ctx, const uint8_t* in48, size_t n, int check_subgroup, plk_g1* out,
                             uint8_t* status) {
-  PLK_I_BEGIN
+  PLK_API_BEGIN
   if (!ctx || !in48 || !out || !status || n == 0 || n > (1u << 28)) return PLK_E_ARG;
   DeviceGuard g(ctx->device);
   IngestWs* w;
@@ -313,11 +250,11 @@ int plk_g1_decompress_batch(plk_ctx* ctx, const uint8_t* in48, size_t n, int che
   std::memcpy(out, pts.data(), n * sizeof(plk_g1));
   std::memcpy(status, sts.data(), n);
   return PLK_OK;
-  PLK_I_END
+  PLK_API_END
 }
 
 int plk_g1_subgroup_check_batch(plk_ctx* ctx, const plk_g1* points, size_t n, uint8_t* ok) {
-  PLK_I_BEGIN
+  PLK_API_BEGIN
   if (!ctx || !points || !ok || n == 0 || n > (1u << 28)) return PLK_E_ARG;
   DeviceGuard g(ctx->device);
   IngestWs* w;
@@ -327,7 +264,7 @@ int plk_g1_subgroup_check_batch(plk_ctx* ctx, const plk_g1* points, size_t n, ui
   if ((st = w->d_status.alloc(n))) return st;
   hipStream_t s = ctx->stream;
   PLK_HIP_TRY(hipMemcpyAsync(w->d_out.ptr, points, n * sizeof(plk_g1), hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(k_g1_validate, dim3(blocks_for(n)), dim3(kBlock), 0, s,
+  hipLaunchKernelGGL(k_g1_validate, dim3(cdiv(n, kBlock)), dim3(kBlock), 0, s,
                      (const plk_g1*)w->d_out.as<plk_g1>(), (uint64_t)n, w->d_status.as<uint8_t>());
   const Layout L = {1, kG1Bytes, sizeof(plk_g1), 1};
   if ((st = run_point_kernels(ctx, *w, n, L, false, true))) return st;
@@ -339,12 +276,12 @@ int plk_g1_subgroup_check_batch(plk_ctx* ctx, const plk_g1* points, size_t n, ui
     if (sts[i] == kBadPoint) return PLK_E_ARG;
   for (size_t i = 0; i < n; ++i) ok[i] = sts[i] == PLK_INGEST_OK ? 1 : 0;
   return PLK_OK;
-  PLK_I_END
+  PLK_API_END
 }
 
 int plk_proofs_ingest(plk_ctx* ctx, const uint8_t* in, size_t count, int check_subgroup, plk_proof* out,
                       uint8_t* status) {
-  PLK_I_BEGIN
+  PLK_API_BEGIN
   if (!ctx || !in || !out || !status || count == 0 || count > (1u << 24)) return PLK_E_ARG;
   DeviceGuard g(ctx->device);
   IngestWs* w;
@@ -359,7 +296,7 @@ int plk_proofs_ingest(plk_ctx* ctx, const uint8_t* in, size_t count, int check_s
   const Layout LP = {(uint32_t)kComms, PLK_PROOF_COMPACT_BYTES, sizeof(plk_proof), kFields};
   if ((st = run_point_kernels(ctx, *w, count * kComms, LP, true, check_subgroup != 0))) return st;
   const Layout LS = {(uint32_t)kEvals, PLK_PROOF_COMPACT_BYTES, sizeof(plk_proof), kFields};
-  hipLaunchKernelGGL(k_fr_decode, dim3(blocks_for(count * kEvals)), dim3(kBlock), 0, s,
+  hipLaunchKernelGGL(k_fr_decode, dim3(cdiv(count * kEvals, kBlock)), dim3(kBlock), 0, s,
                      (const uint8_t*)w->d_in.as<uint8_t>() + kComms * kG1Bytes, (uint64_t)(count * kEvals), LS,
                      w->d_out.as<uint8_t>() + kComms * sizeof(plk_g1), w->d_status.as<uint8_t>() + kComms);
   PLK_HIP_TRY(hipGetLastError());
@@ -377,7 +314,7 @@ int plk_proofs_ingest(plk_ctx* ctx, const uint8_t* in, size_t count, int check_s
   }
   std::memcpy(out, res.data(), count * sizeof(plk_proof));
   return PLK_OK;
-  PLK_I_END
+  PLK_API_END
 }
 
 int plk_ingest_last_ms(plk_ctx* ctx, float* decompress_ms, float* subgroup_ms) {
@@ -391,7 +328,7 @@ int plk_ingest_last_ms(plk_ctx* ctx, float* decompress_ms, float* subgroup_ms) {
 int plk_verifier_verify_each_bytes(plk_ctx* ctx, plk_verifier* v, plk_opening_key* key, const uint8_t* in,
                                    const plk_fr* public_inputs, size_t count, int check_subgroup,
                                    uint8_t* verdict) {
-  PLK_I_BEGIN
+  PLK_API_BEGIN
   if (!ctx || !v || !key || !in || !verdict || count == 0 || count > (1u << 24)) return PLK_E_ARG;
   const size_t npi = verifier_pi_count(v);
   if (npi && !public_inputs) return PLK_E_ARG;
@@ -416,7 +353,7 @@ int plk_verifier_verify_each_bytes(plk_ctx* ctx, plk_verifier* v, plk_opening_ke
   for (size_t j = 0; j < count; ++j) verdict[j] = (uint8_t)(0x10 | status[j]);
   for (size_t k = 0; k < where.size(); ++k) verdict[where[k]] = ok[k];
   return PLK_OK;
-  PLK_I_END
+  PLK_API_END
 }
 
 }  // extern "C"

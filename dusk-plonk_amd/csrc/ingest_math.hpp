@@ -7,6 +7,8 @@
 //  - g1_in_subgroup: P in G1  <=>  (beta x, y) == -[x0^2] P with x0 = 0xd201000000010000 (Scott,
 //    eprint 2021/1130 section 6; zkcrypto's is_torsion_free).
 //  - fr_decode_words: range check and Montgomery form.
+// The limb and byte conversions, the canonical test, the curve constants and the curve equation
+// are abi.hpp's.
 //
 // The square root's exponent is fixed: a sliding window of 3 bits over it with the odd powers
 // x, x^3, x^5, x^7 held in registers (48 VGPRs) costs 379 squarings and about 100 products. The
@@ -16,7 +18,7 @@
 #include <stdint.h>
 
 #include "../../include/plk.h"
-#include "ff.hpp"
+#include "abi.hpp"
 #include "g1.hpp"
 
 namespace plk {
@@ -40,37 +42,6 @@ PLK_HD uint32_t sqrt_exp_word(int i) {
 }
 constexpr int kSqrtExpBits = 379;
 PLK_HD uint32_t sqrt_exp_bit(int i) { return (sqrt_exp_word(i >> 5) >> (i & 31)) & 1u; }
-
-PLK_HD Fp fp_const(const uint32_t (&w)[12]) {
-  Fp r;
-#pragma unroll
-  for (int i = 0; i < 12; ++i) r.v[i] = w[i];
-  return r;
-}
-// 4 and beta in Montgomery form; beta = 0x5f19672f...fffefffe, the cube root of unity with
-// (beta x, y) = [-x0^2] (x, y) on G1
-PLK_HD Fp fp_four() {
-  const uint32_t w[12] = {0x000cfff3u, 0xaa270000u, 0xfc34000au, 0x53cc0032u, 0x6b0a807fu, 0x478fe97au,
-                          0xe6ba24d7u, 0xb1d37ebeu, 0xbf78ab2fu, 0x8ec9733bu, 0x3d83de7eu, 0x09d64551u};
-  return fp_const(w);
-}
-PLK_HD Fp fp_beta() {
-  const uint32_t w[12] = {0x798a64e8u, 0x30f1361bu, 0x7ece5a2au, 0xf3b8ddabu, 0xc61577f7u, 0x16a8ca3au,
-                          0x74fd029bu, 0xc26a2ff8u, 0x60701c6eu, 0x3636b766u, 0x241b6160u, 0x051ba4abu};
-  return fp_const(w);
-}
-
-// a < modulus, for a value in plain 32-bit words
-template <class C>
-PLK_HD bool fe_canonical(const Fe<C>& a) {
-  uint32_t borrow = 0;
-#pragma unroll
-  for (int i = 0; i < C::N; ++i) {
-    const uint64_t t = (uint64_t)a.v[i] - C::P[i] - borrow;
-    borrow = (uint32_t)(t >> 63);
-  }
-  return borrow != 0;
-}
 
 // a > b as integers
 PLK_HD bool fp_gt(const Fp& a, const Fp& b) {
@@ -125,18 +96,6 @@ PLK_HD Fp fp_sqrt_candidate(const Fp& a) {
       started = true;
     }
     i -= len;
-  }
-  return r;
-}
-
-// 12 words read little-endian from 48 big-endian bytes -> the value's words (word i of the value
-// is the byte-swapped word 11 - i)
-PLK_HD Fp fp_of_be_words(const uint32_t* w) {
-  Fp r;
-#pragma unroll
-  for (int i = 0; i < 12; ++i) {
-    const uint32_t v = w[11 - i];
-    r.v[i] = (v >> 24) | ((v >> 8) & 0xff00u) | ((v << 8) & 0xff0000u) | (v << 24);
   }
   return r;
 }
@@ -209,26 +168,6 @@ PLK_HD uint8_t fr_decode_words(const uint32_t (&w)[8], Fr& out) {
   if (!fe_canonical(c)) return PLK_INGEST_RANGE;
   out = fe_to_mont(c);
   return PLK_INGEST_OK;
-}
-
-template <class C>
-PLK_HD Fe<C> fe_of_abi(const uint64_t* l) {
-  Fe<C> r;
-#pragma unroll
-  for (int i = 0; i < C::N / 2; ++i) {
-    r.v[2 * i] = (uint32_t)l[i];
-    r.v[2 * i + 1] = (uint32_t)(l[i] >> 32);
-  }
-  return r;
-}
-template <class C>
-PLK_HD void fe_to_abi(const Fe<C>& a, uint64_t* l) {
-#pragma unroll
-  for (int i = 0; i < C::N / 2; ++i) l[i] = (uint64_t)a.v[2 * i] | ((uint64_t)a.v[2 * i + 1] << 32);
-}
-
-PLK_HD bool g1_on_curve(const Fp& x, const Fp& y) {
-  return fe_eq(fe_sqr(y), fe_add(fe_mul(fe_sqr(x), x), fp_four()));
 }
 
 }  // namespace plk

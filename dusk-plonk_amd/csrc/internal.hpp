@@ -5,10 +5,11 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <new>
 #include <vector>
 
 #include "../../include/plk.h"
-#include "ff.hpp"
+#include "abi.hpp"
 #include "g1.hpp"
 
 namespace plk {
@@ -22,7 +23,43 @@ namespace plk {
     }                                                            \
   } while (0)
 
+// Around the body of every extern "C" entry point that can throw: no C++ exception crosses the
+// boundary, it comes back as a plk_status.
+#define PLK_API_BEGIN try {
+#define PLK_API_END                 \
+  }                                 \
+  catch (const std::bad_alloc&) {   \
+    return PLK_E_OOM;               \
+  }                                 \
+  catch (...) {                     \
+    return PLK_E_DEVICE;            \
+  }
+
 hipError_t& last_hip_error();
+
+// blocks of b threads for a items
+inline uint32_t cdiv(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
+
+// 32 bytes from the OS (getrandom, std::random_device behind it); api.hip
+void os_entropy(uint8_t seed[32]);
+
+// N timing events, created on first use and destroyed with their holder
+template <int N>
+struct TimingEvents {
+  hipEvent_t e[N] = {};
+  TimingEvents() = default;
+  TimingEvents(const TimingEvents&) = delete;
+  TimingEvents& operator=(const TimingEvents&) = delete;
+  ~TimingEvents() {
+    for (hipEvent_t ev : e)
+      if (ev) (void)hipEventDestroy(ev);
+  }
+  int create() {
+    for (hipEvent_t& ev : e)
+      if (!ev) PLK_HIP_TRY(hipEventCreate(&ev));
+    return PLK_OK;
+  }
+};
 
 // Device buffer owned by a context object.
 struct DevBuf {

@@ -1364,22 +1364,13 @@ __global__ void __launch_bounds__(256) k_guard(const uint32_t* __restrict__ offs
 
 }  // namespace
 
-// R'-domain [0, 2p) packed coordinates (ffr.hpp) -> canonical R-domain: x * 2^-SH
-// (SH = BL - 384 = 6) as the R-domain product x * 2^(384 - SH) / 2^384.
-static Fp fp_rx_to_r(Fp x) {
-  constexpr int SH = RxShape<FpCfg>::B * RxShape<FpCfg>::L - 32 * FpCfg::N;
-  static_assert(SH > 0 && SH < 32, "R' / R shift");
-  fe_reduce_once(x);
-  Fp k = fe_zero<FpCfg>();
-  k.v[11] = 1u << (32 - SH);  // 2^(384 - SH) (< p)
-  return fe_mul(x, k);
-}
+// R'-domain [0, 2p) packed coordinates (ffr.hpp) -> canonical R-domain
 G1xyzz rx_to_r_domain(const G1xyzz& p) {
-  G1xyzz r;
-  r.X = fp_rx_to_r(p.X);
-  r.Y = fp_rx_to_r(p.Y);
-  r.ZZ = fp_rx_to_r(p.ZZ);
-  r.ZZZ = fp_rx_to_r(p.ZZZ);
+  G1xyzz r = p;
+  for (Fp* c : {&r.X, &r.Y, &r.ZZ, &r.ZZZ}) {
+    fe_reduce_once(*c);
+    *c = fp_rx_to_r(*c);
+  }
   return r;
 }
 
@@ -1795,11 +1786,7 @@ int msm_run_batch(plk_srs* s, MsmWorkspace& w, const Fr* const* d_scalars, const
     }
     Fp x, y;
     const bool fin = xyzz_to_affine(acc, x, y);
-    for (int i = 0; i < 6; ++i) {
-      out->x[i] = (uint64_t)x.v[2 * i] | ((uint64_t)x.v[2 * i + 1] << 32);
-      out->y[i] = (uint64_t)y.v[2 * i] | ((uint64_t)y.v[2 * i + 1] << 32);
-    }
-    out->infinity = fin ? 0 : 1;
+    g1_store(x, y, fin, out);
     if (statuses) statuses[k] = PLK_OK;
   }
   return overall;

@@ -2,6 +2,7 @@
 #pragma once
 #include <cstdlib>
 
+#include "ffr.hpp"
 #include "internal.hpp"
 
 namespace plk {
@@ -85,9 +86,6 @@ __device__ __forceinline__ Fr ld_fr(const Fr* p) {
   r.v[4] = b.x; r.v[5] = b.y; r.v[6] = b.z; r.v[7] = b.w;
   return r;
 }
-
-
-inline uint32_t cdiv(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
 
 // Head of a batch's readback record (MsmWorkspace::host_out, written by the kernels straight
 // into mapped host memory, the bit sums after it): per slot the degree-check flag (stamped
@@ -175,6 +173,16 @@ inline int lane_tail_policy(uint64_t n) {
 // R'-domain [0, 2p) packed XYZZ coordinates (ffr.hpp), as the reduction kernels store them ->
 // canonical R-domain (msm.hip): what the host tails read back
 G1xyzz rx_to_r_domain(const G1xyzz& p);
+// One coordinate of it, for a value already below p (the host reduces a packed [0, 2p) value once,
+// a kernel packs with rx_pack_canonical): x * 2^-SH (SH = BL - 384 = 6) as the R-domain product
+// x * 2^(384 - SH) / 2^384.
+PLK_HD Fp fp_rx_to_r(const Fp& x) {
+  constexpr int SH = RxShape<FpCfg>::B * RxShape<FpCfg>::L - 32 * FpCfg::N;
+  static_assert(SH > 0 && SH < 32, "R' / R shift");
+  Fp k = fe_zero<FpCfg>();
+  k.v[11] = 1u << (32 - SH);  // 2^(384 - SH) (< p)
+  return fe_mul(x, k);
+}
 
 // k_accumulate (msm_acc.hip) over grid.x * 256 task lanes per slot (grid.y = slots), stamped
 // with the start / stop events ev0 / ev1 by the dispatch itself

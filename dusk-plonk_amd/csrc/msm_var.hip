@@ -37,11 +37,7 @@ namespace plk {
 struct VarMsmWs {
   DevBuf pts, inf, counts, offsets, cursor, task_off, sorted, tasks, partials, bsum, tout, bad;
   PinnedBuf host_out;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  ~VarMsmWs() {
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-  }
+  TimingEvents<2> ev;
 };
 
 void msm_var_ws_delete(VarMsmWs* w) { delete w; }
@@ -52,57 +48,24 @@ struct VarBatch {
   uint32_t start[kMaxSlots], len[kMaxSlots];
 };
 
-// a < p (12 words, little-endian)
-__device__ __forceinline__ bool fp_is_canonical(const Fp& a) {
-  uint32_t borrow = 0;
-#pragma unroll
-  for (int i = 0; i < 12; ++i) {
-    const uint64_t t = (uint64_t)a.v[i] - FpCfg::P[i] - borrow;
-    borrow = (uint32_t)(t >> 63);
-  }
-  return borrow != 0;
-}
-
-// ABI point i -> pts[i] (R' domain) and inf[i]; *bad = 1 for a finite point that is not
-// canonical or not on y^2 = x^3 + 4, or an infinity word other than 0 / 1
+// ABI point i -> pts[i] (R' domain) and inf[i]; *bad = 1 for a point g1_load<true> refuses, which
+// is kept out of the sums (flagged as identity) while the call fails with PLK_E_ARG
 __global__ void __launch_bounds__(256) k_var_prepare(const plk_g1* __restrict__ in, uint32_t n,
                                                      G1Affine* __restrict__ pts,
                                                      uint8_t* __restrict__ inf,
                                                      uint32_t* __restrict__ bad) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const uint64_t* q = reinterpret_cast<const uint64_t*>(&in[i]);
-  const uint64_t flag = q[12];
-  if (flag) {
-    if (flag != 1) *bad = 1;
-    st_aff(&pts[i], fe_zero<FpCfg>(), fe_zero<FpCfg>());
-    inf[i] = 1;
-    return;
+  const G1Abi p = g1_load<true>(&in[i]);
+  if (!p.ok) *bad = 1;
+  const bool keep = p.ok && !p.inf;
+  Fp x = fe_zero<FpCfg>(), y = fe_zero<FpCfg>();
+  if (keep) {
+    x = fe_to_rx_domain(p.x);
+    y = fe_to_rx_domain(p.y);
   }
-  Fp x, y;
-#pragma unroll
-  for (int k = 0; k < 6; ++k) {
-    const uint64_t a = q[k], b = q[6 + k];
-    x.v[2 * k] = (uint32_t)a;
-    x.v[2 * k + 1] = (uint32_t)(a >> 32);
-    y.v[2 * k] = (uint32_t)b;
-    y.v[2 * k + 1] = (uint32_t)(b >> 32);
-  }
-  bool ok = fp_is_canonical(x) && fp_is_canonical(y);
-  if (ok) {
-    Fp four = fe_one<FpCfg>();
-    four = fe_dbl(fe_dbl(four));
-    const Fp rhs = fe_add(fe_mul(fe_sqr(x), x), four);
-    ok = fe_eq(fe_sqr(y), rhs);
-  }
-  if (!ok) {  // kept out of the sums (flagged as identity); the call fails with PLK_E_ARG
-    *bad = 1;
-    st_aff(&pts[i], fe_zero<FpCfg>(), fe_zero<FpCfg>());
-    inf[i] = 1;
-    return;
-  }
-  st_aff(&pts[i], fe_to_rx_domain(x), fe_to_rx_domain(y));
-  inf[i] = 0;
+  st_aff(&pts[i], x, y);
+  inf[i] = keep ? 0 : 1;
 }
 
 // Canonical scalar in [0, (r-1)/2]: s, or r - s with the digit signs flipped (msm.hip
@@ -360,8 +323,7 @@ int msm_var_run(plk_ctx* ctx, const plk_g1* d_points, const Fr* d_scalars, size_
   const size_t out_bytes = (size_t)slots * NT * sizeof(G1xyzz);
   if ((st = w.tout.alloc(out_bytes + 16))) return st;  // the T_j, then the curve-check flag
   if ((st = w.host_out.alloc(out_bytes + 16))) return st;
-  if (!w.ev0) PLK_HIP_TRY(hipEventCreate(&w.ev0));
-  if (!w.ev1) PLK_HIP_TRY(hipEventCreate(&w.ev1));
+  if ((st = w.ev.create())) return st;
   uint32_t* bad = reinterpret_cast<uint32_t*>(w.tout.as<uint8_t>() + out_bytes);
 
   PLK_HIP_TRY(hipMemsetAsync(bad, 0, 16, stream));
@@ -379,7 +341,7 @@ int msm_var_run(plk_ctx* ctx, const plk_g1* d_points, const Fr* d_scalars, size_
                      w.sorted.as<uint32_t>(), (uint64_t)E);
   PLK_HIP_TRY(hipGetLastError());
   // identity inputs emit no entries, so k_accumulate runs without its identity path
-  launch_accumulate(false, true, dim3(cdiv(task_stride, 256), slots), stream, w.ev0, w.ev1,
+  launch_accumulate(false, true, dim3(cdiv(task_stride, 256), slots), stream, w.ev.e[0], w.ev.e[1],
                     w.tasks.as<uint2>(), w.task_off.as<uint32_t>(), NB, (uint64_t)task_stride,
                     w.sorted.as<uint32_t>(), (uint64_t)E, w.pts.as<G1Affine>(),
                     w.inf.as<uint8_t>(), w.partials.as<G1xyzz>());
@@ -403,12 +365,7 @@ int msm_var_run(plk_ctx* ctx, const plk_g1* d_points, const Fr* d_scalars, size_
     }
     Fp x, y;
     const bool fin = xyzz_to_affine(acc, x, y);
-    plk_g1* out = &outs[k];
-    for (int i = 0; i < 6; ++i) {
-      out->x[i] = (uint64_t)x.v[2 * i] | ((uint64_t)x.v[2 * i + 1] << 32);
-      out->y[i] = (uint64_t)y.v[2 * i] | ((uint64_t)y.v[2 * i + 1] << 32);
-    }
-    out->infinity = fin ? 0 : 1;
+    g1_store(x, y, fin, &outs[k]);
   }
   return PLK_OK;
 }
@@ -421,34 +378,30 @@ extern "C" {
 
 int plk_msm_points_ranges(plk_ctx* ctx, const plk_g1* points, const plk_fr* scalars, size_t n,
                           const size_t* starts, const size_t* lens, size_t count, plk_g1* outs) {
-  try {
-    if (!ctx || !outs || count == 0 || count > kMaxSlots || !starts || !lens ||
-        (n && (!points || !scalars)))
-      return PLK_E_ARG;
-    for (size_t k = 0; k < count; ++k)
-      if (starts[k] > n || lens[k] > n - starts[k]) return PLK_E_ARG;
-    for (size_t a = 0; a < count; ++a)  // disjoint ranges
-      for (size_t b = a + 1; b < count; ++b)
-        if (lens[a] && lens[b] && starts[a] < starts[b] + lens[b] && starts[b] < starts[a] + lens[a])
-          return PLK_E_ARG;
-    DeviceGuard g(ctx->device);
-    hipStream_t s = ctx->stream;
-    DevBuf dp, ds;
-    int st;
-    if (n) {
-      if ((st = dp.alloc(n * sizeof(plk_g1)))) return st;
-      if ((st = ds.alloc(n * sizeof(Fr)))) return st;
-      PLK_HIP_TRY(hipMemcpyAsync(dp.ptr, points, n * sizeof(plk_g1), hipMemcpyHostToDevice, s));
-      PLK_HIP_TRY(hipMemcpyAsync(ds.ptr, scalars, n * sizeof(Fr), hipMemcpyHostToDevice, s));
-    }
-    st = msm_var_run(ctx, dp.as<plk_g1>(), ds.as<Fr>(), n, starts, lens, count, outs, s);
-    (void)stream_wait(s);  // dp / ds are freed on return
-    return st;
-  } catch (const std::bad_alloc&) {
-    return PLK_E_OOM;
-  } catch (...) {
-    return PLK_E_DEVICE;
+  PLK_API_BEGIN
+  if (!ctx || !outs || count == 0 || count > kMaxSlots || !starts || !lens ||
+      (n && (!points || !scalars)))
+    return PLK_E_ARG;
+  for (size_t k = 0; k < count; ++k)
+    if (starts[k] > n || lens[k] > n - starts[k]) return PLK_E_ARG;
+  for (size_t a = 0; a < count; ++a)  // disjoint ranges
+    for (size_t b = a + 1; b < count; ++b)
+      if (lens[a] && lens[b] && starts[a] < starts[b] + lens[b] && starts[b] < starts[a] + lens[a])
+        return PLK_E_ARG;
+  DeviceGuard g(ctx->device);
+  hipStream_t s = ctx->stream;
+  DevBuf dp, ds;
+  int st;
+  if (n) {
+    if ((st = dp.alloc(n * sizeof(plk_g1)))) return st;
+    if ((st = ds.alloc(n * sizeof(Fr)))) return st;
+    PLK_HIP_TRY(hipMemcpyAsync(dp.ptr, points, n * sizeof(plk_g1), hipMemcpyHostToDevice, s));
+    PLK_HIP_TRY(hipMemcpyAsync(ds.ptr, scalars, n * sizeof(Fr), hipMemcpyHostToDevice, s));
   }
+  st = msm_var_run(ctx, dp.as<plk_g1>(), ds.as<Fr>(), n, starts, lens, count, outs, s);
+  (void)stream_wait(s);  // dp / ds are freed on return
+  return st;
+  PLK_API_END
 }
 
 int plk_msm_points(plk_ctx* ctx, const plk_g1* points, const plk_fr* scalars, size_t n, plk_g1* out) {

@@ -25,35 +25,7 @@
 
 using namespace plk;
 
-#define PLK_API_BEGIN try {
-#define PLK_API_END               \
-  }                               \
-  catch (const std::bad_alloc&) { \
-    return PLK_E_OOM;             \
-  }                               \
-  catch (...) {                   \
-    return PLK_E_DEVICE;          \
-  }
-
 namespace {
-
-Fr fr_of(const plk_fr& a) {
-  Fr r;
-  for (int i = 0; i < 4; ++i) {
-    r.v[2 * i] = (uint32_t)a.l[i];
-    r.v[2 * i + 1] = (uint32_t)(a.l[i] >> 32);
-  }
-  return r;
-}
-
-// limbs < r (the ABI takes canonical Montgomery values)
-bool fr_canonical(const plk_fr& a) {
-  for (int i = FrCfg::N - 1; i >= 0; --i) {
-    const uint32_t w = (uint32_t)(a.l[i / 2] >> (32 * (i % 2)));
-    if (w != FrCfg::P[i]) return w < FrCfg::P[i];
-  }
-  return false;
-}
 
 // Stream-ordered scratch freed on the same stream when the scope ends.
 struct AsyncBuf {
@@ -118,7 +90,7 @@ int aggregate_witness(const Fr* const* polys, const size_t* lens, size_t count, 
 int check_args(const size_t* lens, size_t count, const plk_fr* point, const plk_fr* challenge,
                size_t* out_len, uint64_t* max_len) {
   if ((count && !lens) || !point || !challenge || !out_len) return PLK_E_ARG;
-  if (!fr_canonical(*point) || !fr_canonical(*challenge)) return PLK_E_ARG;
+  if (!abi_canonical<FrCfg>(point->l) || !abi_canonical<FrCfg>(challenge->l)) return PLK_E_ARG;
   uint64_t m = 0;
   for (size_t i = 0; i < count; ++i) m = std::max<uint64_t>(m, lens[i]);
   *max_len = m;
@@ -145,7 +117,7 @@ int plk_aggregate_witness_dev(plk_ctx* ctx, const plk_fr* const* d_polys, const 
   DeviceGuard g(ctx->device);
   hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
   return aggregate_witness(reinterpret_cast<const Fr* const*>(d_polys), lens, count,
-                           fr_of(*point), fr_of(*challenge), reinterpret_cast<Fr*>(d_out),
+                           fr_from_abi(*point), fr_from_abi(*challenge), reinterpret_cast<Fr*>(d_out),
                            max_len, s);
   PLK_API_END
 }
@@ -179,7 +151,7 @@ int plk_aggregate_witness(plk_ctx* ctx, const plk_fr* const* polys, const size_t
                                  hipMemcpyHostToDevice, s));
     off += lens[i];
   }
-  if ((st = aggregate_witness(dp.data(), lens, count, fr_of(*point), fr_of(*challenge), res.fr(),
+  if ((st = aggregate_witness(dp.data(), lens, count, fr_from_abi(*point), fr_from_abi(*challenge), res.fr(),
                               max_len, s)))
     return st;
   PLK_HIP_TRY(hipMemcpyAsync(out, res.fr(), *out_len * sizeof(Fr), hipMemcpyDeviceToHost, s));

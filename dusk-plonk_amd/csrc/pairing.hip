@@ -64,20 +64,6 @@ struct F12Dev {
   }
 };
 
-// ABI point -> (x, y); false for the point at infinity
-__device__ __forceinline__ bool ld_g1_abi(const plk_g1* p, Fp& x, Fp& y) {
-  const uint64_t* q = reinterpret_cast<const uint64_t*>(p);
-#pragma unroll
-  for (int k = 0; k < 6; ++k) {
-    const uint64_t a = q[k], b = q[6 + k];
-    x.v[2 * k] = (uint32_t)a;
-    x.v[2 * k + 1] = (uint32_t)(a >> 32);
-    y.v[2 * k] = (uint32_t)b;
-    y.v[2 * k + 1] = (uint32_t)(b >> 32);
-  }
-  return q[12] == 0;
-}
-
 // pairs != 0: lane j checks (pts[2 j], pts[2 j + 1]) = (C, W) against (tab H, tab beta_h) and
 // writes ok[j]. pairs == 0: lane j writes ML(pts[j], Q)^(3 (p^12 - 1) / r) to out[72 j ..], Q's
 // lines at tab[0 ..]. ws: one tile of kTileWords words per block of 64 lanes.
@@ -88,28 +74,24 @@ __global__ void __launch_bounds__(64) k_pairing(const plk_g1* __restrict__ pts, 
   const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= count) return;
   F12Dev m{ws + (size_t)blockIdx.x * kTileWords + threadIdx.x};
-  Fp x0, y0, x1, y1;
-  const bool on0 = ld_g1_abi(pairs ? &pts[2 * (size_t)j] : &pts[j], x0, y0);
+  // the points were validated by the caller (pairing_check_dev): the plain load
+  const G1Abi p0 = g1_load<false>(pairs ? &pts[2 * (size_t)j] : &pts[j]);
+  G1Abi p1 = p0;
   bool on1 = false;
   if (pairs) {
-    on1 = ld_g1_abi(&pts[2 * (size_t)j + 1], x1, y1);
-    y1 = fe_neg(y1);
-  } else {
-    x1 = x0;
-    y1 = y0;
+    p1 = g1_load<false>(&pts[2 * (size_t)j + 1]);
+    on1 = !p1.inf;
+    p1.y = fe_neg(p1.y);
   }
-  miller_loop(m, tab + kTabH, on0, x0, y0, pairs != 0, tab + kTabB, on1, x1, y1);
+  miller_loop(m, tab + kTabH, !p0.inf, p0.x, p0.y, pairs != 0, tab + kTabB, on1, p1.x, p1.y);
   const int r = f12_final_exp(m, tab + kTabFrob);
   if (pairs) {
     ok[j] = f12_is_one(m, r) ? 1 : 0;
   } else {
     for (int i = 0; i < 6; ++i) {
       const Fp2 a = m.ld(r, i);
-#pragma unroll
-      for (int k = 0; k < 6; ++k) {
-        out[72 * (size_t)j + 12 * i + k] = (uint64_t)a.c0.v[2 * k] | ((uint64_t)a.c0.v[2 * k + 1] << 32);
-        out[72 * (size_t)j + 12 * i + 6 + k] = (uint64_t)a.c1.v[2 * k] | ((uint64_t)a.c1.v[2 * k + 1] << 32);
-      }
+      fe_to_abi(a.c0, out + 72 * (size_t)j + 12 * i);
+      fe_to_abi(a.c1, out + 72 * (size_t)j + 12 * i + 6);
     }
   }
 }
@@ -175,39 +157,23 @@ int pairing_last_ms(plk_opening_key* key, float* ms) {
 
 }  // namespace plk
 
-#define PLK_P_BEGIN try {
-#define PLK_P_END                   \
-  }                                 \
-  catch (const std::bad_alloc&) {   \
-    return PLK_E_OOM;               \
-  }                                 \
-  catch (...) {                     \
-    return PLK_E_DEVICE;            \
-  }
-
 extern "C" {
 
 int plk_opening_key_setup(const plk_fr* tau, plk_opening_key** out) {
-  PLK_P_BEGIN
+  PLK_API_BEGIN
   if (!out) return PLK_E_ARG;
   *out = nullptr;
   if (!tau) return PLK_E_ARG;
-  Fr t;
-  for (int i = 0; i < 4; ++i) {
-    t.v[2 * i] = (uint32_t)tau->l[i];
-    t.v[2 * i + 1] = (uint32_t)(tau->l[i] >> 32);
-  }
-  Fr red = t;
-  fe_reduce_once(red);
-  if (!fe_eq(red, t) || fe_is_zero(t)) return PLK_E_ARG;  // not canonical, or zero
+  const Fr t = fr_from_abi(*tau);
+  if (!fe_canonical(t) || fe_is_zero(t)) return PLK_E_ARG;
   const Fr plain = fe_from_mont(t);
   const G2Aff h = g2_generator();
   return key_build(h, g2_mul(h, plain.v, 8), out);
-  PLK_P_END
+  PLK_API_END
 }
 
 int plk_opening_key_load(const plk_g2* h, const plk_g2* beta_h, plk_opening_key** out) {
-  PLK_P_BEGIN
+  PLK_API_BEGIN
   if (!out) return PLK_E_ARG;
   *out = nullptr;
   if (!h || !beta_h) return PLK_E_ARG;
@@ -216,7 +182,7 @@ int plk_opening_key_load(const plk_g2* h, const plk_g2* beta_h, plk_opening_key*
   if ((st = g2_from_abi(*h, a)) || (st = g2_from_abi(*beta_h, b))) return st;
   if (!g2_in_subgroup(a) || !g2_in_subgroup(b)) return PLK_E_ARG;
   return key_build(a, b, out);
-  PLK_P_END
+  PLK_API_END
 }
 
 int plk_opening_key_points(const plk_opening_key* key, plk_g2* h, plk_g2* beta_h) {
@@ -227,7 +193,7 @@ int plk_opening_key_points(const plk_opening_key* key, plk_g2* h, plk_g2* beta_h
 }
 
 int plk_opening_key_destroy(plk_opening_key* key) {
-  PLK_P_BEGIN
+  PLK_API_BEGIN
   if (!key) return PLK_E_ARG;
   if (key->device >= 0) {
     DeviceGuard g(key->device);
@@ -238,23 +204,23 @@ int plk_opening_key_destroy(plk_opening_key* key) {
   }
   delete key;
   return PLK_OK;
-  PLK_P_END
+  PLK_API_END
 }
 
 int plk_pairing_check(const plk_opening_key* key, const plk_kzg_pair* pair, int* ok) {
-  PLK_P_BEGIN
+  PLK_API_BEGIN
   if (!key || !pair || !ok) return PLK_E_ARG;
   G1In c, w;
   int st;
   if ((st = g1_from_abi(pair->c, c)) || (st = g1_from_abi(pair->w, w))) return st;
   *ok = pairing_check_host(&key->tab[kTabH], &key->tab[kTabB], &key->tab[kTabFrob], c, w) ? 1 : 0;
   return PLK_OK;
-  PLK_P_END
+  PLK_API_END
 }
 
 int plk_pairing_check_batch(plk_ctx* ctx, plk_opening_key* key, const plk_kzg_pair* pairs,
                             size_t count, uint8_t* ok) {
-  PLK_P_BEGIN
+  PLK_API_BEGIN
   if (!ctx || !key || !pairs || !ok || count == 0 || count > (1u << 24)) return PLK_E_ARG;
   for (size_t j = 0; j < count; ++j) {
     G1In t;
@@ -273,7 +239,7 @@ int plk_pairing_check_batch(plk_ctx* ctx, plk_opening_key* key, const plk_kzg_pa
   float ms;
   pairing_last_ms(key, &ms);
   return PLK_OK;
-  PLK_P_END
+  PLK_API_END
 }
 
 int plk_opening_key_last_pairing_ms(const plk_opening_key* key, float* kernel_ms) {
@@ -283,7 +249,7 @@ int plk_opening_key_last_pairing_ms(const plk_opening_key* key, float* kernel_ms
 }
 
 int plk_debug_pairing(plk_ctx* ctx, const plk_g1* p, const plk_g2* q, size_t n, uint64_t* out) {
-  PLK_P_BEGIN
+  PLK_API_BEGIN
   if (!p || !q || !out || n == 0 || n > 4096) return PLK_E_ARG;
   G2Aff qa;
   int st;
@@ -316,7 +282,7 @@ int plk_debug_pairing(plk_ctx* ctx, const plk_g1* p, const plk_g2* q, size_t n, 
   PLK_HIP_TRY(hipMemcpyAsync(out, d_out.ptr, n * 72 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
   PLK_HIP_TRY(stream_wait(s));
   return PLK_OK;
-  PLK_P_END
+  PLK_API_END
 }
 
 }  // extern "C"

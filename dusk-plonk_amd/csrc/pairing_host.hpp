@@ -1,6 +1,6 @@
 // pairing_host.hpp — the host-only half of the pairing: affine G2 arithmetic (one Fp2 inversion
 // per step; it runs once per key), the preparation of a G2 point into its Miller-loop lines, the
-// ABI conversions and the host pairing check. Plain C++ (no HIP): pairing.hip includes it, and so
+// ABI conversions (on abi.hpp) and the host pairing check. Plain C++ (no HIP): pairing.hip includes it, and so
 // does tools/pairing_selftest.cpp, which runs it under the host sanitizers.
 #pragma once
 #include <string.h>
@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/plk.h"
+#include "abi.hpp"
 #include "pairing.hpp"
 
 namespace plk {
@@ -47,8 +48,7 @@ inline G2Aff g2_infinity() { return {f2_zero(), f2_zero(), true}; }
 // y^2 = x^3 + 4 xi
 inline bool g2_on_curve(const G2Aff& q) {
   if (q.inf) return true;
-  const Fp four = fe_dbl(fe_dbl(fe_one<FpCfg>()));
-  const Fp2 b = f2_mul_xi({four, fe_zero<FpCfg>()});
+  const Fp2 b = f2_mul_xi({fp_four(), fe_zero<FpCfg>()});
   return f2_eq(f2_sqr(q.y), f2_add(f2_mul(f2_sqr(q.x), q.x), b));
 }
 
@@ -105,52 +105,21 @@ inline bool g2_prepare(const G2Aff& q, Fp2* out) {
   return idx == kMillerLines;
 }
 
-// ---- ABI conversions: 6 little-endian u64 Montgomery limbs are the memory image of Fp ---------
-inline Fp fp_from_abi(const uint64_t* l) {
-  Fp r;
-  for (int i = 0; i < 6; ++i) {
-    r.v[2 * i] = (uint32_t)l[i];
-    r.v[2 * i + 1] = (uint32_t)(l[i] >> 32);
-  }
-  return r;
-}
-
-inline void fp_to_abi(const Fp& a, uint64_t* l) {
-  for (int i = 0; i < 6; ++i) l[i] = (uint64_t)a.v[2 * i] | ((uint64_t)a.v[2 * i + 1] << 32);
-}
-
-inline bool fp_canonical(const Fp& a) {
-  uint32_t borrow = 0;
-  for (int i = 0; i < 12; ++i) {
-    const uint64_t t = (uint64_t)a.v[i] - FpCfg::P[i] - borrow;
-    borrow = (uint32_t)(t >> 63);
-  }
-  return borrow != 0;
-}
-
-// PLK_E_ARG: an infinity word other than 0 / 1, a finite point with a limb >= p or off
-// y^2 = x^3 + 4 (plk_msm_points' contract)
+// ---- ABI conversions (abi.hpp) ----------------------------------------------------------------
+// PLK_E_ARG for a point g1_load<true> refuses (plk_msm_points' contract)
 inline int g1_from_abi(const plk_g1& p, G1In& o) {
-  o.x = o.y = fe_zero<FpCfg>();
-  o.inf = true;
-  if (p.infinity == 1) return PLK_OK;
-  if (p.infinity != 0) return PLK_E_ARG;
-  o.x = fp_from_abi(p.x);
-  o.y = fp_from_abi(p.y);
-  o.inf = false;
-  if (!fp_canonical(o.x) || !fp_canonical(o.y)) return PLK_E_ARG;
-  const Fp four = fe_dbl(fe_dbl(fe_one<FpCfg>()));
-  if (!fe_eq(fe_sqr(o.y), fe_add(fe_mul(fe_sqr(o.x), o.x), four))) return PLK_E_ARG;
-  return PLK_OK;
+  const G1Abi a = g1_load<true>(&p);
+  o = {a.x, a.y, a.inf};
+  return a.ok ? PLK_OK : PLK_E_ARG;
 }
 
 // PLK_E_ARG unless q is finite, canonical and on the twist (the subgroup check is the caller's)
 inline int g2_from_abi(const plk_g2& q, G2Aff& o) {
   if (q.infinity != 0) return PLK_E_ARG;
-  o.x = {fp_from_abi(q.x), fp_from_abi(q.x + 6)};
-  o.y = {fp_from_abi(q.y), fp_from_abi(q.y + 6)};
+  o.x = {fe_of_abi<FpCfg>(q.x), fe_of_abi<FpCfg>(q.x + 6)};
+  o.y = {fe_of_abi<FpCfg>(q.y), fe_of_abi<FpCfg>(q.y + 6)};
   o.inf = false;
-  if (!fp_canonical(o.x.c0) || !fp_canonical(o.x.c1) || !fp_canonical(o.y.c0) || !fp_canonical(o.y.c1))
+  if (!fe_canonical(o.x.c0) || !fe_canonical(o.x.c1) || !fe_canonical(o.y.c0) || !fe_canonical(o.y.c1))
     return PLK_E_ARG;
   return g2_on_curve(o) ? PLK_OK : PLK_E_ARG;
 }
@@ -161,10 +130,10 @@ inline void g2_to_abi(const G2Aff& q, plk_g2* o) {
     o->infinity = 1;
     return;
   }
-  fp_to_abi(q.x.c0, o->x);
-  fp_to_abi(q.x.c1, o->x + 6);
-  fp_to_abi(q.y.c0, o->y);
-  fp_to_abi(q.y.c1, o->y + 6);
+  fe_to_abi(q.x.c0, o->x);
+  fe_to_abi(q.x.c1, o->x + 6);
+  fe_to_abi(q.y.c0, o->y);
+  fe_to_abi(q.y.c1, o->y + 6);
 }
 
 // ---- zkcrypto's G2 byte forms (include/plk.h "An SRS from bytes") -----------------------------
@@ -254,12 +223,11 @@ inline int g2_from_bytes(const uint8_t* in, bool compressed, G2Aff& o) {
   memcpy(first, in, 48);
   first[0] &= 0x1f;
   const Fp xc1 = fp_from_be(first), xc0 = fp_from_be(in + 48);
-  if (!fp_canonical(xc1) || !fp_canonical(xc0)) return PLK_E_ARG;
+  if (!fe_canonical(xc1) || !fe_canonical(xc0)) return PLK_E_ARG;
   o.x = {fe_to_mont(xc0), fe_to_mont(xc1)};
   o.inf = false;
   if (compressed) {
-    const Fp four = fe_dbl(fe_dbl(fe_one<FpCfg>()));
-    const Fp2 rhs = f2_add(f2_mul(f2_sqr(o.x), o.x), f2_mul_xi({four, fe_zero<FpCfg>()}));
+    const Fp2 rhs = f2_add(f2_mul(f2_sqr(o.x), o.x), f2_mul_xi({fp_four(), fe_zero<FpCfg>()}));
     Fp2 y;
     if (!f2_sqrt(rhs, y)) return PLK_E_ARG;
     if (g2_y_is_larger(y) != ((flags & 0x20) != 0)) y = f2_neg(y);
@@ -267,7 +235,7 @@ inline int g2_from_bytes(const uint8_t* in, bool compressed, G2Aff& o) {
     return PLK_OK;
   }
   const Fp yc1 = fp_from_be(in + 96), yc0 = fp_from_be(in + 144);
-  if (!fp_canonical(yc1) || !fp_canonical(yc0)) return PLK_E_ARG;
+  if (!fe_canonical(yc1) || !fe_canonical(yc0)) return PLK_E_ARG;
   o.y = {fe_to_mont(yc0), fe_to_mont(yc1)};
   return g2_on_curve(o) ? PLK_OK : PLK_E_ARG;
 }
@@ -305,8 +273,8 @@ inline void pairing_value_host(const Fp2* lines, const Fp2* frob, const G1In& p,
   const int r = f12_final_exp(m, frob);
   for (int i = 0; i < 6; ++i) {
     const Fp2 a = m.ld(r, i);
-    fp_to_abi(a.c0, out + 12 * i);
-    fp_to_abi(a.c1, out + 12 * i + 6);
+    fe_to_abi(a.c0, out + 12 * i);
+    fe_to_abi(a.c1, out + 12 * i + 6);
   }
 }
 

@@ -27,19 +27,6 @@ Fr fr_u64(uint64_t v) {
   x.v[1] = (uint32_t)(v >> 32);
   return fe_to_mont(x);
 }
-Fr fr_from(const plk_fr& a) {
-  Fr r;
-  for (int i = 0; i < 4; ++i) {
-    r.v[2 * i] = (uint32_t)a.l[i];
-    r.v[2 * i + 1] = (uint32_t)(a.l[i] >> 32);
-  }
-  return r;
-}
-plk_fr fr_to(const Fr& a) {
-  plk_fr r;
-  for (int i = 0; i < 4; ++i) r.l[i] = (uint64_t)a.v[2 * i] | ((uint64_t)a.v[2 * i + 1] << 32);
-  return r;
-}
 bool fr_eq(const Fr& a, const Fr& b) { return fe_eq(a, b); }
 
 // SplitMix64 -> uniform Fr (4 words, top masked to 255 bits, rejection), Montgomery out.
@@ -54,45 +41,19 @@ struct Rng {
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
     return z ^ (z >> 31);
   }
-  Fr fr() {
+  // 255 random bits below r, as they come (rejection)
+  Fr below_r() {
     for (;;) {
-      Fr c;
-      for (int i = 0; i < 4; ++i) {
-        const uint64_t w = next();
-        c.v[2 * i] = (uint32_t)w;
-        c.v[2 * i + 1] = (uint32_t)(w >> 32);
-      }
+      const uint64_t w[4] = {next(), next(), next(), next()};
+      Fr c = fe_of_abi<FrCfg>(w);
       c.v[7] &= 0x7fffffffu;
-      bool lt = false;
-      for (int i = 7; i >= 0; --i)
-        if (c.v[i] != FrCfg::P[i]) {
-          lt = c.v[i] < FrCfg::P[i];
-          break;
-        }
-      if (lt) return fe_to_mont(c);
+      if (fe_canonical(c)) return c;
     }
   }
+  Fr fr() { return fe_to_mont(below_r()); }
   // uniform Fr drawn directly as its Montgomery image (x -> xR is a bijection of Fr), so no
   // multiply: used for the synthetic circuit's witnesses
-  Fr fr_mont() {
-    for (;;) {
-      Fr c;
-      for (int i = 0; i < 4; ++i) {
-        const uint64_t w = next();
-        c.v[2 * i] = (uint32_t)w;
-        c.v[2 * i + 1] = (uint32_t)(w >> 32);
-      }
-      c.v[7] &= 0x7fffffffu;
-      if (c.v[7] < FrCfg::P[7]) return c;  // top word strictly below: c < r
-      if (c.v[7] == FrCfg::P[7]) {
-        for (int i = 6; i >= 0; --i)
-          if (c.v[i] != FrCfg::P[i]) {
-            if (c.v[i] < FrCfg::P[i]) return c;
-            break;
-          }
-      }
-    }
-  }
+  Fr fr_mont() { return below_r(); }
 };
 
 enum { QM = 0, QL, QR, QO, Q4, QC, QARITH, QRANGE, QLOGIC, QFIXED, QVAR };
@@ -278,13 +239,13 @@ Gate gate_from(const plk_constraint* s) {
   Gate g = default_gate();
   const plk_fr* qs[11] = {&s->q_m, &s->q_l, &s->q_r, &s->q_o, &s->q_4, &s->q_c, &s->q_arith,
                           &s->q_range, &s->q_logic, &s->q_fixed_group_add, &s->q_variable_group_add};
-  for (int i = 0; i < 11; ++i) g.q[i] = fr_from(*qs[i]);
+  for (int i = 0; i < 11; ++i) g.q[i] = fr_from_abi(*qs[i]);
   g.w[0] = s->a;
   g.w[1] = s->b;
   g.w[2] = s->o;
   g.w[3] = s->d;
   g.has_pi = s->has_public != 0;
-  g.pi = fr_from(s->public_input);
+  g.pi = fr_from_abi(s->public_input);
   return g;
 }
 
@@ -593,20 +554,20 @@ int plk_composer_size(const plk_composer* c, size_t* gates, size_t* witnesses) {
 
 int plk_composer_append_witness(plk_composer* c, const plk_fr* v, uint32_t* wire) {
   if (!c || !v || !wire) return PLK_E_ARG;
-  *wire = append_witness(c, fr_from(*v));
+  *wire = append_witness(c, fr_from_abi(*v));
   return PLK_OK;
 }
 
 int plk_composer_witness_value(const plk_composer* c, uint32_t wire, plk_fr* v) {
   if (!c || !v || wire >= c->witness.size()) return PLK_E_ARG;
-  *v = fr_to(c->witness[wire]);
+  *v = fr_to_abi(c->witness[wire]);
   return PLK_OK;
 }
 
 // lib.rs:708-719: witness + assert_equal_constant(w, 0, Some(-public))
 int plk_composer_append_public(plk_composer* c, const plk_fr* v, uint32_t* wire) {
   if (!c || !v || !wire) return PLK_E_ARG;
-  const Fr val = fr_from(*v);
+  const Fr val = fr_from_abi(*v);
   *wire = append_witness(c, val);
   const Fr neg = fe_neg(val);
   assert_equal_constant(c, *wire, fe_zero<FrCfg>(), &neg);
@@ -651,8 +612,8 @@ int plk_composer_assert_equal(plk_composer* c, uint32_t a, uint32_t b) {
 int plk_composer_assert_equal_constant(plk_composer* c, uint32_t a, const plk_fr* constant,
                                        const plk_fr* public_input) {
   if (!c || !constant || a >= c->witness.size()) return PLK_E_ARG;
-  const Fr pi = public_input ? fr_from(*public_input) : fe_zero<FrCfg>();
-  assert_equal_constant(c, a, fr_from(*constant), public_input ? &pi : nullptr);
+  const Fr pi = public_input ? fr_from_abi(*public_input) : fe_zero<FrCfg>();
+  assert_equal_constant(c, a, fr_from_abi(*constant), public_input ? &pi : nullptr);
   return PLK_OK;
 }
 
@@ -750,7 +711,7 @@ int plk_composer_synthetic_chain(plk_composer* c, size_t gates, uint64_t seed) {
 // re-synthesizes the circuit with new witnesses, prover.rs:76-78).
 int plk_composer_set_witness(plk_composer* c, uint32_t wire, const plk_fr* v) {
   if (!c || !v || wire >= c->witness.size()) return PLK_E_ARG;
-  c->witness[wire] = fr_from(*v);
+  c->witness[wire] = fr_from_abi(*v);
   return PLK_OK;
 }
 
@@ -762,7 +723,7 @@ int plk_composer_public_inputs(const plk_composer* c, plk_fr* values, uint64_t* 
   for (size_t i = 0; i < c->gates.size(); ++i) {
     if (!(c->gates[i].code & kPiBit)) continue;
     if (k < cap) {
-      if (values) values[k] = fr_to(gate_unpack(c, i).pi);
+      if (values) values[k] = fr_to_abi(gate_unpack(c, i).pi);
       if (indexes) indexes[k] = i;
     }
     ++k;
@@ -784,26 +745,26 @@ int plk_composer_export(const plk_composer* c, plk_constraint* gates, size_t cap
       plk_fr* qs[11] = {&o.q_m,     &o.q_l,   &o.q_r,     &o.q_o,
                         &o.q_4,     &o.q_c,   &o.q_arith, &o.q_range,
                         &o.q_logic, &o.q_fixed_group_add, &o.q_variable_group_add};
-      for (int q = 0; q < 11; ++q) *qs[q] = fr_to(g.q[q]);
+      for (int q = 0; q < 11; ++q) *qs[q] = fr_to_abi(g.q[q]);
       o.a = g.w[0];
       o.b = g.w[1];
       o.o = g.w[2];
       o.d = g.w[3];
       o.has_public = g.has_pi ? 1u : 0u;
       o._pad = 0;
-      o.public_input = fr_to(g.pi);
+      o.public_input = fr_to_abi(g.pi);
     }
   }
   if (witness) {
     const size_t cnt = std::min(wcap, c->witness.size());
-    for (size_t j = 0; j < cnt; ++j) witness[j] = fr_to(c->witness[j]);
+    for (size_t j = 0; j < cnt; ++j) witness[j] = fr_to_abi(c->witness[j]);
   }
   return PLK_OK;
 }
 
 // ---------------------------------------------------------------------------- key
 int plk_key_compile(plk_srs* srs, const plk_composer* cs, const char* label, plk_key** out) {
-  try {
+  PLK_API_BEGIN
     if (!srs || !cs || !out) return PLK_E_ARG;
     *out = nullptr;
     plk_ctx* ctx = srs->ctx;
@@ -981,11 +942,7 @@ int plk_key_compile(plk_srs* srs, const plk_composer* cs, const char* label, plk
     PLK_HIP_TRY(stream_wait(s));
     *out = key.release();
     return PLK_OK;
-  } catch (const std::bad_alloc&) {
-    return PLK_E_OOM;
-  } catch (...) {
-    return PLK_E_DEVICE;
-  }
+  PLK_API_END
 }
 
 int plk_key_destroy(plk_key* key) {
@@ -1006,7 +963,7 @@ int plk_key_info(const plk_key* key, uint64_t* n, uint64_t* m, plk_g1* commitmen
 
 // ----------------------------------------------------------------------- prover
 int plk_prover_create(plk_key* key, plk_prover** out) {
-  try {
+  PLK_API_BEGIN
     if (!key || !out) return PLK_E_ARG;
     *out = nullptr;
     DeviceGuard guard(key->ctx->device);
@@ -1021,9 +978,7 @@ int plk_prover_create(plk_key* key, plk_prover** out) {
     p->own_stream = true;
     *out = p.release();
     return PLK_OK;
-  } catch (const std::bad_alloc&) {
-    return PLK_E_OOM;
-  }
+  PLK_API_END
 }
 
 int plk_prover_destroy(plk_prover* p) {
@@ -1090,27 +1045,25 @@ int plk_prover_shard_buckets(plk_prover* p, int rank, int world, plk_allgather_f
 
 int plk_prove(plk_key* key, const plk_composer* cs, uint64_t seed, plk_proof* proof,
               plk_fr* public_inputs, size_t pi_cap, size_t* pi_count) {
+  PLK_API_BEGIN
   if (!key) return PLK_E_ARG;
   // the default prover's scratch, workspace and stream serve one proof at a time: concurrent
   // plk_prove calls on one key run one after the other (plk_prover_create gives parallel lanes)
   std::lock_guard<std::mutex> lk(key->def_mu);
   if (!key->def_prover) {
-    try {
-      std::unique_ptr<plk_prover> d(new plk_prover());
-      d->key = key;
-      d->ws = msm_workspace_new();
-      d->stream = key->ctx->stream;  // the context's stream, not owned
-      key->def_prover = std::move(d);
-    } catch (const std::bad_alloc&) {
-      return PLK_E_OOM;
-    }
+    std::unique_ptr<plk_prover> d(new plk_prover());
+    d->key = key;
+    d->ws = msm_workspace_new();
+    d->stream = key->ctx->stream;  // the context's stream, not owned
+    key->def_prover = std::move(d);
   }
   return plk_prover_prove(key->def_prover.get(), cs, seed, proof, public_inputs, pi_cap, pi_count);
+  PLK_API_END
 }
 
 int plk_prover_prove(plk_prover* P, const plk_composer* cs, uint64_t seed, plk_proof* proof,
                      plk_fr* public_inputs, size_t pi_cap, size_t* pi_count) {
-  try {
+  PLK_API_BEGIN
     if (!P || !cs || !proof) return PLK_E_ARG;
     plk_key* key = P->key;
     // the proving circuit must have the key's structure (prover.rs:114-119 gathers the
@@ -1173,7 +1126,7 @@ int plk_prover_prove(plk_prover* P, const plk_composer* cs, uint64_t seed, plk_p
     for (auto& p : pis) tr.append_scalar("pi", p.second);
     if (pi_count) *pi_count = pis.size();
     if (public_inputs)
-      for (size_t i = 0; i < pis.size() && i < pi_cap; ++i) public_inputs[i] = fr_to(pis[i].second);
+      for (size_t i = 0; i < pis.size() && i < pi_cap; ++i) public_inputs[i] = fr_to_abi(pis[i].second);
 
     // ---- round 1: wires -> idft -> blind(1) -> commit (prover.rs:107-158)
     {  // witness upload through pinned staging, in chunks: the CPU copy of chunk i+1
@@ -1603,28 +1556,24 @@ int plk_prover_prove(plk_prover* P, const plk_composer* cs, uint64_t seed, plk_p
     proof->t_4_comm = tcom[3];
     proof->w_z_chall_comm = wcm[0];
     proof->w_z_chall_w_comm = wcm[1];
-    proof->a_eval = fr_to(a_e);
-    proof->b_eval = fr_to(b_e);
-    proof->c_eval = fr_to(c_e);
-    proof->d_eval = fr_to(d_e);
-    proof->a_next_eval = fr_to(an_e);
-    proof->b_next_eval = fr_to(bn_e);
-    proof->d_next_eval = fr_to(dn_e);
-    proof->q_arith_eval = fr_to(qar_e);
-    proof->q_c_eval = fr_to(qc_e);
-    proof->q_l_eval = fr_to(ql_e);
-    proof->q_r_eval = fr_to(qr_e);
-    proof->s_sigma_1_eval = fr_to(s1_e);
-    proof->s_sigma_2_eval = fr_to(s2_e);
-    proof->s_sigma_3_eval = fr_to(s3_e);
-    proof->r_poly_eval = fr_to(r_e);
-    proof->perm_eval = fr_to(perm_e);
+    proof->a_eval = fr_to_abi(a_e);
+    proof->b_eval = fr_to_abi(b_e);
+    proof->c_eval = fr_to_abi(c_e);
+    proof->d_eval = fr_to_abi(d_e);
+    proof->a_next_eval = fr_to_abi(an_e);
+    proof->b_next_eval = fr_to_abi(bn_e);
+    proof->d_next_eval = fr_to_abi(dn_e);
+    proof->q_arith_eval = fr_to_abi(qar_e);
+    proof->q_c_eval = fr_to_abi(qc_e);
+    proof->q_l_eval = fr_to_abi(ql_e);
+    proof->q_r_eval = fr_to_abi(qr_e);
+    proof->s_sigma_1_eval = fr_to_abi(s1_e);
+    proof->s_sigma_2_eval = fr_to_abi(s2_e);
+    proof->s_sigma_3_eval = fr_to_abi(s3_e);
+    proof->r_poly_eval = fr_to_abi(r_e);
+    proof->perm_eval = fr_to_abi(perm_e);
     return PLK_OK;
-  } catch (const std::bad_alloc&) {
-    return PLK_E_OOM;
-  } catch (...) {
-    return PLK_E_DEVICE;
-  }
+  PLK_API_END
 }
 
 }  // extern "C"

@@ -66,7 +66,6 @@ __device__ __forceinline__ RFr rx_norm(const RFr& a) {
   return r;
 }
 
-inline uint32_t blocks_for(uint64_t n, uint32_t bs) { return (uint32_t)((n + bs - 1) / bs); }
 
 // ---------------------------------------------------------------------------- wires
 __global__ void k_gather_wires(const Fr* __restrict__ witness, const uint32_t* __restrict__ idx,
@@ -717,7 +716,7 @@ __global__ void __launch_bounds__(256) k_scale_powers(const Fr* __restrict__ c, 
 // ============================================================== host launchers
 int pk_gather_wires(const Fr* witness, const uint32_t* idx, uint64_t m, uint64_t n, Fr* out,
                     uint64_t stride, hipStream_t s) {
-  hipLaunchKernelGGL(k_gather_wires, dim3(blocks_for(n, 256), 4), dim3(256), 0, s, witness, idx, m,
+  hipLaunchKernelGGL(k_gather_wires, dim3(cdiv(n, 256), 4), dim3(256), 0, s, witness, idx, m,
                      n, out, stride);
   PLK_HIP_TRY(hipGetLastError());
   return PLK_OK;
@@ -731,7 +730,7 @@ int pk_blind(Fr* poly, uint64_t n, const BlindArgs& b, hipStream_t s) {
 
 int pk_pi_coef(const PiDirect& pd, const Fr* tw_inv, uint64_t n, Fr* out, hipStream_t s) {
   if (pd.count > (uint32_t)kPiDirect || (n & (n - 1))) return PLK_E_ARG;
-  hipLaunchKernelGGL(k_pi_coef, dim3(blocks_for(n, 256)), dim3(256), 0, s, pd, tw_inv, n, out);
+  hipLaunchKernelGGL(k_pi_coef, dim3(cdiv(n, 256)), dim3(256), 0, s, pd, tw_inv, n, out);
   PLK_HIP_TRY(hipGetLastError());
   return PLK_OK;
 }
@@ -739,7 +738,7 @@ int pk_pi_coef(const PiDirect& pd, const Fr* tw_inv, uint64_t n, Fr* out, hipStr
 int pk_pi_sparse(const PiSparse& ps, const Fr* l1, uint32_t log_n, uint64_t nq, Fr* out,
                  hipStream_t s) {
   if (ps.count == 0 || ps.count > (uint32_t)kPiSparse) return PLK_E_ARG;
-  hipLaunchKernelGGL(k_pi_sparse, dim3(blocks_for(nq, 256)), dim3(256), 0, s, ps, l1, log_n, nq,
+  hipLaunchKernelGGL(k_pi_sparse, dim3(cdiv(nq, 256)), dim3(256), 0, s, ps, l1, log_n, nq,
                      out);
   PLK_HIP_TRY(hipGetLastError());
   return PLK_OK;
@@ -752,7 +751,7 @@ int pk_blind_batch(const BlindBatch& bb, uint64_t n, hipStream_t s) {
 }
 
 int pk_fill(Fr* out, const Fr& v, uint64_t n, hipStream_t s) {
-  hipLaunchKernelGGL(k_fill, dim3(blocks_for(n, 256)), dim3(256), 0, s, out, v, n);
+  hipLaunchKernelGGL(k_fill, dim3(cdiv(n, 256)), dim3(256), 0, s, out, v, n);
   PLK_HIP_TRY(hipGetLastError());
   return PLK_OK;
 }
@@ -763,7 +762,7 @@ int pk_perm_numden(const Fr* wires, uint64_t wire_stride, const Fr* sigmas, cons
   Fr fix = fe_zero<FrCfg>();  // 2^276 mod r = R'^4 / R^3 (k_perm_numden)
   fix.v[0] = 1;
   for (int b = 0; b < 4 * RxShape<FrCfg>::B * RxShape<FrCfg>::L - 3 * 256; ++b) fix = fe_dbl(fix);
-  hipLaunchKernelGGL(k_perm_numden, dim3(blocks_for(n, 256)), dim3(256), 0, s, wires, wire_stride,
+  hipLaunchKernelGGL(k_perm_numden, dim3(cdiv(n, 256)), dim3(256), 0, s, wires, wire_stride,
                      sigmas, elements, n, fe_to_rx_domain(beta), gamma, fe_to_rx_domain(k1),
                      fe_to_rx_domain(k2), fe_to_rx_domain(k3), fix, num, den);
   PLK_HIP_TRY(hipGetLastError());
@@ -771,7 +770,7 @@ int pk_perm_numden(const Fr* wires, uint64_t wire_stride, const Fr* sigmas, cons
 }
 
 int pk_mul3(const Fr* a, const Fr* b, const Fr& c, Fr* out, uint64_t n, hipStream_t s) {
-  hipLaunchKernelGGL(k_mul3, dim3(blocks_for(n, 256)), dim3(256), 0, s, a, b, c, out, n);
+  hipLaunchKernelGGL(k_mul3, dim3(cdiv(n, 256)), dim3(256), 0, s, a, b, c, out, n);
   PLK_HIP_TRY(hipGetLastError());
   return PLK_OK;
 }
@@ -815,7 +814,7 @@ int pk_scan(const Fr* in, Fr* out, uint64_t n, bool mul, bool suffix, bool exclu
 
 int pk_coset_combine(const Fr* in, uint64_t n, int blocks, const CombineMat& mat, Fr* out,
                      hipStream_t s) {
-  const dim3 grid(blocks_for(n, 256));
+  const dim3 grid(cdiv(n, 256));
   if (blocks == kQBlocks)
     hipLaunchKernelGGL((k_coset_combine<kQBlocks>), grid, dim3(256), 0, s, in, n, mat, out);
   else if (blocks == kQBlocksSmall)
@@ -827,7 +826,7 @@ int pk_coset_combine(const Fr* in, uint64_t n, int blocks, const CombineMat& mat
 }
 
 int pk_quotient(const QuotientArgs& q, hipStream_t s) {
-  const dim3 grid(blocks_for(q.nq, 256));
+  const dim3 grid(cdiv(q.nq, 256));
   if (q.has_logic || q.has_fixed || q.has_var) {
     hipLaunchKernelGGL((k_quotient<false>), grid, dim3(256), 0, s, q);
     hipLaunchKernelGGL(k_quotient_ext, grid, dim3(256), 0, s, q);
@@ -844,7 +843,7 @@ uint32_t pk_eval_max_blocks(uint64_t max_len) {
 
 int pk_scale_copy(const Fr* in, const Fr& c, Fr* out, uint64_t n, hipStream_t s) {
   if (n == 0) return PLK_OK;
-  hipLaunchKernelGGL(k_scale_copy, dim3(blocks_for(n, 256)), dim3(256), 0, s, in, c, out, n);
+  hipLaunchKernelGGL(k_scale_copy, dim3(cdiv(n, 256)), dim3(256), 0, s, in, c, out, n);
   PLK_HIP_TRY(hipGetLastError());
   return PLK_OK;
 }
@@ -864,7 +863,7 @@ int pk_lincomb(const LinComb& lc, Fr* out, uint64_t len_out, hipStream_t s) {
   if (len_out == 0) return PLK_OK;
   LinComb lr = lc;  // scalars in the R' domain (k_lincomb)
   for (uint32_t t = 0; t < lc.terms; ++t) lr.s[t] = fe_to_rx_domain(lc.s[t]);
-  hipLaunchKernelGGL(k_lincomb, dim3(blocks_for(len_out, 256)), dim3(256), 0, s, lr, out, len_out);
+  hipLaunchKernelGGL(k_lincomb, dim3(cdiv(len_out, 256)), dim3(256), 0, s, lr, out, len_out);
   PLK_HIP_TRY(hipGetLastError());
   return PLK_OK;
 }
@@ -876,7 +875,7 @@ int pk_scale_powers(const Fr* c, uint64_t len, const Fr& x, uint64_t shift, Fr* 
   Fr x4096 = x16;
   for (int i = 0; i < 8; ++i) x4096 = fe_sqr(x4096);
   const Fr xshift = fe_pow_u64(x, shift);
-  hipLaunchKernelGGL(k_scale_powers, dim3(blocks_for((len + 15) / 16, 256)), dim3(256), 0, s, c, len,
+  hipLaunchKernelGGL(k_scale_powers, dim3(cdiv((len + 15) / 16, 256)), dim3(256), 0, s, c, len,
                      fe_to_rx_domain(x), fe_to_rx_domain(x16), fe_to_rx_domain(x4096),
                      fe_to_rx_domain(xshift), y);
   PLK_HIP_TRY(hipGetLastError());

@@ -203,20 +203,8 @@ int srs_generate(plk_srs* s, const Fr& tau_mont, uint64_t start, hipStream_t str
   DevBuf temp, pref;
   if ((st = temp.alloc(n * sizeof(G1xyzz)))) return st;
   if ((st = pref.alloc(n * sizeof(Fp)))) return st;
-  // G1 generator (Montgomery form)
-  static const uint32_t gx[12] = {0xdb22c6bbu, 0xfb3af00au, 0xf97a1aefu, 0x6c55e83fu,
-                                  0x171bac58u, 0xa14e3a3fu, 0x9774b905u, 0xc3688c4fu,
-                                  0x4fa9ac0fu, 0x2695638cu, 0x3197d794u, 0x17f1d3a7u};
-  static const uint32_t gy[12] = {0x46c5e7e1u, 0x0caa2329u, 0xa2888ae4u, 0xd03cc744u,
-                                  0x2c04b3edu, 0x00db18cbu, 0xd5d00af6u, 0xfcf5e095u,
-                                  0x741d8ae4u, 0xa09e30edu, 0xe3aaa0f1u, 0x08b3f481u};
   G1Affine gen;
-  for (int i = 0; i < 12; ++i) {
-    gen.x.v[i] = gx[i];
-    gen.y.v[i] = gy[i];
-  }
-  gen.x = fe_to_mont(gen.x);
-  gen.y = fe_to_mont(gen.y);
+  g1_generator(gen.x, gen.y);
   hipLaunchKernelGGL(k_srs_powers, dim3(cdiv(n, 128)), dim3(128), 0, stream, tau_mont, gen,
                      start, (uint64_t)n, temp.as<G1xyzz>());
   hipLaunchKernelGGL(k_batch_affine, dim3(cdiv(cdiv(n, kBatchAff), 128)), dim3(128), 0, stream,

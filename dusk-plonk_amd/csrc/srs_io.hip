@@ -3,8 +3,8 @@
 //  - plk_srs_load_bytes: the ceremony's bytes are uploaded and decoded one point per lane straight
 //    into the SRS's device arrays (G1Affine limbs and the infinity bytes). The compressed form is
 //    k_g1_decompress's per-lane function (ingest_math.hpp g1_decompress_words) in the SRS's layout;
-//    the uncompressed form is g1_decode_raw_words: byte swap, strict flags, range, curve equation,
-//    Montgomery form. The subgroup test is g1_in_subgroup, as k_g1_subgroup.
+//    the uncompressed form is g1_decode_raw_words: strict flags, then abi.hpp's byte swap, range
+//    test and curve equation, Montgomery form. The item loads and the encoder's words are abi.hpp's. The subgroup test is g1_in_subgroup, as k_g1_subgroup.
 //  - No status array: a rejecting lane folds (index << 8 | status) into one 64-bit word with an
 //    atomic minimum, so the host reads 8 bytes whatever n is, and the smallest index wins. A
 //    rejected point gets the infinity byte kRejected, which keeps the later kernels of the same
@@ -19,12 +19,9 @@
 //    the device, one scalar multiplication per point (g1_mul.hip), the opening key and the witness
 //    [s]H on the host (g2_mul); the verification is plk_srs_verify plus one host pairing check on
 //    the temporary key (H, witness).
-#include <sys/random.h>
-
 #include <chrono>
 #include <cstring>
 #include <new>
-#include <random>
 #include <vector>
 
 #include "ingest_math.hpp"
@@ -47,8 +44,6 @@ constexpr uint8_t kBadPoint = 0xff;             // k_srs_validate's status (inge
 constexpr unsigned long long kNoBad = ~0ull;
 
 static_assert(sizeof(G1Affine) == 96, "SRS point layout");
-
-inline uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + kBlock - 1) / kBlock); }
 
 // ---- shared math ------------------------------------------------------------------------------
 // 96 uncompressed bytes as the 24 words read little-endian from memory -> Montgomery (x, y) or
@@ -76,32 +71,9 @@ PLK_HD uint8_t g1_decode_raw_words(const uint32_t (&w)[24], Fp& x, Fp& y, bool& 
   return PLK_INGEST_OK;
 }
 
-// Montgomery value -> the 12 words of its 48 big-endian bytes
-PLK_HD void fp_to_be_words(const Fp& a_mont, uint32_t* out) {
-  const Fp a = fe_from_mont(a_mont);
-#pragma unroll
-  for (int k = 0; k < 12; ++k) {
-    const uint32_t v = a.v[11 - k];
-    out[k] = (v >> 24) | ((v >> 8) & 0xff00u) | ((v << 8) & 0xff0000u) | (v << 24);
-  }
-}
-
 // ---- kernels ----------------------------------------------------------------------------------
 __device__ __forceinline__ void report(unsigned long long* bad, uint64_t index, uint8_t status) {
   atomicMin(bad, (unsigned long long)((index << 8) | status));
-}
-
-template <int kWords>
-__device__ __forceinline__ void ld_words(const uint8_t* p, uint32_t (&w)[kWords]) {
-  const uint4* src = reinterpret_cast<const uint4*>(p);  // 16-B aligned: 48 t / 96 t of a hipMalloc
-#pragma unroll
-  for (int i = 0; i < kWords / 4; ++i) {
-    const uint4 q = src[i];
-    w[4 * i] = q.x;
-    w[4 * i + 1] = q.y;
-    w[4 * i + 2] = q.z;
-    w[4 * i + 3] = q.w;
-  }
 }
 
 __device__ __forceinline__ void st_decoded(uint64_t t, uint8_t st, const Fp& x, const Fp& y, bool is_inf,
@@ -118,7 +90,7 @@ __global__ void __launch_bounds__(kBlock) k_srs_decompress(const uint8_t* __rest
   const uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   if (t >= n) return;
   uint32_t w[12];
-  ld_words(in + t * kG1Comp, w);
+  ld_words(in + t * kG1Comp, w);  // 16-B aligned: 48 t of a hipMalloc
   Fp x, y;
   bool is_inf;
   const uint8_t st = g1_decompress_words(w, x, y, is_inf);
@@ -160,7 +132,7 @@ __global__ void __launch_bounds__(kBlock) k_srs_validate(const G1Affine* __restr
   if (t >= n || inf[t] != 0) return;
   Fp x, y;
   ld_aff(&pts[t], x, y);
-  if (!fe_canonical(x) || !fe_canonical(y) || !g1_on_curve(x, y)) report(bad, t, kBadPoint);
+  if (!g1_coords_valid(x, y)) report(bad, t, kBadPoint);
 }
 
 __global__ void __launch_bounds__(256) k_srs_scan_inf(const uint8_t* __restrict__ inf, uint64_t n,
@@ -170,7 +142,7 @@ __global__ void __launch_bounds__(256) k_srs_scan_inf(const uint8_t* __restrict_
   if (inf[t] != 0) report(bad, t, 0);
 }
 
-// out of Montgomery, big-endian; compressed: transcript_dev.hpp g1_compress_words (the sort bit
+// out of Montgomery, big-endian; compressed: abi.hpp g1_compress_words (the sort bit
 // from y > (p-1)/2), uncompressed: x then y with 0x40 alone for the identity
 __global__ void __launch_bounds__(kBlock) k_srs_encode(const G1Affine* __restrict__ pts,
                                                        const uint8_t* __restrict__ inf, uint64_t count,
@@ -199,18 +171,6 @@ __global__ void __launch_bounds__(kBlock) k_srs_encode(const G1Affine* __restric
 }
 
 // ---- host side --------------------------------------------------------------------------------
-struct Events {
-  hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-  int create() {
-    for (hipEvent_t& ev : e) PLK_HIP_TRY(hipEventCreate(&ev));
-    return PLK_OK;
-  }
-  ~Events() {
-    for (hipEvent_t ev : e)
-      if (ev) (void)hipEventDestroy(ev);
-  }
-};
-
 // the reduction word: cleared before a pass, read after it (the stream has been waited for)
 struct BadWord {
   DevBuf d;
@@ -233,22 +193,6 @@ struct BadWord {
   }
 };
 
-void srs_entropy(uint8_t seed[32]) {
-  size_t got = 0;
-  while (got < 32) {
-    const ssize_t r = getrandom(seed + got, 32 - got, 0);
-    if (r <= 0) break;
-    got += (size_t)r;
-  }
-  if (got < 32) {
-    std::random_device rd;
-    for (size_t i = 0; i < 32; i += 4) {
-      const uint32_t x = rd();
-      std::memcpy(seed + i, &x, 4);
-    }
-  }
-}
-
 // The root of the fold's weights: binds the label, the number of points and the seed. rho_i is
 // drawn from a clone after append_u64("index", i) (k_fold_rho / rho_host; rho_0 = 1).
 void fold_root(const uint8_t seed[32], uint64_t n, RhoPlan& plan) {
@@ -259,25 +203,19 @@ void fold_root(const uint8_t seed[32], uint64_t n, RhoPlan& plan) {
   rho_plan_compile(s.state(), s.pos(), s.pos_begin(), plan);
 }
 
-plk_g1 g1_identity() {
-  plk_g1 p;
-  std::memset(&p, 0, sizeof p);
-  p.infinity = 1;
-  return p;
-}
-
 // the caller holds the device guard
 int fold_run(plk_srs* s, const uint8_t* seed_or_null, plk_kzg_pair* out) {
   const size_t n = s->n;
   if (n == 1) {
-    out->c = out->w = g1_identity();
+    g1_store(fe_zero<FpCfg>(), fe_zero<FpCfg>(), false, &out->c);
+    out->w = out->c;
     return PLK_OK;
   }
   uint8_t seed[32];
   if (seed_or_null) {
     std::memcpy(seed, seed_or_null, 32);
   } else {
-    srs_entropy(seed);
+    os_entropy(seed);
   }
   RhoPlan rho;
   fold_root(seed, n, rho);
@@ -304,20 +242,6 @@ int fold_run(plk_srs* s, const uint8_t* seed_or_null, plk_kzg_pair* out) {
   return PLK_OK;
 }
 
-// the standard generator in the SRS's layout (Montgomery limbs)
-G1Affine g1_generator_aff() {
-  static const uint32_t gx[12] = {0xdb22c6bbu, 0xfb3af00au, 0xf97a1aefu, 0x6c55e83fu,
-                                  0x171bac58u, 0xa14e3a3fu, 0x9774b905u, 0xc3688c4fu,
-                                  0x4fa9ac0fu, 0x2695638cu, 0x3197d794u, 0x17f1d3a7u};
-  static const uint32_t gy[12] = {0x46c5e7e1u, 0x0caa2329u, 0xa2888ae4u, 0xd03cc744u,
-                                  0x2c04b3edu, 0x00db18cbu, 0xd5d00af6u, 0xfcf5e095u,
-                                  0x741d8ae4u, 0xa09e30edu, 0xe3aaa0f1u, 0x08b3f481u};
-  G1Affine g;
-  g.x = fe_to_mont(fp_const(gx));
-  g.y = fe_to_mont(fp_const(gy));
-  return g;
-}
-
 double ms_since(std::chrono::steady_clock::time_point t0) {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
@@ -331,8 +255,8 @@ void fr_from_entropy(Fr& out) {
   uint8_t buf[64];
   Fr lo, hi;
   do {
-    srs_entropy(buf);
-    srs_entropy(buf + 32);
+    os_entropy(buf);
+    os_entropy(buf + 32);
     for (int i = 0; i < 8; ++i) {
       std::memcpy(&lo.v[i], buf + 4 * i, 4);
       std::memcpy(&hi.v[i], buf + 32 + 4 * i, 4);
@@ -385,7 +309,7 @@ int srs_ensure_g1(plk_srs* srs, bool* any, uint64_t* idx) {
   *any = false;
   if (!srs->points_checked) {
     if ((st = bad.reset(s))) return st;
-    hipLaunchKernelGGL(k_srs_validate, dim3(blocks_for(n)), dim3(kBlock), 0, s, pts, inf, n, bad.dev());
+    hipLaunchKernelGGL(k_srs_validate, dim3(cdiv(n, kBlock)), dim3(kBlock), 0, s, pts, inf, n, bad.dev());
     PLK_HIP_TRY(hipGetLastError());
     if ((st = bad.read(s, any, idx, &code))) return st;
     if (*any) return PLK_OK;
@@ -393,7 +317,7 @@ int srs_ensure_g1(plk_srs* srs, bool* any, uint64_t* idx) {
   }
   if (!srs->subgroup_checked) {
     if ((st = bad.reset(s))) return st;
-    hipLaunchKernelGGL(k_srs_subgroup, dim3(blocks_for(n)), dim3(kBlock), 0, s, pts, inf, n, bad.dev());
+    hipLaunchKernelGGL(k_srs_subgroup, dim3(cdiv(n, kBlock)), dim3(kBlock), 0, s, pts, inf, n, bad.dev());
     PLK_HIP_TRY(hipGetLastError());
     if ((st = bad.read(s, any, idx, &code))) return st;
     if (*any) return PLK_OK;
@@ -405,21 +329,11 @@ int srs_ensure_g1(plk_srs* srs, bool* any, uint64_t* idx) {
 }  // namespace
 }  // namespace plk
 
-#define PLK_S_BEGIN try {
-#define PLK_S_END                 \
-  }                               \
-  catch (const std::bad_alloc&) { \
-    return PLK_E_OOM;             \
-  }                               \
-  catch (...) {                   \
-    return PLK_E_DEVICE;          \
-  }
-
 extern "C" {
 
 int plk_srs_load_bytes(plk_ctx* ctx, const uint8_t* in, size_t n_points, int format, int check_subgroup,
                        plk_srs** out, uint64_t* bad_index, uint8_t* bad_status) {
-  PLK_S_BEGIN
+  PLK_API_BEGIN
   if (!out) return PLK_E_ARG;
   *out = nullptr;
   if (!ctx || !in || n_points == 0 || n_points > kMaxPoints) return PLK_E_ARG;
@@ -429,7 +343,7 @@ int plk_srs_load_bytes(plk_ctx* ctx, const uint8_t* in, size_t n_points, int for
   const uint64_t n = n_points;
   const size_t bytes = n_points * (format == PLK_G1_COMPRESSED ? kG1Comp : kG1Raw);
   std::unique_ptr<plk_srs> srs;
-  Events ev;
+  TimingEvents<4> ev;
   BadWord bad;
   int st;
   if ((st = srs_new(ctx, n_points, srs))) return st;
@@ -443,16 +357,16 @@ int plk_srs_load_bytes(plk_ctx* ctx, const uint8_t* in, size_t n_points, int for
     uint8_t* inf = srs->inf.as<uint8_t>();
     PLK_HIP_TRY(hipEventRecord(ev.e[0], s));
     if (format == PLK_G1_COMPRESSED) {
-      hipLaunchKernelGGL(k_srs_decompress, dim3(blocks_for(n)), dim3(kBlock), 0, s,
+      hipLaunchKernelGGL(k_srs_decompress, dim3(cdiv(n, kBlock)), dim3(kBlock), 0, s,
                          (const uint8_t*)d_in.as<uint8_t>(), n, pts, inf, bad.dev());
     } else {
-      hipLaunchKernelGGL(k_srs_decode_raw, dim3(blocks_for(n)), dim3(kBlock), 0, s,
+      hipLaunchKernelGGL(k_srs_decode_raw, dim3(cdiv(n, kBlock)), dim3(kBlock), 0, s,
                          (const uint8_t*)d_in.as<uint8_t>(), n, pts, inf, bad.dev());
     }
     PLK_HIP_TRY(hipEventRecord(ev.e[1], s));
     if (check_subgroup) {
       PLK_HIP_TRY(hipEventRecord(ev.e[2], s));
-      hipLaunchKernelGGL(k_srs_subgroup, dim3(blocks_for(n)), dim3(kBlock), 0, s, (const G1Affine*)pts,
+      hipLaunchKernelGGL(k_srs_subgroup, dim3(cdiv(n, kBlock)), dim3(kBlock), 0, s, (const G1Affine*)pts,
                          (const uint8_t*)inf, n, bad.dev());
       PLK_HIP_TRY(hipEventRecord(ev.e[3], s));
     }
@@ -475,7 +389,7 @@ int plk_srs_load_bytes(plk_ctx* ctx, const uint8_t* in, size_t n_points, int for
   if ((st = srs_complete(srs.get()))) return st;
   *out = srs.release();
   return PLK_OK;
-  PLK_S_END
+  PLK_API_END
 }
 
 int plk_srs_last_load_ms(plk_ctx* ctx, float* decode_ms, float* subgroup_ms) {
@@ -486,7 +400,7 @@ int plk_srs_last_load_ms(plk_ctx* ctx, float* decode_ms, float* subgroup_ms) {
 }
 
 int plk_srs_export_bytes(const plk_srs* srs, size_t start, size_t count, int format, uint8_t* out) {
-  PLK_S_BEGIN
+  PLK_API_BEGIN
   if (!srs || (!out && count) || start > srs->n || count > srs->n - start) return PLK_E_ARG;
   if (format != PLK_G1_COMPRESSED && format != PLK_G1_UNCOMPRESSED) return PLK_E_ARG;
   if (!count) return PLK_OK;
@@ -496,7 +410,7 @@ int plk_srs_export_bytes(const plk_srs* srs, size_t start, size_t count, int for
   DevBuf d_out;
   int st;
   if ((st = d_out.alloc(bytes))) return st;
-  hipLaunchKernelGGL(k_srs_encode, dim3(blocks_for(count)), dim3(kBlock), 0, s,
+  hipLaunchKernelGGL(k_srs_encode, dim3(cdiv(count, kBlock)), dim3(kBlock), 0, s,
                      (const G1Affine*)srs->points.as<G1Affine>() + start,
                      (const uint8_t*)srs->inf.as<uint8_t>() + start, (uint64_t)count,
                      format == PLK_G1_COMPRESSED ? 1 : 0, d_out.as<uint8_t>());
@@ -504,20 +418,20 @@ int plk_srs_export_bytes(const plk_srs* srs, size_t start, size_t count, int for
   PLK_HIP_TRY(hipMemcpyAsync(out, d_out.ptr, bytes, hipMemcpyDeviceToHost, s));
   PLK_HIP_TRY(stream_wait(s));
   return PLK_OK;
-  PLK_S_END
+  PLK_API_END
 }
 
 int plk_srs_fold(plk_srs* srs, const uint8_t seed[32], plk_kzg_pair* out) {
-  PLK_S_BEGIN
+  PLK_API_BEGIN
   if (!srs || !out) return PLK_E_ARG;
   DeviceGuard g(srs->ctx->device);
   return fold_run(srs, seed, out);
-  PLK_S_END
+  PLK_API_END
 }
 
 int plk_srs_verify(plk_ctx* ctx, plk_srs* srs, const plk_opening_key* key, const uint8_t seed[32],
                    int* verdict, uint64_t* bad_index) {
-  PLK_S_BEGIN
+  PLK_API_BEGIN
   if (!ctx || !srs || !key || !verdict || srs->ctx != ctx) return PLK_E_ARG;
   DeviceGuard g(ctx->device);
   hipStream_t s = ctx->stream;
@@ -536,7 +450,7 @@ int plk_srs_verify(plk_ctx* ctx, plk_srs* srs, const plk_opening_key* key, const
   };
   if (!srs->points_checked) {
     if ((st = bad.reset(s))) return st;
-    hipLaunchKernelGGL(k_srs_validate, dim3(blocks_for(n)), dim3(kBlock), 0, s, pts, inf, n, bad.dev());
+    hipLaunchKernelGGL(k_srs_validate, dim3(cdiv(n, kBlock)), dim3(kBlock), 0, s, pts, inf, n, bad.dev());
     PLK_HIP_TRY(hipGetLastError());
     if ((st = bad.read(s, &any, &idx, &code))) return st;
     if (any) return fail(PLK_SRS_POINT);
@@ -544,7 +458,7 @@ int plk_srs_verify(plk_ctx* ctx, plk_srs* srs, const plk_opening_key* key, const
   }
   if (!srs->subgroup_checked) {
     if ((st = bad.reset(s))) return st;
-    hipLaunchKernelGGL(k_srs_subgroup, dim3(blocks_for(n)), dim3(kBlock), 0, s, pts, inf, n, bad.dev());
+    hipLaunchKernelGGL(k_srs_subgroup, dim3(cdiv(n, kBlock)), dim3(kBlock), 0, s, pts, inf, n, bad.dev());
     PLK_HIP_TRY(hipGetLastError());
     if ((st = bad.read(s, &any, &idx, &code))) return st;
     if (any) return fail(PLK_SRS_SUBGROUP);
@@ -560,7 +474,8 @@ int plk_srs_verify(plk_ctx* ctx, plk_srs* srs, const plk_opening_key* key, const
   G1Affine first;
   PLK_HIP_TRY(hipMemcpyAsync(&first, pts, sizeof first, hipMemcpyDeviceToHost, s));
   PLK_HIP_TRY(stream_wait(s));
-  const G1Affine gen = g1_generator_aff();
+  G1Affine gen;
+  g1_generator(gen.x, gen.y);
   if (!fe_eq(first.x, gen.x) || !fe_eq(first.y, gen.y)) {
     *verdict = PLK_SRS_GENERATOR;
     return PLK_OK;
@@ -575,7 +490,7 @@ int plk_srs_verify(plk_ctx* ctx, plk_srs* srs, const plk_opening_key* key, const
   srs->verify_pairing_ms = ms_since(t0);
   *verdict = ok ? PLK_SRS_OK : PLK_SRS_CHAIN;
   return PLK_OK;
-  PLK_S_END
+  PLK_API_END
 }
 
 int plk_srs_last_verify_ms(const plk_srs* srs, double* fold_ms, double* pairing_ms) {
@@ -586,7 +501,7 @@ int plk_srs_last_verify_ms(const plk_srs* srs, double* fold_ms, double* pairing_
 }
 
 int plk_debug_srs_weights(plk_ctx* ctx, const uint8_t seed[32], size_t n, plk_fr* out) {
-  PLK_S_BEGIN
+  PLK_API_BEGIN
   if (!seed || n == 0 || n > kMaxPoints || (!out && n > 1)) return PLK_E_ARG;
   if (n == 1) return PLK_OK;
   const size_t count = n - 1;
@@ -609,14 +524,14 @@ int plk_debug_srs_weights(plk_ctx* ctx, const uint8_t seed[32], size_t n, plk_fr
     PLK_HIP_TRY(hipMemcpyAsync(w.data(), d_out.ptr, count * sizeof(Fr), hipMemcpyDeviceToHost, s));
     PLK_HIP_TRY(stream_wait(s));
   }
-  for (size_t i = 0; i < count; ++i) fe_to_abi(w[i], out[i].l);
+  for (size_t i = 0; i < count; ++i) out[i] = fr_to_abi(w[i]);
   return PLK_OK;
-  PLK_S_END
+  PLK_API_END
 }
 
 // ---- the opening key from bytes (host only) ---------------------------------------------------
 int plk_opening_key_load_bytes(const uint8_t* h, const uint8_t* beta_h, int format, plk_opening_key** out) {
-  PLK_S_BEGIN
+  PLK_API_BEGIN
   if (!out) return PLK_E_ARG;
   *out = nullptr;
   if (!h || !beta_h || (format != PLK_G1_COMPRESSED && format != PLK_G1_UNCOMPRESSED)) return PLK_E_ARG;
@@ -628,11 +543,11 @@ int plk_opening_key_load_bytes(const uint8_t* h, const uint8_t* beta_h, int form
   g2_to_abi(a, &pa);
   g2_to_abi(b, &pb);
   return plk_opening_key_load(&pa, &pb, out);
-  PLK_S_END
+  PLK_API_END
 }
 
 int plk_opening_key_to_bytes(const plk_opening_key* key, int format, uint8_t* h, uint8_t* beta_h) {
-  PLK_S_BEGIN
+  PLK_API_BEGIN
   if (!key || (format != PLK_G1_COMPRESSED && format != PLK_G1_UNCOMPRESSED)) return PLK_E_ARG;
   const bool comp = format == PLK_G1_COMPRESSED;
   plk_g2 pa, pb;
@@ -643,29 +558,29 @@ int plk_opening_key_to_bytes(const plk_opening_key* key, int format, uint8_t* h,
   if (h) g2_to_bytes(a, comp, h);
   if (beta_h) g2_to_bytes(b, comp, beta_h);
   return PLK_OK;
-  PLK_S_END
+  PLK_API_END
 }
 
 int plk_debug_f2_sqrt(const uint64_t* a, uint64_t* out, int* is_square) {
-  PLK_S_BEGIN
+  PLK_API_BEGIN
   if (!a || !out || !is_square) return PLK_E_ARG;
-  const Fp2 v = {fp_from_abi(a), fp_from_abi(a + 6)};
-  if (!fp_canonical(v.c0) || !fp_canonical(v.c1)) return PLK_E_ARG;
+  const Fp2 v = {fe_of_abi<FpCfg>(a), fe_of_abi<FpCfg>(a + 6)};
+  if (!fe_canonical(v.c0) || !fe_canonical(v.c1)) return PLK_E_ARG;
   Fp2 r;
   *is_square = f2_sqrt(v, r) ? 1 : 0;
-  fp_to_abi(r.c0, out);
-  fp_to_abi(r.c1, out + 6);
+  fe_to_abi(r.c0, out);
+  fe_to_abi(r.c1, out + 6);
   return PLK_OK;
-  PLK_S_END
+  PLK_API_END
 }
 
 // ---- updating an SRS --------------------------------------------------------------------------
 int plk_opening_key_update(const plk_opening_key* key, const plk_fr* s, plk_opening_key** out, plk_g2* witness) {
-  PLK_S_BEGIN
+  PLK_API_BEGIN
   if (!out) return PLK_E_ARG;
   *out = nullptr;
   if (!key || !s || !witness) return PLK_E_ARG;
-  const Fr sm = fe_of_abi<FrCfg>(s->l);
+  const Fr sm = fr_from_abi(*s);
   if (!update_scalar_ok(sm)) return PLK_E_ARG;
   plk_g2 ph, pb;
   G2Aff h, bh;
@@ -680,19 +595,19 @@ int plk_opening_key_update(const plk_opening_key* key, const plk_fr* s, plk_open
   if ((st = plk_opening_key_load(&ph, &pnb, out))) return st;
   g2_to_abi(w, witness);
   return PLK_OK;
-  PLK_S_END
+  PLK_API_END
 }
 
 int plk_srs_update(plk_srs* srs, const plk_opening_key* key, const plk_fr* s, plk_srs** out_srs,
                    plk_opening_key** out_key, plk_g2* witness, uint64_t* bad_index) {
-  PLK_S_BEGIN
+  PLK_API_BEGIN
   if (!out_srs || !out_key) return PLK_E_ARG;
   *out_srs = nullptr;
   *out_key = nullptr;
   if (!srs || !key || !witness || srs->n < 2) return PLK_E_ARG;
   Fr sm;
   if (s) {
-    sm = fe_of_abi<FrCfg>(s->l);
+    sm = fr_from_abi(*s);
     if (!update_scalar_ok(sm)) return PLK_E_ARG;
   } else {
     fr_from_entropy(sm);
@@ -707,7 +622,7 @@ int plk_srs_update(plk_srs* srs, const plk_opening_key* key, const plk_fr* s, pl
   };
   plk_fr s_abi;
   Wipe wipe{sm, s_abi};
-  fe_to_abi(sm, s_abi.l);
+  s_abi = fr_to_abi(sm);
   plk_ctx* ctx = srs->ctx;
   DeviceGuard g(ctx->device);
   hipStream_t st = ctx->stream;
@@ -738,12 +653,12 @@ int plk_srs_update(plk_srs* srs, const plk_opening_key* key, const plk_fr* s, pl
   *out_srs = ns.release();
   *out_key = nk.release();
   return PLK_OK;
-  PLK_S_END
+  PLK_API_END
 }
 
 int plk_srs_verify_update(plk_ctx* ctx, const plk_g1* prev_tau_g1, plk_srs* new_srs, const plk_opening_key* new_key,
                           const plk_g2* witness, const uint8_t seed[32], int* verdict, uint64_t* bad_index) {
-  PLK_S_BEGIN
+  PLK_API_BEGIN
   if (!ctx || !prev_tau_g1 || !new_srs || !new_key || !witness || !verdict) return PLK_E_ARG;
   if (new_srs->ctx != ctx || new_srs->n < 2) return PLK_E_ARG;
   // the witness as the beta_h of a temporary key on the same H: plk_opening_key_load refuses what
@@ -775,29 +690,29 @@ int plk_srs_verify_update(plk_ctx* ctx, const plk_g1* prev_tau_g1, plk_srs* new_
   if ((st = plk_pairing_check(tk.k, &pair, &ok))) return st;
   if (ok) *verdict = PLK_SRS_OK;
   return PLK_OK;
-  PLK_S_END
+  PLK_API_END
 }
 
 int plk_g2_to_bytes(const plk_g2* q, int format, uint8_t* out) {
-  PLK_S_BEGIN
+  PLK_API_BEGIN
   if (!q || !out || (format != PLK_G1_COMPRESSED && format != PLK_G1_UNCOMPRESSED)) return PLK_E_ARG;
   G2Aff a = g2_infinity();
   int st;
   if (q->infinity != 1 && (st = g2_from_abi(*q, a))) return st;
   g2_to_bytes(a, format == PLK_G1_COMPRESSED, out);
   return PLK_OK;
-  PLK_S_END
+  PLK_API_END
 }
 
 int plk_g2_from_bytes(const uint8_t* in, int format, plk_g2* out) {
-  PLK_S_BEGIN
+  PLK_API_BEGIN
   if (!in || !out || (format != PLK_G1_COMPRESSED && format != PLK_G1_UNCOMPRESSED)) return PLK_E_ARG;
   G2Aff a;
   int st;
   if ((st = g2_from_bytes(in, format == PLK_G1_COMPRESSED, a))) return st;
   g2_to_abi(a, out);
   return PLK_OK;
-  PLK_S_END
+  PLK_API_END
 }
 
 }  // extern "C"

@@ -7,7 +7,7 @@
 #include <cstring>
 #include <string>
 
-#include "ff.hpp"
+#include "abi.hpp"
 #include "g1.hpp"
 
 namespace plk {
@@ -177,33 +177,10 @@ class Transcript {
     return fe_add(fe_mul(lo, r2), fe_mul(hi, r3));
   }
 
+  // zkcrypto's compressed G1 of a point taken as it is (no validation: the callers' business)
   static void g1_compress(const plk_g1& p, uint8_t* out) {
-    std::memset(out, 0, 48);
-    if (p.infinity) {
-      out[0] = 0xc0;
-      return;
-    }
-    Fp x, y;
-    for (int k = 0; k < 6; ++k) {
-      x.v[2 * k] = (uint32_t)p.x[k];
-      x.v[2 * k + 1] = (uint32_t)(p.x[k] >> 32);
-      y.v[2 * k] = (uint32_t)p.y[k];
-      y.v[2 * k + 1] = (uint32_t)(p.y[k] >> 32);
-    }
-    x = fe_from_mont(x);
-    y = fe_from_mont(y);
-    for (int i = 0; i < 12; ++i)
-      for (int k = 0; k < 4; ++k) out[47 - (4 * i + k)] = (uint8_t)(x.v[i] >> (8 * k));
-    // sort flag: y > (p-1)/2  <=>  2y > p - 1  <=>  y != 0 and y is the larger root
-    const Fp ny = fe_neg(y);
-    bool larger = false;
-    for (int i = 11; i >= 0; --i) {
-      if (y.v[i] != ny.v[i]) {
-        larger = y.v[i] > ny.v[i];
-        break;
-      }
-    }
-    out[0] |= 0x80 | (larger ? 0x20 : 0);
+    const G1Abi a = g1_load<false>(&p);
+    g1_compress_bytes(a.x, a.y, a.inf, out);
   }
 
   const Strobe128& strobe() const { return s_; }

@@ -24,7 +24,7 @@
 #include <string>
 #include <vector>
 
-#include "ff.hpp"
+#include "abi.hpp"
 
 namespace plk {
 
@@ -140,28 +140,6 @@ PLK_HD Fr sched_take_u128(uint64_t (&s)[25]) {
     s[i] = 0;
   }
   return fe_to_mont(r);
-}
-
-// zkcrypto's compressed G1 (transcript.hpp g1_compress) as the 12 words of its 48 bytes.
-// x, y: Montgomery form.
-PLK_HD void g1_compress_words(const Fp& x_mont, const Fp& y_mont, bool infinity, uint32_t out[12]) {
-  const Fp x = fe_from_mont(x_mont), y = fe_from_mont(y_mont), ny = fe_neg(y);
-  // sort flag: y is the larger of y, -y. Decided at the highest differing word.
-  bool larger = false, decided = false;
-#pragma unroll
-  for (int i = 11; i >= 0; --i) {
-    if (!decided && y.v[i] != ny.v[i]) {
-      larger = y.v[i] > ny.v[i];
-      decided = true;
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < 12; ++k) {
-    const uint32_t w = x.v[11 - k];  // big-endian bytes: the words reversed and byte-swapped
-    const uint32_t be = (w >> 24) | ((w >> 8) & 0xff00u) | ((w << 8) & 0xff0000u) | (w << 24);
-    out[k] = infinity ? 0u : be;
-  }
-  out[0] |= infinity ? 0xc0u : (0x80u | (larger ? 0x20u : 0u));
 }
 
 // The host's recording STROBE: Strobe128 / Transcript of transcript.hpp with positions only.

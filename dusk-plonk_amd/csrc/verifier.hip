@@ -26,13 +26,11 @@
 // (verifier_replay.hip). The host keeps the canonical-form checks, the uploads and, for random
 // weights, one sequential hash over the batch's u challenges (fold_device below).
 #include <hip/hip_runtime.h>
-#include <sys/random.h>
 
 #include <algorithm>
 #include <chrono>
 #include <cstring>
 #include <new>
-#include <random>
 #include <string>
 #include <thread>
 #include <vector>
@@ -230,16 +228,6 @@ __global__ void __launch_bounds__(256) k_fold_shared(const Fr* __restrict__ tmp,
 constexpr int kPairLanes = 32;  // half a wave per proof
 constexpr int kPairC = kShared + kPerProof;  // lanes [0, 27): the terms of C; 27, 28: of W
 
-__device__ __forceinline__ bool fp_is_canonical_dev(const Fp& a) {
-  uint32_t borrow = 0;
-#pragma unroll
-  for (int i = 0; i < 12; ++i) {
-    const uint64_t t = (uint64_t)a.v[i] - FpCfg::P[i] - borrow;
-    borrow = (uint32_t)(t >> 63);
-  }
-  return borrow != 0;
-}
-
 __device__ __forceinline__ G1xyzz xyzz_shfl_down(const G1xyzz& p, int off) {
   G1xyzz r;
 #pragma unroll
@@ -252,16 +240,6 @@ __device__ __forceinline__ G1xyzz xyzz_shfl_down(const G1xyzz& p, int off) {
   return r;
 }
 
-__device__ __forceinline__ void st_g1_abi(plk_g1* o, bool finite, const Fp& x, const Fp& y) {
-  uint64_t* q = reinterpret_cast<uint64_t*>(o);
-#pragma unroll
-  for (int k = 0; k < 6; ++k) {
-    q[k] = finite ? ((uint64_t)x.v[2 * k] | ((uint64_t)x.v[2 * k + 1] << 32)) : 0;
-    q[6 + k] = finite ? ((uint64_t)y.v[2 * k] | ((uint64_t)y.v[2 * k + 1] << 32)) : 0;
-  }
-  q[12] = finite ? 0 : 1;
-}
-
 // (C_j, W_j) of proof j = the fold of that proof alone at weight 1, as canonical affine points.
 // points / scalars: the fold's layout ([16 shared][11 per proof][2 per proof]); the proof's own
 // share of the 16 shared scalars is tmp[k * count + j] (k_fold_scalars at rho = 1). Lane l of the
@@ -272,8 +250,8 @@ __device__ __forceinline__ void st_g1_abi(plk_g1* o, bool finite, const Fp& x, c
 // lane 27, and lane 0 brings both to affine with one shared inversion. g1.hpp's packed XYZZ is
 // used, not g1r.hpp's redundant-limb form: the points stay in the ABI's Montgomery domain from
 // load to store and the operations are host-and-device code the host tail of the MSM already runs.
-// A finite point that is not canonical or not on the curve, or an infinity word other than
-// 0 / 1, sets *bad (the call fails with PLK_E_ARG) and counts as the identity.
+// A point g1_load<true> refuses sets *bad (the call fails with PLK_E_ARG) and counts as the
+// identity.
 __global__ void __launch_bounds__(128) k_proof_pairs(const plk_g1* __restrict__ points,
                                                      const Fr* __restrict__ scalars,
                                                      const Fr* __restrict__ tmp, uint32_t count,
@@ -296,32 +274,10 @@ __global__ void __launch_bounds__(128) k_proof_pairs(const plk_g1* __restrict__ 
     } else {
       pi = si = n_c + 2 * (size_t)j + (size_t)(l - kPairC);
     }
-    const uint64_t* q = reinterpret_cast<const uint64_t*>(&points[pi]);
-    const uint64_t flag = q[12];
-    Fp x, y;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-      const uint64_t a = q[k], b = q[6 + k];
-      x.v[2 * k] = (uint32_t)a;
-      x.v[2 * k + 1] = (uint32_t)(a >> 32);
-      y.v[2 * k] = (uint32_t)b;
-      y.v[2 * k + 1] = (uint32_t)(b >> 32);
-    }
-    bool finite = flag == 0;
-    if (flag > 1) *bad = 1;
-    if (finite) {
-      bool ok = fp_is_canonical_dev(x) && fp_is_canonical_dev(y);
-      if (ok) {
-        const Fp four = fe_dbl(fe_dbl(fe_one<FpCfg>()));
-        ok = fe_eq(fe_sqr(y), fe_add(fe_mul(fe_sqr(x), x), four));
-      }
-      if (!ok) {
-        *bad = 1;
-        finite = false;
-      }
-    }
+    const G1Abi p = g1_load<true>(&points[pi]);
+    if (!p.ok) *bad = 1;
     Fr s = fe_from_mont(sp[si]);
-    if (finite) {
+    if (!p.inf && p.ok) {
 #pragma nounroll
       for (int i = 0; i < 256; ++i) {
         acc = xyzz_dbl(acc);
@@ -329,7 +285,7 @@ __global__ void __launch_bounds__(128) k_proof_pairs(const plk_g1* __restrict__ 
 #pragma unroll
         for (int k = 7; k > 0; --k) s.v[k] = (s.v[k] << 1) | (s.v[k - 1] >> 31);
         s.v[0] <<= 1;
-        if (top) acc = xyzz_add_affine(acc, x, y);
+        if (top) acc = xyzz_add_affine(acc, p.x, p.y);
       }
     }
   }
@@ -347,31 +303,8 @@ __global__ void __launch_bounds__(128) k_proof_pairs(const plk_g1* __restrict__ 
   const Fp zc = fc ? acc.ZZZ : fe_one<FpCfg>(), zw = fw ? w.ZZZ : fe_one<FpCfg>();
   const Fp inv = fe_inv(fe_mul(zc, zw));
   const Fp ic = fe_mul(inv, zw), iw = fe_mul(inv, zc);  // 1 / ZZZ; 1 / ZZ = (ZZ / ZZZ)^2
-  st_g1_abi(&out[j].c, fc, fe_mul(acc.X, fe_sqr(fe_mul(acc.ZZ, ic))), fe_mul(acc.Y, ic));
-  st_g1_abi(&out[j].w, fw, fe_mul(w.X, fe_sqr(fe_mul(w.ZZ, iw))), fe_mul(w.Y, iw));
-}
-
-bool fr_abi_canonical(const plk_fr& a) {
-  uint64_t borrow = 0;
-  for (int i = 0; i < 4; ++i) {
-    const uint64_t p = (uint64_t)FrCfg::P[2 * i] | ((uint64_t)FrCfg::P[2 * i + 1] << 32);
-    const unsigned __int128 t = (unsigned __int128)a.l[i] - p - borrow;
-    borrow = (uint64_t)(t >> 64) & 1u;
-  }
-  return borrow != 0;  // a < r
-}
-
-Fr fr_from_abi(const plk_fr& a) {
-  Fr r;
-  for (int i = 0; i < 4; ++i) {
-    r.v[2 * i] = (uint32_t)a.l[i];
-    r.v[2 * i + 1] = (uint32_t)(a.l[i] >> 32);
-  }
-  return r;
-}
-
-void fr_to_abi(const Fr& a, plk_fr* out) {
-  for (int i = 0; i < 4; ++i) out->l[i] = (uint64_t)a.v[2 * i] | ((uint64_t)a.v[2 * i + 1] << 32);
+  g1_store(fe_mul(acc.X, fe_sqr(fe_mul(acc.ZZ, ic))), fe_mul(acc.Y, ic), fc, &out[j].c);
+  g1_store(fe_mul(w.X, fe_sqr(fe_mul(w.ZZ, iw))), fe_mul(w.Y, iw), fw, &out[j].w);
 }
 
 }  // namespace
@@ -417,13 +350,13 @@ namespace {
 int replay(const plk_verifier* v, const plk_proof& p, const plk_fr* pis, FoldIn& o) {
   const plk_fr* evals = &p.a_eval;
   for (int i = 0; i < 16; ++i) {
-    if (!fr_abi_canonical(evals[i])) return PLK_E_ARG;
+    if (!abi_canonical<FrCfg>(evals[i].l)) return PLK_E_ARG;
     o.ev[i] = fr_from_abi(evals[i]);
   }
   const size_t npi = v->pi_idx.size();
   std::vector<Fr> pi(npi);
   for (size_t i = 0; i < npi; ++i) {
-    if (!fr_abi_canonical(pis[i])) return PLK_E_ARG;
+    if (!abi_canonical<FrCfg>(pis[i].l)) return PLK_E_ARG;
     pi[i] = fr_from_abi(pis[i]);
   }
   Transcript t = v->base;
@@ -522,47 +455,17 @@ int replay(const plk_verifier* v, const plk_proof& p, const plk_fr* pis, FoldIn&
   return PLK_OK;
 }
 
-// The G1 generator (Montgomery form, ABI layout)
-plk_g1 g1_generator() {
-  static const uint32_t gx[12] = {0xdb22c6bbu, 0xfb3af00au, 0xf97a1aefu, 0x6c55e83fu,
-                                  0x171bac58u, 0xa14e3a3fu, 0x9774b905u, 0xc3688c4fu,
-                                  0x4fa9ac0fu, 0x2695638cu, 0x3197d794u, 0x17f1d3a7u};
-  static const uint32_t gy[12] = {0x46c5e7e1u, 0x0caa2329u, 0xa2888ae4u, 0xd03cc744u,
-                                  0x2c04b3edu, 0x00db18cbu, 0xd5d00af6u, 0xfcf5e095u,
-                                  0x741d8ae4u, 0xa09e30edu, 0xe3aaa0f1u, 0x08b3f481u};
+// The G1 generator in the ABI layout
+plk_g1 g1_generator_abi() {
   Fp x, y;
-  for (int i = 0; i < 12; ++i) {
-    x.v[i] = gx[i];
-    y.v[i] = gy[i];
-  }
-  x = fe_to_mont(x);
-  y = fe_to_mont(y);
-  plk_g1 g{};
-  for (int i = 0; i < 6; ++i) {
-    g.x[i] = (uint64_t)x.v[2 * i] | ((uint64_t)x.v[2 * i + 1] << 32);
-    g.y[i] = (uint64_t)y.v[2 * i] | ((uint64_t)y.v[2 * i + 1] << 32);
-  }
+  g1_generator(x, y);
+  plk_g1 g;
+  g1_store(x, y, true, &g);
   return g;
 }
 
 // rho_0 = 1, rho_j = 128 bits of a merlin transcript over every proof's u challenge and 32 bytes
 // of OS entropy: nobody who fixed the proofs beforehand knows the weights
-void os_entropy(uint8_t seed[32]) {
-  size_t got = 0;
-  while (got < 32) {
-    const ssize_t r = getrandom(seed + got, 32 - got, 0);
-    if (r <= 0) break;
-    got += (size_t)r;
-  }
-  if (got < 32) {
-    std::random_device rd;
-    for (size_t i = 0; i < 32; i += 4) {
-      const uint32_t x = rd();
-      std::memcpy(seed + i, &x, 4);
-    }
-  }
-}
-
 int random_weights(std::vector<FoldIn>& in) {
   uint8_t seed[32];
   os_entropy(seed);
@@ -624,7 +527,7 @@ std::vector<plk_g1> batch_points(const plk_verifier* v, const plk_proof* proofs,
   const size_t n_c = kShared + (size_t)kPerProof * count;
   std::vector<plk_g1> pts(n_c + 2 * count);
   std::memcpy(pts.data(), v->comms, sizeof v->comms);
-  pts[15] = g1_generator();
+  pts[15] = g1_generator_abi();
   for (size_t j = 0; j < count; ++j) {
     std::memcpy(&pts[kShared + kPerProof * j], &proofs[j].a_comm, kPerProof * sizeof(plk_g1));
     pts[n_c + 2 * j] = proofs[j].w_z_chall_comm;
@@ -661,10 +564,10 @@ int check_canonical(const plk_verifier* v, const plk_proof* proofs, const plk_fr
   for (size_t j = 0; j < count; ++j) {
     const plk_fr* evals = &proofs[j].a_eval;
     for (int i = 0; i < 16; ++i)
-      if (!fr_abi_canonical(evals[i])) return PLK_E_ARG;
+      if (!abi_canonical<FrCfg>(evals[i].l)) return PLK_E_ARG;
   }
   for (size_t i = 0; i < npi * count; ++i)
-    if (!fr_abi_canonical(pis[i])) return PLK_E_ARG;
+    if (!abi_canonical<FrCfg>(pis[i].l)) return PLK_E_ARG;
   return PLK_OK;
 }
 
@@ -702,7 +605,7 @@ int replay_on_device(plk_ctx* ctx, plk_verifier* v, const plk_proof* proofs, con
   const size_t n_c = kShared + (size_t)kPerProof * count, n_pts = n_c + 2 * count;
   std::vector<plk_g1> pts(n_pts);
   std::memcpy(pts.data(), v->comms, sizeof v->comms);
-  pts[15] = g1_generator();
+  pts[15] = g1_generator_abi();
   std::vector<plk_fr> evals(16 * count);
   for (size_t j = 0; j < count; ++j) {
     std::memcpy(&pts[kShared + kPerProof * j], &proofs[j].a_comm, kPerProof * sizeof(plk_g1));
@@ -866,21 +769,11 @@ int pairs_status(plk_ctx* ctx, plk_verifier* v) {
 }  // namespace
 }  // namespace plk
 
-#define PLK_V_BEGIN try {
-#define PLK_V_END                   \
-  }                                 \
-  catch (const std::bad_alloc&) {   \
-    return PLK_E_OOM;               \
-  }                                 \
-  catch (...) {                     \
-    return PLK_E_DEVICE;            \
-  }
-
 extern "C" {
 
 int plk_verifier_create(const char* label, uint64_t n, uint64_t m, const plk_g1 commitments[15],
                         const uint64_t* pi_indexes, size_t pi_count, plk_verifier** out) {
-  PLK_V_BEGIN
+  PLK_API_BEGIN
   if (!out) return PLK_E_ARG;
   *out = nullptr;
   if (!label || !commitments || (pi_count && !pi_indexes)) return PLK_E_ARG;
@@ -913,11 +806,11 @@ int plk_verifier_create(const char* label, uint64_t n, uint64_t m, const plk_g1 
   v->base = t;
   *out = v.release();
   return PLK_OK;
-  PLK_V_END
+  PLK_API_END
 }
 
 int plk_verifier_destroy(plk_verifier* v) {
-  PLK_V_BEGIN
+  PLK_API_BEGIN
   if (!v) return PLK_E_ARG;
   if (v->device >= 0) {
     DeviceGuard g(v->device);
@@ -932,31 +825,31 @@ int plk_verifier_destroy(plk_verifier* v) {
   }
   delete v;
   return PLK_OK;
-  PLK_V_END
+  PLK_API_END
 }
 
 int plk_verifier_challenges(const plk_verifier* v, const plk_proof* proof, const plk_fr* public_inputs,
                             plk_fr out[11]) {
-  PLK_V_BEGIN
+  PLK_API_BEGIN
   if (!v || !proof || !out || (!public_inputs && !v->pi_idx.empty())) return PLK_E_ARG;
   FoldIn in;
   const int st = replay(v, *proof, public_inputs, in);
   if (st != PLK_OK) return st;
-  for (int i = 0; i < 11; ++i) fr_to_abi(in.ch[i], &out[i]);
+  for (int i = 0; i < 11; ++i) out[i] = fr_to_abi(in.ch[i]);
   return PLK_OK;
-  PLK_V_END
+  PLK_API_END
 }
 
 int plk_verifier_fold(plk_ctx* ctx, plk_verifier* v, const plk_proof* proofs,
                       const plk_fr* public_inputs, size_t count, const plk_fr* weights,
                       plk_kzg_pair* out) {
-  PLK_V_BEGIN
+  PLK_API_BEGIN
   if (!ctx || !v || !proofs || !out || count == 0 || count > (1u << 24)) return PLK_E_ARG;
   const size_t npi = v->pi_idx.size();
   if (npi && !public_inputs) return PLK_E_ARG;
   if (weights)
     for (size_t j = 0; j < count; ++j)
-      if (!fr_abi_canonical(weights[j])) return PLK_E_ARG;
+      if (!abi_canonical<FrCfg>(weights[j].l)) return PLK_E_ARG;
   if (v->replay_mode == PLK_REPLAY_DEVICE)
     return fold_device(ctx, v, proofs, public_inputs, count, weights, out);
   v->replay_kernel_ms = 0.f;
@@ -1008,12 +901,12 @@ int plk_verifier_fold(plk_ctx* ctx, plk_verifier* v, const plk_proof* proofs,
   out->c = res[0];
   out->w = res[1];
   return PLK_OK;
-  PLK_V_END
+  PLK_API_END
 }
 
 int plk_verifier_pairs(plk_ctx* ctx, plk_verifier* v, const plk_proof* proofs,
                        const plk_fr* public_inputs, size_t count, plk_kzg_pair* out) {
-  PLK_V_BEGIN
+  PLK_API_BEGIN
   if (!ctx || !v || !proofs || !out || count == 0 || count > (1u << 24)) return PLK_E_ARG;
   if (!public_inputs && !v->pi_idx.empty()) return PLK_E_ARG;
   DeviceGuard g(ctx->device);
@@ -1026,7 +919,7 @@ int plk_verifier_pairs(plk_ctx* ctx, plk_verifier* v, const plk_proof* proofs,
   v->pairing_ms = 0.f;
   std::memcpy(out, res.data(), count * sizeof(plk_kzg_pair));
   return PLK_OK;
-  PLK_V_END
+  PLK_API_END
 }
 
 int plk_verifier_verify(plk_ctx* ctx, plk_verifier* v, const plk_opening_key* key,
@@ -1042,7 +935,7 @@ int plk_verifier_verify(plk_ctx* ctx, plk_verifier* v, const plk_opening_key* ke
 int plk_verifier_verify_each(plk_ctx* ctx, plk_verifier* v, plk_opening_key* key,
                              const plk_proof* proofs, const plk_fr* public_inputs, size_t count,
                              uint8_t* ok) {
-  PLK_V_BEGIN
+  PLK_API_BEGIN
   if (!ctx || !v || !key || !proofs || !ok || count == 0 || count > (1u << 24)) return PLK_E_ARG;
   if (!public_inputs && !v->pi_idx.empty()) return PLK_E_ARG;
   DeviceGuard g(ctx->device);
@@ -1059,7 +952,7 @@ int plk_verifier_verify_each(plk_ctx* ctx, plk_verifier* v, plk_opening_key* key
   pairing_last_ms(key, &v->pairing_ms);
   std::memcpy(ok, res.data(), count);
   return PLK_OK;
-  PLK_V_END
+  PLK_API_END
 }
 
 int plk_verifier_last_each_stats(const plk_verifier* v, float* pairs_ms, float* pairing_ms) {
@@ -1077,7 +970,7 @@ int plk_verifier_set_replay(plk_verifier* v, int mode) {
 
 int plk_verifier_challenges_batch(plk_ctx* ctx, plk_verifier* v, const plk_proof* proofs,
                                   const plk_fr* public_inputs, size_t count, plk_fr* out) {
-  PLK_V_BEGIN
+  PLK_API_BEGIN
   if (!ctx || !v || !proofs || !out || count == 0 || count > (1u << 24)) return PLK_E_ARG;
   if (!public_inputs && !v->pi_idx.empty()) return PLK_E_ARG;
   int st;
@@ -1093,9 +986,9 @@ int plk_verifier_challenges_batch(plk_ctx* ctx, plk_verifier* v, const plk_proof
   (void)hipEventElapsedTime(&v->replay_kernel_ms, v->e2, v->e3);
   if (status) return PLK_E_ARG;  // z_h(z) = 0 or z = 1 in some proof
   for (size_t j = 0; j < count; ++j)
-    for (int i = 0; i < 11; ++i) fr_to_abi(in[j].ch[i], &out[11 * j + i]);
+    for (int i = 0; i < 11; ++i) out[11 * j + i] = fr_to_abi(in[j].ch[i]);
   return PLK_OK;
-  PLK_V_END
+  PLK_API_END
 }
 
 int plk_verifier_last_replay_ms(const plk_verifier* v, float* kernel_ms) {
@@ -1106,17 +999,17 @@ int plk_verifier_last_replay_ms(const plk_verifier* v, float* kernel_ms) {
 
 int plk_debug_fold_weights(plk_ctx* ctx, const uint8_t entropy[32], const plk_fr* u, size_t count,
                            plk_fr* out) {
-  PLK_V_BEGIN
+  PLK_API_BEGIN
   if (!entropy || !u || !out || count == 0 || count > (1u << 24)) return PLK_E_ARG;
   std::vector<Fr> um(count);
   for (size_t j = 0; j < count; ++j) {
-    if (!fr_abi_canonical(u[j])) return PLK_E_ARG;
+    if (!abi_canonical<FrCfg>(u[j].l)) return PLK_E_ARG;
     um[j] = fr_from_abi(u[j]);
   }
   RhoPlan rho;
   fold_weights_root(entropy, um.data(), count, rho);
   if (!ctx) {
-    for (size_t j = 0; j < count; ++j) fr_to_abi(rho_host(rho, (uint32_t)j), &out[j]);
+    for (size_t j = 0; j < count; ++j) out[j] = fr_to_abi(rho_host(rho, (uint32_t)j));
     return PLK_OK;
   }
   DeviceGuard g(ctx->device);
@@ -1131,9 +1024,9 @@ int plk_debug_fold_weights(plk_ctx* ctx, const uint8_t entropy[32], const plk_fr
     return st;
   PLK_HIP_TRY(hipMemcpyAsync(um.data(), d_out.ptr, count * sizeof(Fr), hipMemcpyDeviceToHost, s));
   PLK_HIP_TRY(stream_wait(s));
-  for (size_t j = 0; j < count; ++j) fr_to_abi(um[j], &out[j]);
+  for (size_t j = 0; j < count; ++j) out[j] = fr_to_abi(um[j]);
   return PLK_OK;
-  PLK_V_END
+  PLK_API_END
 }
 
 int plk_verifier_last_fold_stats(const plk_verifier* v, double* replay_ms, float* gpu_ms) {

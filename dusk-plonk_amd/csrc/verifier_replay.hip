@@ -45,16 +45,9 @@ __global__ void __launch_bounds__(256) k_replay_prep(PrepArgs a) {
   if (item >= kItems + a.lay.npi) return;
   if (item < 11) {
     const plk_g1* p = a.comms + (size_t)11 * j + item;
-    Fp x, y;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-      x.v[2 * k] = (uint32_t)p->x[k];
-      x.v[2 * k + 1] = (uint32_t)(p->x[k] >> 32);
-      y.v[2 * k] = (uint32_t)p->y[k];
-      y.v[2 * k + 1] = (uint32_t)(p->y[k] >> 32);
-    }
+    const G1Abi c = g1_load<false>(p);
     uint32_t w[12];
-    g1_compress_words(x, y, p->infinity != 0, w);
+    g1_compress_words(c.x, c.y, c.inf, w);
 #pragma unroll
     for (int i = 0; i < 12; ++i)
       a.vals[((size_t)a.lay.comm((uint32_t)item) / 4u + 1u + i) * a.count + j] = w[i];

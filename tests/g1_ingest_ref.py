@@ -156,3 +156,34 @@ def proof_status(data: bytes, subgroup: bool = True) -> int:
         if st != OK:
             return st
     return OK
+
+
+# ---- the rules every entry point that validates plk_g1 input shares (plk_msm_points' contract) ---
+ABI_REFUSED = ("infinity word 2", "x = p", "y = 2p - y0", "off the curve")
+ABI_IDENTITY = "identity with garbage"
+ABI_LANES = (0, 63, 64)  # first lane, last lane of a wave, first lane of the second wave
+
+
+def abi_spoil(row, what: str) -> np.ndarray:
+    """A copy of the finite ABI row uint64[13] (Montgomery limbs) turned into one of the malformed
+    points of ABI_REFUSED (every one refused with PLK_E_ARG) or into ABI_IDENTITY (infinity word 1
+    over arbitrary coordinate words: accepted as the identity)."""
+    row = np.array(row, dtype=np.uint64)
+    assert row.shape == (13,) and row[12] == 0
+    y0 = P.limbs_to_int(row[6:12])
+    if what == "infinity word 2":
+        row[12] = 2
+    elif what == "x = p":  # the limbs of p itself: the smallest value that is not canonical
+        row[:6] = np.array(P.int_to_limbs(p, 6), dtype=np.uint64)
+    elif what == "y = 2p - y0":  # -y0 mod p, so on the curve as a residue, but >= p as limbs
+        assert p <= 2 * p - y0 < 1 << 384
+        row[6:12] = np.array(P.int_to_limbs(2 * p - y0, 6), dtype=np.uint64)
+    elif what == "off the curve":  # canonical; y0 + 1 = -y0 has no solution beside y0 = (p - 1) / 2
+        assert 2 * y0 + 1 != p
+        row[6:12] = np.array(P.int_to_limbs((y0 + 1) % p, 6), dtype=np.uint64)
+    elif what == ABI_IDENTITY:  # words >= p, a canonical residue, zero: none of them is looked at
+        row[:12] = np.array([0xFFFFFFFFFFFFFFFF] * 6 + [0xDEADBEEF, 1, 2, 3, 0, 5], dtype=np.uint64)
+        row[12] = 1
+    else:
+        raise ValueError(what)
+    return row

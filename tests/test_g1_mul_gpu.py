@@ -113,3 +113,32 @@ def test_device_split_equals_the_host_mirror(plk, gpu_ctx):
     dev = plk.plonk.debug_glv_split(vals, gpu_ctx)
     assert np.array_equal(dev, plk.plonk.debug_glv_split(vals))
     assert np.array_equal(dev, U.split_rows(scalars))
+
+
+# ---- the plk_g1 input rules, at the first lane, a wave's last lane and the next wave's first ----
+@pytest.fixture(scope="module")
+def abi_batch(cases):
+    """65 of the random (finite point, scalar, product) cases."""
+    sel = cases[5 * len(U.edge_scalars()):][:65]
+    assert len(sel) == 65 and all(c[0] is not None for c in sel)
+    return sel
+
+
+@pytest.mark.parametrize("assume", [False, True])
+@pytest.mark.parametrize("lane", ref.ABI_LANES)
+@pytest.mark.parametrize("what", ref.ABI_REFUSED)
+def test_malformed_point_is_refused(plk, gpu_ctx, abi_batch, what, lane, assume):
+    pts = P.g1_vec_to_np([c[0] for c in abi_batch])
+    pts[lane] = ref.abi_spoil(pts[lane], what)
+    assert refused(plk, gpu_ctx, pts, P.fr_vec_to_np([c[1] for c in abi_batch]), assume)
+
+
+@pytest.mark.parametrize("assume", [False, True])
+@pytest.mark.parametrize("lane", ref.ABI_LANES)
+def test_identity_word_hides_the_coordinates(plk, gpu_ctx, abi_batch, lane, assume):
+    pts = P.g1_vec_to_np([c[0] for c in abi_batch])
+    pts[lane] = ref.abi_spoil(pts[lane], ref.ABI_IDENTITY)
+    want = P.g1_vec_to_np([c[2] for c in abi_batch])
+    want[lane] = IDENTITY_ROW
+    got = plk.plonk.g1_mul(pts, P.fr_vec_to_np([c[1] for c in abi_batch]), assume, gpu_ctx)
+    assert np.array_equal(got, want)

@@ -198,3 +198,33 @@ def test_proofs_ingest(plk, gpu_ctx, S, pts):
     assert list(st1) == [0] and one[0] == S.proofs[1]
     one, st1 = ingest_proofs(blobs[33], ctx=gpu_ctx)
     assert list(st1) == [ref.OFF_CURVE] and one[0] is None
+
+
+# ---- the plk_g1 input rules of plk_g1_subgroup_check_batch ------------------------------------
+@pytest.fixture(scope="module")
+def abi_batch(pts):
+    """65 finite curve points, members and non-members, and [r]P == O of each in Python."""
+    points = (pts.members + pts.non_members + pts.low)
+    points = (points * (65 // len(points) + 1))[:65]
+    member = {pt: ref.in_subgroup(pt) for pt in set(points)}
+    return points, np.array([member[pt] for pt in points])
+
+
+@pytest.mark.parametrize("lane", ref.ABI_LANES)
+@pytest.mark.parametrize("what", ref.ABI_REFUSED)
+def test_subgroup_check_refuses_a_malformed_point(plk, gpu_ctx, abi_batch, what, lane):
+    arr = P.g1_vec_to_np(abi_batch[0])
+    arr[lane] = ref.abi_spoil(arr[lane], what)
+    with pytest.raises(plk.PlonkError) as err:
+        plk.g1_subgroup_check(arr, ctx=gpu_ctx)
+    assert err.value.status == plk.PLK_E_ARG
+
+
+@pytest.mark.parametrize("lane", ref.ABI_LANES)
+def test_subgroup_check_identity_word_hides_the_coordinates(plk, gpu_ctx, abi_batch, lane):
+    arr = P.g1_vec_to_np(abi_batch[0])
+    arr[lane] = ref.abi_spoil(arr[lane], ref.ABI_IDENTITY)
+    want = abi_batch[1].copy()
+    want[lane] = True  # the identity has order r
+    assert want.any() and not want.all()
+    assert np.array_equal(plk.g1_subgroup_check(arr, ctx=gpu_ctx), want)

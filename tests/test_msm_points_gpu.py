@@ -9,6 +9,7 @@ batched form over disjoint ranges of one point array.
 import numpy as np
 import pytest
 
+import g1_ingest_ref as ref
 import pyref as P
 from oracle_lib import random_fr
 
@@ -139,3 +140,39 @@ def test_two_ranges_in_one_batch_equal_two_calls(plk, gpu_ctx, oracle, points):
     one = plk.msm_points_ranges(points[:n], sc, [(0, 0), (5, 60)], gpu_ctx)
     assert one[0].is_identity
     assert np.array_equal(one[1].words, oracle.msm(points[5:65], sc[5:65]))
+
+
+# ---- the plk_g1 input rules, at the first lane, a wave's last lane and the next wave's first ----
+@pytest.fixture(scope="module")
+def abi_batch():
+    """65 points of G1 and 65 scalars as Python integers, with each term's product."""
+    rng = P.SplitMix64(0xAB1)
+    step, acc, pts = ref.member(0x9E3779B97F4A7C15), ref.member(3), []
+    for _ in range(65):
+        pts.append(acc)
+        acc = P.g1_add(acc, step)
+    ks = [rng.fr() for _ in range(65)]
+    return pts, ks, [P.g1_mul(pt, k) for pt, k in zip(pts, ks)]
+
+
+@pytest.mark.parametrize("lane", ref.ABI_LANES)
+@pytest.mark.parametrize("what", ref.ABI_REFUSED)
+def test_malformed_point_is_refused(plk, gpu_ctx, abi_batch, what, lane):
+    pts = P.g1_vec_to_np(abi_batch[0])
+    pts[lane] = ref.abi_spoil(pts[lane], what)
+    with pytest.raises(plk.PlonkError) as e:
+        plk.msm_points(pts, P.fr_vec_to_np(abi_batch[1]), gpu_ctx)
+    assert e.value.status == plk.PLK_E_ARG
+
+
+@pytest.mark.parametrize("lane", ref.ABI_LANES)
+def test_identity_word_hides_the_coordinates(plk, gpu_ctx, abi_batch, lane):
+    points, ks, terms = abi_batch
+    pts = P.g1_vec_to_np(points)
+    pts[lane] = ref.abi_spoil(pts[lane], ref.ABI_IDENTITY)
+    want = None
+    for i, t in enumerate(terms):
+        if i != lane:
+            want = P.g1_add(want, t)
+    got = plk.msm_points(pts, P.fr_vec_to_np(ks), gpu_ctx).words
+    assert np.array_equal(got, P.g1_vec_to_np([want])[0])

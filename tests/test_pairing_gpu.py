@@ -6,6 +6,7 @@ at counts around the wave size with wrong pairs at the first, wave-boundary and 
 import numpy as np
 import pytest
 
+import g1_ingest_ref as ref
 import pyref as P
 from make_pairing_vectors import OUT
 
@@ -93,3 +94,26 @@ def test_check_batch_refuses_malformed_points(plk, gpu_ctx, honest):
     with pytest.raises(plk.PlonkError) as err:
         key.check_batch(words, gpu_ctx)
     assert err.value.status == plk.PLK_E_ARG
+
+
+# ---- the plk_g1 input rules of plk_pairing_check_batch, on C and on W --------------------------
+@pytest.mark.parametrize("lane", ref.ABI_LANES)
+@pytest.mark.parametrize("which", [0, 1])
+@pytest.mark.parametrize("what", ref.ABI_REFUSED)
+def test_check_batch_refuses_a_malformed_point(plk, gpu_ctx, honest, what, which, lane):
+    words = np.stack([P.g1_vec_to_np(list(pr)) for pr in honest])
+    words[lane, which] = ref.abi_spoil(words[lane, which], what)
+    with pytest.raises(plk.PlonkError) as err:
+        plk.OpeningKey.setup(TAU).check_batch(words, gpu_ctx)
+    assert err.value.status == plk.PLK_E_ARG
+
+
+@pytest.mark.parametrize("lane", ref.ABI_LANES)
+def test_check_batch_identity_word_hides_the_coordinates(plk, gpu_ctx, honest, lane):
+    """(O, O) holds and (O, W) does not, whatever the identity's coordinate words are."""
+    words = np.stack([P.g1_vec_to_np(list(pr)) for pr in honest])
+    key = plk.OpeningKey.setup(TAU)
+    words[lane, 0] = ref.abi_spoil(words[lane, 0], ref.ABI_IDENTITY)
+    assert list(key.check_batch(words, gpu_ctx)) == [j != lane for j in range(65)]
+    words[lane, 1] = ref.abi_spoil(words[lane, 1], ref.ABI_IDENTITY)
+    assert list(key.check_batch(words, gpu_ctx)) == [True] * 65

@@ -9,6 +9,7 @@ equation e(C, H) == e(W, [tau]H) as C == tau W in G1 (tests/verifier.py's device
 import numpy as np
 import pytest
 
+import g1_ingest_ref as ref
 import pyref as P
 import verifier_pair as VP
 from verifier_pair import copy_proof
@@ -218,3 +219,34 @@ def test_identity_commitments_are_legal(S):
     _, c, w = VP.pair(vd, p, pis)
     got_c, got_w = ver.fold([p], [pis], [1])
     assert np.array_equal(got_c, VP.to_words(c)) and np.array_equal(got_w, VP.to_words(w))
+
+
+# ---- the plk_g1 input rules of plk_verifier_pairs, through one tampered commitment -------------
+@pytest.mark.parametrize("lane", ref.ABI_LANES)
+@pytest.mark.parametrize("what", ref.ABI_REFUSED)
+def test_pairs_refuse_a_malformed_commitment(S, plk, what, lane):
+    proofs, pis, _, _ = S.batch()
+    proofs, pis = list(proofs[:65]), pis[:65]
+    proofs[lane] = copy_proof(proofs[lane], z_comm=ref.abi_spoil(proofs[lane].z_comm, what))
+    with pytest.raises(plk.PlonkError) as err:
+        S.key["public_sum"][2].pairs(proofs, pis)
+    assert err.value.status == plk.PLK_E_ARG
+
+
+@pytest.mark.parametrize("replay", ["host", "device"])
+@pytest.mark.parametrize("lane", ref.ABI_LANES)
+def test_pairs_identity_word_hides_the_coordinates(S, lane, replay):
+    """An identity commitment over arbitrary coordinate words gives the pair of the identity."""
+    proofs, pis, _, _ = S.batch()
+    proofs, pis = list(proofs[:65]), pis[:65]
+    _, vd, ver, _, _ = S.key["public_sum"]
+    garbage = ref.abi_spoil(proofs[lane].w_z_chall_w_comm, ref.ABI_IDENTITY)
+    clean = copy_proof(proofs[lane], w_z_chall_w_comm=np.array([0] * 12 + [1], dtype=np.uint64))
+    proofs[lane] = copy_proof(proofs[lane], w_z_chall_w_comm=garbage)
+    _, c, w = VP.pair(vd, clean, pis[lane])
+    ver.set_replay(replay)
+    try:
+        got = ver.pairs(proofs, pis)
+    finally:
+        ver.set_replay("host")
+    assert np.array_equal(got[lane, 0], VP.to_words(c)) and np.array_equal(got[lane, 1], VP.to_words(w))
