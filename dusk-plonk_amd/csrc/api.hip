@@ -90,6 +90,7 @@ int plk_ctx_destroy(plk_ctx* ctx) {
     ctx->domains.clear();
     msm_var_ws_delete(ctx->var_ws);
     ingest_ws_delete(ctx->ingest_ws);
+    check_ws_delete(ctx->check_ws);
     (void)hipStreamDestroy(ctx->stream);
   }
   delete ctx;

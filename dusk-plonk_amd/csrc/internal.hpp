@@ -182,6 +182,7 @@ struct plk_srs {
 namespace plk {
 struct VarMsmWs;
 struct IngestWs;
+struct CheckWs;
 }
 
 struct plk_ctx {
@@ -197,6 +198,10 @@ struct plk_ctx {
   float srs_decode_ms = 0.f, srs_subgroup_ms = 0.f;
   // kernel time of the most recent scalar multiplication batch (g1_mul.hip; measurement only)
   float g1_mul_ms = 0.f;
+  // buffers of plk_composer_check (circuit_check.hip), made on first use, and the kernel time of
+  // the most recent check or diagnosis on this context (measurement only)
+  plk::CheckWs* check_ws = nullptr;
+  float check_ms = 0.f;
 };
 
 namespace plk {
@@ -331,6 +336,7 @@ int msm_var_run(plk_ctx* ctx, const plk_g1* d_points, const Fr* d_scalars, size_
                 hipStream_t stream);
 void msm_var_ws_delete(VarMsmWs* w);
 void ingest_ws_delete(IngestWs* w);
+void check_ws_delete(CheckWs* w);  // circuit_check.hip
 // the number of public inputs a verifier was created with (verifier.hip)
 size_t verifier_pi_count(const plk_verifier* v);
 // The batched pairing check (pairing.hip) on device buffers, stream-ordered on the context's

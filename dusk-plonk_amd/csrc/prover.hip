@@ -939,6 +939,27 @@ int plk_key_compile(plk_srs* srs, const plk_composer* cs, const char* label, plk
     key->struct_hash = cs->struct_hash;
     TRY(key->wire_idx.alloc(4 * n * 4));
     PLK_HIP_TRY(hipMemcpyAsync(key->wire_idx.ptr, idx.data(), 4 * n * 4, hipMemcpyHostToDevice, s));
+    // 6. the gate table of plk_prover_diagnose: the compact records and pooled constants as the
+    // composer holds them, a public-input slot carrying the gate's ordinal (prover.hpp)
+    std::vector<Fr> consts(cs->consts);
+    {
+      uint32_t ordinal = 0;
+      for (uint64_t i = 0; i < m; ++i) {
+        const GateRec& g = cs->gates[i];
+        if (!(g.code & kPiBit)) continue;
+        uint32_t e = g.ext;
+        for (int q = 0; q < 11; ++q) e += sel_code(g.code, q) == kSelPooled;
+        consts[e] = fe_zero<FrCfg>();
+        consts[e].v[0] = ordinal++;
+      }
+    }
+    TRY(key->gate_recs.alloc(std::max<size_t>(m, 1) * sizeof(GateRec)));
+    TRY(key->gate_consts.alloc(std::max<size_t>(consts.size(), 1) * sizeof(Fr)));
+    PLK_HIP_TRY(hipMemcpyAsync(key->gate_recs.ptr, cs->gates.data(), m * sizeof(GateRec),
+                               hipMemcpyHostToDevice, s));
+    if (!consts.empty())
+      PLK_HIP_TRY(hipMemcpyAsync(key->gate_consts.ptr, consts.data(), consts.size() * sizeof(Fr),
+                                 hipMemcpyHostToDevice, s));
     PLK_HIP_TRY(stream_wait(s));
     *out = key.release();
     return PLK_OK;
@@ -1064,7 +1085,9 @@ int plk_prove(plk_key* key, const plk_composer* cs, uint64_t seed, plk_proof* pr
 int plk_prover_prove(plk_prover* P, const plk_composer* cs, uint64_t seed, plk_proof* proof,
                      plk_fr* public_inputs, size_t pi_cap, size_t* pi_count) {
   PLK_API_BEGIN
-    if (!P || !cs || !proof) return PLK_E_ARG;
+    if (!P) return PLK_E_ARG;
+    P->have_witness = false;  // plk_prover_diagnose: a refused call leaves no witness to check
+    if (!cs || !proof) return PLK_E_ARG;
     plk_key* key = P->key;
     // the proving circuit must have the key's structure (prover.rs:114-119 gathers the
     // wires of this circuit; the key's gather indices stand for them)
@@ -1142,6 +1165,10 @@ int plk_prover_prove(plk_prover* P, const plk_composer* cs, uint64_t seed, plk_p
         std::memcpy(pin + off, src + off, len);
         PLK_HIP_TRY(hipMemcpyAsync(dst + off, pin + off, len, hipMemcpyHostToDevice, s));
       }
+      // what plk_prover_diagnose checks: this witness with this proof's public inputs
+      P->last_pi.resize(pis.size());
+      for (size_t i = 0; i < pis.size(); ++i) P->last_pi[i] = pis[i].second;
+      P->have_witness = true;
     }
     Fr* wl = P->wires_lag.as<Fr>();
     Fr* wc = P->wires_coef.as<Fr>();
@@ -1581,6 +1608,7 @@ int plk_prover_prove(plk_prover* P, const plk_composer* cs, uint64_t seed, plk_p
 plk_prover::~plk_prover() {
   if (own_stream && stream) (void)hipStreamDestroy(stream);
   plk::msm_workspace_delete(ws);
+  plk::check_ws_delete(check_ws);
 }
 
 plk_key::~plk_key() { delete lag; }

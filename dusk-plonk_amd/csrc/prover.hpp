@@ -244,12 +244,13 @@ struct Gate {
 // dominated by 0/±1 selectors, so synthesis writes ~17x fewer bytes per gate.
 enum : uint32_t { kSelZero = 0, kSelOne = 1, kSelMinusOne = 2, kSelPooled = 3 };
 constexpr uint32_t kPiBit = 1u << 22;
+struct CheckWs;  // circuit_check.hpp
 struct GateRec {
   uint32_t w[4];
   uint32_t code;
   uint32_t ext;
 };
-inline uint32_t sel_code(uint32_t code, int q) { return (code >> (2 * q)) & 3u; }
+PLK_HD uint32_t sel_code(uint32_t code, int q) { return (code >> (2 * q)) & 3u; }
 
 }  // namespace plk
 
@@ -296,6 +297,10 @@ struct plk_key {
   plk::Fr s_m[plk::kQBlocksMax];  // g w_8n^m (R domain)
   plk::CombineMat comb;     // pk_coset_combine's matrix (R')
   plk::DevBuf wire_idx;     // 4 x n witness indices per gate (u32)
+  // the compact gate table of plk_prover_diagnose (circuit_check.hpp): the composer's m gate
+  // records and its pooled constants, a public-input slot holding the gate's ordinal among the
+  // public inputs in place of the compile-time value
+  plk::DevBuf gate_recs, gate_consts;
   plk::Fr vh_inv[plk::kQBlocksMax];
   plk_g1 comms[15];         // q_m q_l q_r q_o q_c q_4 q_arith q_range q_logic q_fixed q_var s1..s4
   // the circuit the key was compiled from: plk_prove refuses a circuit whose structure hash
@@ -335,6 +340,13 @@ struct plk_prover {
   // Lagrange values) and MSM entry count per wire
   int commit_basis[4] = {0, 0, 0, 0};
   uint64_t commit_entries[4] = {0, 0, 0, 0};
+  // plk_prover_diagnose: whether `witness` holds the most recent plk_prover_prove's upload, that
+  // proof's public-input values in gate order (host, and their device copy), and the check's own
+  // buffers, made on first use
+  bool have_witness = false;
+  std::vector<plk::Fr> last_pi;
+  plk::DevBuf pi_vals;
+  plk::CheckWs* check_ws = nullptr;
   plk::DevBuf witness, wires_lag, wires_coef, z_lag, z_coef, num, den, tmp_a, scan_tmp, pi_lag,
       pi_coef, evq, quotq, t_coef, agg, agg2, w_coef, eval_partial, ntt_scratch;
   ~plk_prover();

@@ -47,6 +47,9 @@ _SRS_UPDATE_SYMBOLS = (
     "plk_srs_verify_update", "plk_g2_to_bytes", "plk_g2_from_bytes", "plk_debug_glv_split",
 )
 
+# the entry points of csrc/circuit_check.hip (bound only when the loaded library has them, as above)
+_CHECK_SYMBOLS = ("plk_composer_check", "plk_prover_diagnose", "plk_key_diagnose", "plk_check_last_ms")
+
 # Symbols declared in include/plk.h (checked by tests/test_abi.py)
 ABI_SYMBOLS = (
     "plk_abi_version", "plk_status_str", "plk_build_info", "plk_device_count", "plk_ctx_create",
@@ -93,6 +96,8 @@ ABI_SYMBOLS = (
     "plk_verifier_verify_each_bytes",
     *_SRS_IO_SYMBOLS,
     *_SRS_UPDATE_SYMBOLS,
+    # the circuit check and the prover's diagnosis (Plonk.check / Prover.diagnose in prover.py)
+    *_CHECK_SYMBOLS,
 )
 
 # per-item status of the ingest calls (include/plk.h PLK_INGEST_*)
@@ -109,6 +114,8 @@ class PlonkError(RuntimeError):
     def __init__(self, status: int, what: str = "", bad_index: int | None = None,
                  bad_status: int | None = None):
         self.status = status
+        # create_proof(..., explain=True) on an unsatisfied circuit: the CircuitReport
+        self.report = None
         # PlonkParams.from_bytes: the smallest rejected index and its INGEST_* code
         self.bad_index, self.bad_status = bad_index, bad_status
         msg = _lib().plk_status_str(status).decode() if _LIB is not None else str(status)
@@ -208,9 +215,10 @@ def _lib():
             "plk_g2_to_bytes": (i32, [vp, i32, vp]),
             "plk_g2_from_bytes": (i32, [vp, i32, vp]),
             "plk_debug_glv_split": (i32, [vp, vp, sz, vp]),
+            "plk_check_last_ms": (i32, [vp, C.POINTER(C.c_float)]),
         }
         for name, (res, args) in sig.items():
-            if name in _SRS_IO_SYMBOLS + _SRS_UPDATE_SYMBOLS and not hasattr(lib, name):
+            if name in _SRS_IO_SYMBOLS + _SRS_UPDATE_SYMBOLS + _CHECK_SYMBOLS and not hasattr(lib, name):
                 continue  # a PLK_LIB build from before srs_io.hip still loads; a use fails loudly
             f = getattr(lib, name)
             f.restype, f.argtypes = res, args
@@ -702,6 +710,14 @@ def ingest_last_ms(ctx: "Context | None" = None):
     a, b = C.c_float(), C.c_float()
     _check(_lib().plk_ingest_last_ms(ctx.handle, C.byref(a), C.byref(b)), "plk_ingest_last_ms")
     return a.value, b.value
+
+
+def check_last_ms(ctx: "Context | None" = None) -> float:
+    """k_gate_check's kernel ms in the most recent Plonk.check / diagnose on the context."""
+    ctx = ctx or Context.default()
+    a = C.c_float()
+    _check(_lib().plk_check_last_ms(ctx.handle, C.byref(a)), "plk_check_last_ms")
+    return a.value
 
 
 def _seed32(seed) -> np.ndarray:

@@ -16,7 +16,7 @@ import ctypes as C
 
 import numpy as np
 
-from .plonk import (PLK_OK, PlonkError, PlonkParams, _check, _lib, _ptr)
+from .plonk import (_CHECK_SYMBOLS, PLK_OK, PlonkError, PlonkParams, _check, _lib, _ptr)
 
 R_MOD = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
 _R = 1 << 256
@@ -108,8 +108,13 @@ def _bind():
         "plk_proof_decode_compact": [vp, sz, vp, i32],
         "plk_proofs_ingest": [vp, vp, sz, i32, vp, vp],
         "plk_verifier_verify_each_bytes": [vp, vp, vp, vp, vp, sz, i32, vp],
+        "plk_composer_check": [vp, vp, vp, vp, sz, C.POINTER(sz)],
+        "plk_prover_diagnose": [vp, vp, vp, sz, C.POINTER(sz)],
+        "plk_key_diagnose": [vp, vp, vp, sz, C.POINTER(sz)],
     }
     for name, args in sig.items():
+        if name in _CHECK_SYMBOLS and not hasattr(lib, name):
+            continue  # a PLK_LIB build from before circuit_check.hip still loads
         f = getattr(lib, name)
         f.restype, f.argtypes = i32, args
     lib._prover_bound = True
@@ -195,6 +200,99 @@ class Constraint:
     def d(self, w):
         self.c.d = w
         return self
+
+
+# ---- circuit check (include/plk.h, "circuit check") ---------------------------------------
+class PlkGateFailure(C.Structure):
+    _fields_ = [("gate", C.c_uint64), ("mask", C.c_uint32), ("_pad", C.c_uint32),
+                ("residual", PlkFr)]
+
+
+class PlkCheckSummary(C.Structure):
+    _fields_ = [("gates", C.c_uint64), ("failing", C.c_uint64), ("by_class", C.c_uint64 * 5)]
+
+
+GATE_CLASSES = ("arithmetic", "range", "logic", "fixed_base", "variable_base")
+# class -> (first mask bit, number of terms): PLK_GATE_ARITH / _RANGE / _LOGIC / _FIXED / _VAR
+_GATE_BITS = {"arithmetic": (0, 1), "range": (4, 4), "logic": (8, 5), "fixed_base": (16, 4),
+              "variable_base": (20, 3)}
+
+
+class GateFailure:
+    """One failing gate: its index, the PLK_GATE_* mask of its non-zero terms, the classes and
+    terms the mask names ((class, term index) pairs) and the arithmetic term's value."""
+
+    def __init__(self, gate: int, mask: int, residual: int):
+        self.gate, self.mask, self.residual = gate, mask, residual
+        self.terms = [(c, j) for c, (lo, cnt) in _GATE_BITS.items() for j in range(cnt)
+                      if mask >> (lo + j) & 1]
+        self.classes = [c for c in GATE_CLASSES if any(t[0] == c for t in self.terms)]
+
+    def __eq__(self, other) -> bool:
+        return (isinstance(other, GateFailure)
+                and (self.gate, self.mask, self.residual) == (other.gate, other.mask, other.residual))
+
+    def __repr__(self) -> str:
+        return f"GateFailure(gate={self.gate}, mask={self.mask:#x}, residual={self.residual:#x})"
+
+    def __str__(self) -> str:
+        parts = []
+        for c in self.classes:
+            if c == "arithmetic":
+                parts.append(f"arithmetic, residual = {self.residual:#x}")
+            else:
+                js = " ".join(str(j) for cc, j in self.terms if cc == c)
+                parts.append(f"{c.replace('_', '-')} term {js}")
+        return f"gate {self.gate}: " + "; ".join(parts)
+
+
+class CircuitReport:
+    """The verdict of Plonk.check / diagnose: ok, gates, failing (the number of failing gates),
+    by_class (failing gates per class, a dict over GATE_CLASSES) and failures, the failing gates
+    with the smallest indices in ascending order (at most max_failures of them)."""
+
+    def __init__(self, summary: PlkCheckSummary, failures):
+        self.gates, self.failing = int(summary.gates), int(summary.failing)
+        self.by_class = {c: int(summary.by_class[i]) for i, c in enumerate(GATE_CLASSES)}
+        self.failures = list(failures)
+        self.ok = self.failing == 0
+
+    def __bool__(self) -> bool:
+        return self.ok
+
+    def __eq__(self, other) -> bool:
+        return (isinstance(other, CircuitReport) and self.gates == other.gates
+                and self.failing == other.failing and self.by_class == other.by_class
+                and self.failures == other.failures)
+
+    def __str__(self) -> str:
+        if self.ok:
+            return f"all {self.gates} gates hold"
+        lines = [f"{self.failing} of {self.gates} gates fail"]
+        lines += [str(f) for f in self.failures]
+        if self.failing > len(self.failures):
+            lines.append(f"... and {self.failing - len(self.failures)} more")
+        return "\n".join(lines)
+
+
+def _check_call(fn, what: str, max_failures: int) -> CircuitReport:
+    """fn(summary, failures, cap, count) -> status, one of the three check entry points."""
+    summary, cnt = PlkCheckSummary(), C.c_size_t()
+    cap = max(0, int(max_failures))
+    fails = (PlkGateFailure * cap)() if cap else None
+    _check(fn(C.byref(summary), fails, cap, C.byref(cnt)), what)
+    return CircuitReport(summary, [GateFailure(int(fails[i].gate), int(fails[i].mask),
+                                               fr_int(fails[i].residual))
+                                   for i in range(cnt.value)])
+
+
+def _explained(err: PlonkError, explain: bool, diagnose) -> PlonkError:
+    """create_proof's error, with the diagnosis attached when asked for and the status is the
+    unsatisfied circuit's."""
+    from .plonk import PLK_E_DEGREE
+    if explain and err.status == PLK_E_DEGREE:
+        err.report = diagnose()
+    return err
 
 
 # ---- JubJub (twisted Edwards -x^2 + y^2 = 1 + d x^2 y^2 over Fr), the composer's curve C ----
@@ -516,6 +614,19 @@ class Plonk:
                                        C.byref(m), C.byref(nw)), "export")
         return gates[: m.value], wit[: nw.value]
 
+    def check(self, ctx=None, host: bool = False, max_failures: int = 16) -> CircuitReport:
+        """Which gates this witness fails (plk_composer_check), without a key or a proof: every
+        gate identity evaluated on its own. On the GPU of `ctx` (default: the default context);
+        host=True runs the same per-gate function in a host loop, no GPU. The report lists the
+        max_failures failing gates with the smallest indices."""
+        h = None
+        if not host:
+            from .plonk import Context
+            h = (ctx or Context.default()).handle
+        lib = _bind()
+        return _check_call(lambda *a: lib.plk_composer_check(h, self._h, *a), "Plonk.check",
+                           max_failures)
+
     def public_inputs(self):
         cnt = C.c_size_t()
         lib = _bind()
@@ -822,19 +933,29 @@ class Prover:
     def __init__(self, key_handle, n, m, label, pp):
         self._key, self.n, self.m, self.label, self.pp = key_handle, n, m, label, pp
 
-    def create_proof(self, seed: int, circuit):
+    def create_proof(self, seed: int, circuit, explain: bool = False):
         cs = Plonk()
         circuit.synthesize(cs)
-        return self.prove_composer(cs, seed)
+        return self.prove_composer(cs, seed, explain)
 
-    def prove_composer(self, cs: Plonk, seed: int):
+    def prove_composer(self, cs: Plonk, seed: int, explain: bool = False):
+        """explain=True: a PlonkError with status PLK_E_DEGREE (an unsatisfied circuit) carries
+        the diagnosis of the failed proof as ``.report``."""
         proof = PlkProof()
         pis = (PlkFr * 4096)()
         cnt = C.c_size_t()
         st = _bind().plk_prove(self._key, cs._h, seed, C.byref(proof), pis, 4096, C.byref(cnt))
         if st != PLK_OK:
-            raise PlonkError(st, "create_proof")
+            raise _explained(PlonkError(st, "create_proof"), explain, self.diagnose)
         return Proof(proof), [fr_int(pis[i]) for i in range(cnt.value)]
+
+    def diagnose(self, max_failures: int = 16) -> CircuitReport:
+        """Which gates the witness of the most recent create_proof fails (plk_key_diagnose),
+        whether that proof succeeded or failed with PLK_E_DEGREE: one kernel on the witness
+        still on the device, no proof re-run. PlonkError(PLK_E_ARG) before any proof."""
+        lib = _bind()
+        return _check_call(lambda *a: lib.plk_key_diagnose(self._key, *a), "Prover.diagnose",
+                           max_failures)
 
     def lane(self) -> "ProverLane":
         """A concurrent prover over this key (plk_prover_create): own stream, MSM workspace
@@ -900,20 +1021,26 @@ class ProverLane:
                                         slice_start, rank, world, C.cast(fn, C.c_void_p), None),
                "plk_prover_shard")
 
-    def prove_composer(self, cs: Plonk, seed: int):
+    def prove_composer(self, cs: Plonk, seed: int, explain: bool = False):
         proof = PlkProof()
         pis = (PlkFr * 4096)()
         cnt = C.c_size_t()
         st = _bind().plk_prover_prove(self._h, cs._h, seed, C.byref(proof), pis, 4096,
                                       C.byref(cnt))
         if st != PLK_OK:
-            raise PlonkError(st, "create_proof")
+            raise _explained(PlonkError(st, "create_proof"), explain, self.diagnose)
         return Proof(proof), [fr_int(pis[i]) for i in range(cnt.value)]
 
-    def create_proof(self, seed: int, circuit):
+    def create_proof(self, seed: int, circuit, explain: bool = False):
         cs = Plonk()
         circuit.synthesize(cs)
-        return self.prove_composer(cs, seed)
+        return self.prove_composer(cs, seed, explain)
+
+    def diagnose(self, max_failures: int = 16) -> CircuitReport:
+        """Prover.diagnose on this lane's most recent proof (plk_prover_diagnose), on its stream."""
+        lib = _bind()
+        return _check_call(lambda *a: lib.plk_prover_diagnose(self._h, *a), "ProverLane.diagnose",
+                           max_failures)
 
     def msm_stats(self, reset: bool = False):
         """(k_accumulate ms, launches, point additions, MSM points) since the last reset."""

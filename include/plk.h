@@ -328,6 +328,56 @@ int plk_prover_msm_stats(plk_prover* p, int reset, double* accumulate_ms, uint64
  * Either output may be NULL. */
 int plk_prover_commit_info(const plk_prover* p, int basis[4], uint64_t entries[4]);
 
+/* ---- circuit check: which gates a witness fails -------------------------------------------
+ * Every gate identity of the quotient's numerator evaluated on its own at the gate (not folded
+ * with separation challenges): the job of a mock prover. The permutation terms are left out:
+ * wires are witness indices, so copy constraints hold by construction. A circuit passes exactly
+ * when no bit is set on any gate, which is when plk_prove succeeds (up to the negligible chance
+ * that a random challenge cancels a non-zero term). The next row of gate i is gate i + 1, of the
+ * last gate the all-zero row. Mask bits of a gate (a bit is set when the term is non-zero):
+ *   PLK_GATE_ARITH       q_arith (q_m a b + q_l a + q_r b + q_o o + q_4 d + q_c) + PI, always
+ *                        evaluated; its value is the reported residual
+ *   PLK_GATE_RANGE(j)    j < 4, q_range != 0:  delta(o - 4d), delta(b - 4o), delta(a - 4b),
+ *                        delta(d' - 4a), delta(f) = f (f - 1)(f - 2)(f - 3)
+ *   PLK_GATE_LOGIC(j)    j < 5, q_logic != 0, on the quads qa = a' - 4a, qb = b' - 4b,
+ *                        qd = d' - 4d and w = o: delta(qa), delta(qb), delta(qd), w - qa qb, and
+ *                        the xor / and identity selected by q_c
+ *   PLK_GATE_FIXED(j)    j < 4, q_fixed_group_add != 0, bit = d' - 2d: bit (bit - 1)(bit + 1),
+ *                        bit q_c - o, the x check, the y check
+ *   PLK_GATE_VAR(j)      j < 3, q_variable_group_add != 0: x1 y2 - d', the x3 check, the y3 check */
+#define PLK_GATE_ARITH 0x1u
+#define PLK_GATE_RANGE(j) (1u << (4 + (j)))
+#define PLK_GATE_LOGIC(j) (1u << (8 + (j)))
+#define PLK_GATE_FIXED(j) (1u << (16 + (j)))
+#define PLK_GATE_VAR(j) (1u << (20 + (j)))
+typedef struct { uint64_t gate; uint32_t mask; uint32_t _pad; plk_fr residual; } plk_gate_failure;
+/* by_class: gates failing a term of the arithmetic, range, logic, fixed-base, variable-base class */
+typedef struct { uint64_t gates, failing, by_class[5]; } plk_check_summary;
+/* A failing circuit is a verdict, not an error: all three return PLK_OK, summary->failing counts
+ * the failing gates, failures[0 .. min(cap, failing)) are the failing gates with the smallest
+ * indices in ascending order and *count (nullable) their number; cap = 0 with failures = NULL is
+ * a count-only call. PLK_E_ARG only for a NULL summary / circuit / p / key (and, for the two
+ * diagnoses, when there is no witness to check).
+ *
+ * plk_composer_check needs no key: the witness and the composer's compact gate records are
+ * uploaded and one kernel (k_gate_check) checks a gate per lane; a satisfied circuit reads back
+ * the summary alone. ctx = NULL evaluates the same per-gate function in a host loop, no GPU. */
+int plk_composer_check(plk_ctx* ctx, const plk_composer* circuit, plk_check_summary* summary,
+                       plk_gate_failure* failures, size_t cap, size_t* count);
+/* The same check of the witness and public inputs of this prover's most recent plk_prover_prove,
+ * whether it succeeded or failed with PLK_E_DEGREE: the witness is still on the device, so it
+ * costs one kernel on the prover's stream and no upload, against the gate table the key keeps.
+ * PLK_E_ARG when no witness has been uploaded yet (a plk_prover_prove refused with PLK_E_ARG
+ * counts as none). The prover is not disturbed: its next proof is what a fresh prover's would
+ * be. plk_key_diagnose is the same on the prover behind plk_prove. */
+int plk_prover_diagnose(plk_prover* p, plk_check_summary* summary,
+                        plk_gate_failure* failures, size_t cap, size_t* count);
+int plk_key_diagnose(plk_key* key, plk_check_summary* summary,
+                     plk_gate_failure* failures, size_t cap, size_t* count);
+/* HIP-event milliseconds of k_gate_check in the most recent plk_composer_check on this context
+ * or diagnosis of a key of this context (measurement only). */
+int plk_check_last_ms(plk_ctx* ctx, float* kernel_ms);
+
 /* ---- sharded commits: one proof, its MSMs split over the GPUs of a node ------------------
  * BASELINE configs[4] / SURVEY §8e. One process (rank) per GPU proves the SAME circuit with
  * the same seed; every rank runs the NTT / elementwise rounds on its own GPU (replicas, they
