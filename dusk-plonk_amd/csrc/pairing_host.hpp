@@ -256,20 +256,32 @@ inline void g2_to_bytes(const G2Aff& q, bool compressed, uint8_t* out) {
   fp_to_be(q.y.c0, out + 144);
 }
 
+// slot 0 of m = ML(c, Q0) ML(-w, Q1): the value the check raises to the final power (and what
+// plk_debug_miller returns)
+inline void miller_check_host(F12Host& m, const Fp2* lines0, const Fp2* lines1, const G1In& c,
+                              const G1In& w) {
+  miller_loop(m, lines0, !c.inf, c.x, c.y, true, lines1, !w.inf, w.x, fe_neg(w.y));
+}
+
 // e(c, Q0) == e(w, Q1), as ML(c, Q0) ML(-w, Q1) -> final exponentiation == 1. lines0 / lines1:
 // the prepared tables of Q0 / Q1; frob: frob_table.
 inline bool pairing_check_host(const Fp2* lines0, const Fp2* lines1, const Fp2* frob, const G1In& c,
                                const G1In& w) {
   F12Host m;
-  miller_loop(m, lines0, !c.inf, c.x, c.y, true, lines1, !w.inf, w.x, fe_neg(w.y));
+  miller_check_host(m, lines0, lines1, c, w);
   const int r = f12_final_exp(m, frob);
   return f12_is_one(m, r);
+}
+
+// slot 0 of m = ML(p, Q), one pair
+inline void miller_value_host(F12Host& m, const Fp2* lines, const G1In& p) {
+  miller_loop(m, lines, !p.inf, p.x, p.y, false, lines, false, p.x, p.y);
 }
 
 // out[72] = ML(p, Q)^(3 (p^12 - 1) / r), the six coefficients as (c0, c1) Montgomery limbs
 inline void pairing_value_host(const Fp2* lines, const Fp2* frob, const G1In& p, uint64_t* out) {
   F12Host m;
-  miller_loop(m, lines, !p.inf, p.x, p.y, false, lines, false, p.x, p.y);
+  miller_value_host(m, lines, p);
   const int r = f12_final_exp(m, frob);
   for (int i = 0; i < 6; ++i) {
     const Fp2 a = m.ld(r, i);

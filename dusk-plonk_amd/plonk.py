@@ -87,7 +87,8 @@ ABI_SYMBOLS = (
     # opening key, pairing check and the verdicts (OpeningKey here, Verifier in prover.py)
     "plk_opening_key_setup", "plk_opening_key_load", "plk_opening_key_points",
     "plk_opening_key_destroy", "plk_pairing_check", "plk_pairing_check_batch",
-    "plk_opening_key_last_pairing_ms", "plk_debug_pairing", "plk_verifier_pairs",
+    "plk_opening_key_last_pairing_ms", "plk_debug_pairing", "plk_debug_f12_op", "plk_debug_miller",
+    "plk_verifier_pairs",
     "plk_verifier_verify", "plk_verifier_verify_each", "plk_verifier_last_each_stats",
     # compact proofs and the ingest stage (g1_decompress / g1_subgroup_check here, the rest in
     # prover.py)
@@ -194,6 +195,8 @@ def _lib():
             "plk_pairing_check_batch": (i32, [vp, vp, vp, sz, vp]),
             "plk_opening_key_last_pairing_ms": (i32, [vp, C.POINTER(C.c_float)]),
             "plk_debug_pairing": (i32, [vp, vp, vp, sz, vp]),
+            "plk_debug_f12_op": (i32, [vp, i32, vp, vp, sz, vp]),
+            "plk_debug_miller": (i32, [vp, vp, vp, vp, vp, sz, vp]),
             "plk_g1_decompress_batch": (i32, [vp, vp, sz, i32, vp, vp]),
             "plk_g1_subgroup_check_batch": (i32, [vp, vp, sz, vp]),
             "plk_ingest_last_ms": (i32, [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
@@ -1149,4 +1152,48 @@ def debug_pairing(points, q, ctx: "Context | None" = None) -> np.ndarray:
     out = np.zeros((a.shape[0], 72), dtype=np.uint64)
     _check(_lib().plk_debug_pairing(None if ctx is None else ctx.handle, _ptr(a), _ptr(g), a.shape[0],
                                     _ptr(out)), "plk_debug_pairing")
+    return out
+
+
+# plk_debug_f12_op's op codes (include/plk.h)
+F12_OPS = {"f2_mul": 0, "f2_sqr": 1, "f2_inv": 2, "f2_mul_xi": 3, "mul": 4, "sqr": 5, "cyc_sqr": 6,
+           "inv_even": 7, "conj": 8, "frob1": 9, "frob2": 10, "mul_line": 11, "final_exp": 12}
+F12_IN_PLACE = 0x100
+
+
+def debug_f12_op(op, a, b=None, ctx: "Context | None" = None, in_place: bool = False) -> np.ndarray:
+    """Test support (plk_debug_f12_op): one operation of the pairing's tower (a name of F12_OPS) on
+    uint64[n, 72] rows (debug_pairing's layout); b: the second operand's rows for f2_mul and mul,
+    (c0, c2, y) in limbs 0..29 for mul_line. in_place: conj / frob1 / frob2 on the operand's own
+    slot. ctx = None: the host code; otherwise the kernel. uint64[n, 72]."""
+    x = np.ascontiguousarray(np.asarray(a, dtype=np.uint64).reshape(-1, 72))
+    y = None
+    if b is not None:
+        y = np.ascontiguousarray(np.asarray(b, dtype=np.uint64).reshape(-1, 72))
+        if y.shape != x.shape:
+            raise PlonkError(PLK_E_ARG, "debug_f12_op: a and b hold the same number of rows")
+    out = np.zeros_like(x)
+    code = F12_OPS[op] | (F12_IN_PLACE if in_place else 0)
+    _check(_lib().plk_debug_f12_op(None if ctx is None else ctx.handle, code, _ptr(x),
+                                   None if y is None else _ptr(y), x.shape[0], _ptr(out)),
+           "plk_debug_f12_op")
+    return out
+
+
+def debug_miller(p0, q0, p1=None, q1=None, ctx: "Context | None" = None) -> np.ndarray:
+    """Test support (plk_debug_miller): the raw Miller value ML(p0_i, q0), or with p1 / q1 the
+    check's ML(p0_i, q0) ML(-p1_i, q1), for uint64[n, 13] G1 points and uint64[25] G2 points, as
+    uint64[n, 72]. ctx = None: the host code; otherwise the kernel."""
+    a = np.ascontiguousarray(np.asarray(p0, dtype=np.uint64).reshape(-1, 13))
+    g0 = np.ascontiguousarray(np.asarray(q0, dtype=np.uint64).reshape(G2_WORDS))
+    c = g1 = None
+    if p1 is not None:
+        c = np.ascontiguousarray(np.asarray(p1, dtype=np.uint64).reshape(-1, 13))
+        g1 = np.ascontiguousarray(np.asarray(q1, dtype=np.uint64).reshape(G2_WORDS))
+        if c.shape != a.shape:
+            raise PlonkError(PLK_E_ARG, "debug_miller: p0 and p1 hold the same number of points")
+    out = np.zeros((a.shape[0], 72), dtype=np.uint64)
+    _check(_lib().plk_debug_miller(None if ctx is None else ctx.handle, _ptr(a), _ptr(g0),
+                                   None if c is None else _ptr(c), None if g1 is None else _ptr(g1),
+                                   a.shape[0], _ptr(out)), "plk_debug_miller")
     return out

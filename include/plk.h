@@ -879,6 +879,34 @@ int plk_debug_fold_weights(plk_ctx* ctx, const uint8_t entropy[32], const plk_fr
  * coefficient order and power (the cube), not a reference-compatible Gt encoding. q: finite,
  * canonical, on the twist, of order r; n <= 4096. */
 int plk_debug_pairing(plk_ctx* ctx, const plk_g1* p, const plk_g2* q, size_t n, uint64_t* out);
+/* One operation of the pairing's tower (csrc/pairing.hpp) on n rows of plk_debug_pairing's layout
+ * (72 u64: the six Fp2 coefficients of w^0 .. w^5 as (c0, c1) Montgomery limbs): out row i =
+ * op(a row i, b row i). ctx = NULL: the host slot store; otherwise one lane per row over the
+ * kernel's wave-tiled workspace. Ops:
+ *    0 f2_mul a b      1 f2_sqr a      2 f2_inv a      3 f2_mul_xi a: the Fp2 function applied to
+ *      each of the six coefficients (of a and b pairwise)
+ *    4 f12_mul a b     5 f12_sqr a     6 f12_cyc_sqr a (a in the cyclotomic subgroup; undefined
+ *      elsewhere)      7 f12_inv_even a (a in Fp6: even coefficients; the odd ones return zero)
+ *    8 f12_conj a      9 f12_frob a^p                 10 f12_frob a^(p^2)
+ *      each out of place, or with PLK_F12_IN_PLACE added to the op on the operand's own slot
+ *   11 f12_mul_line a (c0 + c2 w^2 + y w^3): b row = c0 (limbs 0..11), c2 (12..23), y (24..29)
+ *   12 f12_final_exp a: a^(3 (p^12 - 1) / r)
+ * The operands of an Fp12 operation sit in distinct slots and the result in a third, as the
+ * functions require. b may be NULL for the ops of a alone (it is not read). PLK_E_ARG: another op,
+ * PLK_F12_IN_PLACE on an op other than 8..10, a NULL a / out / needed b, a limb row of a or of a
+ * needed b (all 72 limbs) that is not canonical, n = 0, n > 4096. */
+#define PLK_F12_IN_PLACE 0x100
+int plk_debug_f12_op(plk_ctx* ctx, int op, const uint64_t* a, const uint64_t* b, size_t n,
+                     uint64_t* out);
+/* out[72 i ..] = the raw Miller value, before the final exponentiation, in the same layout.
+ * p1 = NULL: ML(p0_i, q0), what plk_debug_pairing raises to its power (q1 is not read). Otherwise
+ * ML(p0_i, q0) ML(-p1_i, q1) with the squarings shared, exactly the value plk_pairing_check[_batch]
+ * computes for the pair (C, W) = (p0_i, p1_i) against (H, beta_h) = (q0, q1). A point at infinity
+ * contributes the factor one. ctx = NULL: the host code; otherwise a kernel that makes k_pairing's
+ * call. p0, p1: plk_g1 rules of plk_msm_points (on the curve; the subgroup is not checked); q0, q1:
+ * finite, canonical, on the twist, of order r; n <= 4096. */
+int plk_debug_miller(plk_ctx* ctx, const plk_g1* p0, const plk_g2* q0, const plk_g1* p1,
+                     const plk_g2* q1, size_t n, uint64_t* out);
 
 #ifdef __cplusplus
 }

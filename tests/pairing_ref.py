@@ -122,6 +122,81 @@ def f12conj(a):
     return [a[i] if i % 2 == 0 else f2neg(a[i]) for i in range(6)]
 
 
+# What the per-operation tests of csrc/pairing.hpp compare with (tests/pairing_tower_ops.py). Each
+# is derived another way than the product's formula: the square is the general product, a
+# Frobenius map a literal power, the inverse a polynomial gcd.
+F12_ZERO = [(0, 0)] * 6
+
+
+def f12sqr(a):
+    return f12mul(a, a)
+
+
+def f12frob(a, k):
+    """a^(p^k) as a literal power (no coefficient table)."""
+    return f12pow(a, p ** k)
+
+
+def _poly_trim(a):
+    while a and a[-1] == (0, 0):
+        a = a[:-1]
+    return a
+
+
+def _poly_divmod(a, b):
+    """Quotient and remainder in Fp2[w]; coefficient lists, lowest first, b trimmed and not zero."""
+    a, q = list(a), [(0, 0)] * max(len(a) - len(b) + 1, 0)
+    lead = f2inv(b[-1])
+    for k in range(len(a) - len(b), -1, -1):
+        c = f2mul(a[k + len(b) - 1], lead)
+        q[k] = c
+        for i, bi in enumerate(b):
+            a[k + i] = f2sub(a[k + i], f2mul(c, bi))
+    return q, _poly_trim(a[:len(b) - 1])
+
+
+def _poly_mul(a, b):
+    out = [(0, 0)] * (len(a) + len(b) - 1) if a and b else []
+    for i, ai in enumerate(a):
+        for j, bj in enumerate(b):
+            out[i + j] = f2add(out[i + j], f2mul(ai, bj))
+    return out
+
+
+def _poly_sub(a, b):
+    n = max(len(a), len(b))
+    a, b = a + [(0, 0)] * (n - len(a)), b + [(0, 0)] * (n - len(b))
+    return _poly_trim([f2sub(x, y) for x, y in zip(a, b)])
+
+
+def f12inv(a):
+    """1 / a by the extended Euclidean algorithm on a(w) and w^6 - xi in Fp2[w] (w^6 - xi is
+    irreducible, so the gcd of a non-zero a is a constant). The inverse of zero is zero, the
+    product's convention."""
+    r0, r1 = [f2neg(XI)] + [(0, 0)] * 5 + [(1, 0)], _poly_trim(list(a))
+    t0, t1 = [], [(1, 0)]  # r_i = t_i a mod (w^6 - xi)
+    if not r1:
+        return list(F12_ZERO)
+    while len(r1) > 1:
+        q, rem = _poly_divmod(r0, r1)
+        r0, r1, t0, t1 = r1, rem, t1, _poly_sub(t0, _poly_mul(q, t1))
+    c = f2inv(r1[0])
+    out = [f2mul(c, x) for x in t1]
+    assert len(out) <= 6
+    return out + [(0, 0)] * (6 - len(out))
+
+
+def easy_part(f):
+    """f^((p^6 - 1)(p^2 + 1)): an element of the cyclotomic subgroup (order p^4 - p^2 + 1)."""
+    g = f12mul(f12conj(f), f12inv(f))
+    return f12mul(f12frob(g, 2), g)
+
+
+def line(c0, c2, y):
+    """The Fp12 element c0 + c2 w^2 + y w^3 (y in Fp) of a Miller line."""
+    return [c0, (0, 0), c2, (y % p, 0), (0, 0), (0, 0)]
+
+
 # --------------------------------------------------------------------------- G2 (affine)
 def g2_is_on_curve(q) -> bool:
     if q is None:
@@ -187,6 +262,11 @@ def miller_loop(pt, q):
 
 def final_power(f):
     return f12pow(f, FINAL_POWER)
+
+
+def final_power_cubed(f):
+    """f^(3 (p^12 - 1) / r): what the product's f12_final_exp computes."""
+    return f12pow(final_power(f), 3)
 
 
 def pairing(pt, q):

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import pairing_ref as R
+import pairing_tower_ops as T
 import pyref as P
 from make_pairing_vectors import OUT, f12_from_row, f12_row, g2_row
 
@@ -87,6 +88,24 @@ def test_check_accepts_and_rejects(plk):
     assert not R.pairing_check(P.g1_add(c, P.G1_GEN), w, h, bh)
 
 
+def test_check_with_points_outside_the_subgroup(plk):
+    """T = (0, 2) is on the curve, of order 3, and makes the line's w^2 coefficient zero. The
+    check takes on-curve points without a subgroup test; its answer for pairs with T in them is
+    the restatement's, and since T = r T' lies in r E the reduced pairing sends it to one: a
+    commitment moved by T passes (DESIGN.md "Points outside G1")."""
+    rng = P.SplitMix64(0x7033)
+    tau, s = rng.fr(), rng.fr()
+    key = plk.OpeningKey.setup(tau)
+    h, bh = R.G2_GEN, R.g2_mul(R.G2_GEN, tau)
+    answers = {}
+    for name, (c, w) in T.off_subgroup_pairs(tau, P.g1_mul(P.G1_GEN, s)):
+        assert P.g1_is_on_curve(c) and P.g1_is_on_curve(w), name
+        answers[name] = key.check(pair_words(c, w))
+        assert answers[name] == R.pairing_check(c, w, h, bh), name
+    assert answers == {"(T, T)": True, "(C + T, W)": True, "(C, W + T)": True, "(T, O)": True,
+                       "(tau (W + T), W + T)": True}
+
+
 def test_check_refuses_malformed_points(plk):
     key = plk.OpeningKey.setup(5)
     g = g1_words(P.G1_GEN)
@@ -162,6 +181,8 @@ def test_null_arguments(plk):
     assert lib.plk_pairing_check(None, None, None) == plk.PLK_E_ARG
     assert lib.plk_pairing_check_batch(None, None, None, 0, None) == plk.PLK_E_ARG
     assert lib.plk_debug_pairing(None, None, None, 0, None) == plk.PLK_E_ARG
+    assert lib.plk_debug_f12_op(None, 0, None, None, 0, None) == plk.PLK_E_ARG
+    assert lib.plk_debug_miller(None, None, None, None, None, 0, None) == plk.PLK_E_ARG
     from dusk_plonk_amd.prover import _bind
     b = _bind()
     assert b.plk_verifier_pairs(None, None, None, None, 0, None) == plk.PLK_E_ARG

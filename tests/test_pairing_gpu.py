@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import g1_ingest_ref as ref
+import pairing_tower_ops as T
 import pyref as P
 from make_pairing_vectors import OUT
 
@@ -85,6 +86,24 @@ def test_check_batch(plk, gpu_ctx, honest, count):
         assert not got[k]
     if count == 1:  # and the honest pair alone
         assert list(key.check_batch(np.stack([P.g1_vec_to_np(list(honest[0]))]), gpu_ctx)) == [True]
+
+
+@pytest.mark.parametrize("first", [0, 3])
+def test_check_batch_with_points_outside_the_subgroup(plk, gpu_ctx, honest, first):
+    """The pairs of test_pairing_cpu's test_check_with_points_outside_the_subgroup (the order-3
+    point (0, 2) in C, in W, in both) at lanes 0, 63 and 64 of 65 pairs: the kernel's verdicts
+    are the host check's, pair by pair, and a wrong pair moved by T stays wrong."""
+    odd = T.off_subgroup_pairs(TAU, honest[0][1])
+    pairs = list(honest)
+    for i, lane in enumerate(ref.ABI_LANES):
+        pairs[lane] = odd[(first + i) % len(odd)][1]
+    c, w = honest[9]
+    pairs[9] = (P.g1_add(P.g1_add(c, P.G1_GEN), T.T3), w)
+    words = np.stack([P.g1_vec_to_np([c, w]) for c, w in pairs])
+    key = plk.OpeningKey.setup(TAU)
+    got = key.check_batch(words, gpu_ctx)
+    assert list(got) == [key.check(words[j]) for j in range(65)]
+    assert not got[9] and all(got[lane] for lane in ref.ABI_LANES)
 
 
 def test_check_batch_refuses_malformed_points(plk, gpu_ctx, honest):
