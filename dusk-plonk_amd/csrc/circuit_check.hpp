@@ -29,14 +29,6 @@ PLK_HD Fr ld_fr(const Fr* p) {
 #endif
 }
 
-// JubJub d = -10240/10241 (R domain)
-PLK_HD Fr edwards_d_mont() {
-  Fr x;
-  x.v[0] = 0xd6343eb1u; x.v[1] = 0x01065fd6u; x.v[2] = 0x37579d26u; x.v[3] = 0x292d7f6du;
-  x.v[4] = 0xe6bd7fd4u; x.v[5] = 0xf5fd9207u; x.v[6] = 0x4bfa2b48u; x.v[7] = 0x2a9318e7u;
-  return fe_to_mont(x);
-}
-
 // delta(f) = f (f - 1)(f - 2)(f - 3) != 0
 PLK_HD bool delta_nonzero(const Fr& f) {
   const Fr one = fe_one<FrCfg>();
@@ -44,8 +36,6 @@ PLK_HD bool delta_nonzero(const Fr& f) {
   // a product in a field vanishes exactly when a factor does
   return !(fe_is_zero(f) || fe_is_zero(f1) || fe_is_zero(f2) || fe_is_zero(f3));
 }
-
-PLK_HD Fr fe_quad(const Fr& x) { return fe_dbl(fe_dbl(x)); }
 
 // The gate's 11 selectors q (SEL_* order), its own wire values a b c (= o) d, the next row's
 // an bn cn dn and its public input pi (0 without one). cn enters no identity; it is taken so
@@ -90,7 +80,7 @@ PLK_HD GateVerdict gate_check(const Fr* q, const Fr& a, const Fr& b, const Fr& c
     if (!fe_eq(fe_mul(bit, q[SEL_QC]), c)) v.mask |= PLK_GATE_FIXED(1);
     const Fr y_alpha = fe_add(fe_mul(fe_sqr(bit), fe_sub(q[SEL_QR], one)), one);
     const Fr x_alpha = fe_mul(q[SEL_QL], bit);
-    const Fr prod = fe_mul(fe_mul(fe_mul(c, a), b), edwards_d_mont());
+    const Fr prod = fe_mul(fe_mul(fe_mul(c, a), b), edwards_d());
     const Fr x_lhs = fe_add(an, fe_mul(an, prod));
     const Fr x_rhs = fe_add(fe_mul(a, y_alpha), fe_mul(b, x_alpha));
     if (!fe_eq(x_lhs, x_rhs)) v.mask |= PLK_GATE_FIXED(2);
@@ -102,7 +92,7 @@ PLK_HD GateVerdict gate_check(const Fr* q, const Fr& a, const Fr& b, const Fr& c
     // gate (x1, y1, x2, y2) = (a, b, c, d), next row (x3, y3, ., x1 y2)
     if (!fe_eq(fe_mul(a, d), dn)) v.mask |= PLK_GATE_VAR(0);
     const Fr y1x2 = fe_mul(b, c);
-    const Fr dprod = fe_mul(fe_mul(edwards_d_mont(), dn), y1x2);
+    const Fr dprod = fe_mul(fe_mul(edwards_d(), dn), y1x2);
     if (!fe_eq(fe_add(dn, y1x2), fe_add(an, fe_mul(an, dprod)))) v.mask |= PLK_GATE_VAR(1);
     if (!fe_eq(fe_add(fe_mul(b, d), fe_mul(a, c)), fe_sub(bn, fe_mul(bn, dprod))))
       v.mask |= PLK_GATE_VAR(2);

@@ -56,7 +56,9 @@ struct Rng {
   Fr fr_mont() { return below_r(); }
 };
 
-enum { QM = 0, QL, QR, QO, Q4, QC, QARITH, QRANGE, QLOGIC, QFIXED, QVAR };
+enum { QM = SEL_QM, QL = SEL_QL, QR = SEL_QR, QO = SEL_QO, Q4 = SEL_Q4, QC = SEL_QC,
+       QARITH = SEL_QARITH, QRANGE = SEL_QRANGE, QLOGIC = SEL_QLOGIC, QFIXED = SEL_QFIXED,
+       QVAR = SEL_QVAR };  // the selector rows (protocol.hpp), short
 
 Gate default_gate() {
   Gate g;
@@ -396,16 +398,6 @@ int prover_commit(plk_prover* P, const std::vector<const Fr*>& ptrs,
   return key_commit(P->key, *P->ws, ptrs, lens, outs, statuses, P->stream, cap);
 }
 
-// JubJub twisted-Edwards d = -10240/10241 mod r
-// (0x2a9318e74bfa2b48f5fd9207e6bd7fd4292d7f6d37579d2601065fd6d6343eb1), Montgomery form
-Fr edwards_d() {
-  static const uint32_t w[8] = {0xd6343eb1u, 0x01065fd6u, 0x37579d26u, 0x292d7f6du,
-                                0xe6bd7fd4u, 0xf5fd9207u, 0x4bfa2b48u, 0x2a9318e7u};
-  Fr x;
-  for (int i = 0; i < 8; ++i) x.v[i] = w[i];
-  return fe_to_mont(x);
-}
-
 Fr d2h_fr(const Fr* p, hipStream_t s) {
   thread_local PinnedBuf pin;
   if (pin.alloc(sizeof(Fr)) != PLK_OK) return fe_zero<FrCfg>();
@@ -425,27 +417,21 @@ void quotient_constants(QuotientArgs& qa, const QuotientChallenges& ch, const Fr
   qa.alpha = ch.alpha;
   qa.beta = ch.beta;
   qa.gamma = ch.gamma;
-  qa.k1 = fr_u64(7);
-  qa.k2 = fr_u64(13);
-  qa.k3 = fr_u64(17);
+  qa.k1 = perm_k(1);
+  qa.k2 = perm_k(2);
+  qa.k3 = perm_k(3);
+  const SepPowers rk = sep_powers(ch.range_sep), lk = sep_powers(ch.logic_sep),
+                  fk = sep_powers(ch.fixed_sep), vk = sep_powers(ch.var_sep);
   qa.range_sep = ch.range_sep;
-  qa.kappa = fe_sqr(ch.range_sep);
-  qa.kappa2 = fe_sqr(qa.kappa);
-  qa.kappa3 = fe_mul(qa.kappa2, qa.kappa);
+  qa.kappa = rk.k, qa.kappa2 = rk.k2, qa.kappa3 = rk.k3;
   qa.has_range = has_range ? 1 : 0;
   qa.logic_sep = ch.logic_sep;
-  qa.lk = fe_sqr(ch.logic_sep);
-  qa.lk2 = fe_sqr(qa.lk);
-  qa.lk3 = fe_mul(qa.lk2, qa.lk);
-  qa.lk4 = fe_mul(qa.lk3, qa.lk);
+  qa.lk = lk.k, qa.lk2 = lk.k2, qa.lk3 = lk.k3, qa.lk4 = lk.k4;
   qa.has_logic = has_logic ? 1 : 0;
   qa.fixed_sep = ch.fixed_sep;
-  qa.fk = fe_sqr(ch.fixed_sep);
-  qa.fk2 = fe_sqr(qa.fk);
-  qa.fk3 = fe_mul(qa.fk2, qa.fk);
+  qa.fk = fk.k, qa.fk2 = fk.k2, qa.fk3 = fk.k3;
   qa.var_sep = ch.var_sep;
-  qa.vk = fe_sqr(ch.var_sep);
-  qa.vk2 = fe_sqr(qa.vk);
+  qa.vk = vk.k, qa.vk2 = vk.k2;
   qa.edwards_d = edwards_d();
   qa.has_fixed = has_fixed ? 1 : 0;
   qa.has_var = has_var ? 1 : 0;
@@ -825,8 +811,8 @@ int plk_key_compile(plk_srs* srs, const plk_composer* cs, const char* label, plk
     PLK_HIP_TRY(hipMemcpyAsync(dcodes.ptr, codes.data(), 4 * n * 4, hipMemcpyHostToDevice, s));
     TRY(key->sigma_lag.alloc(4 * n * sizeof(Fr)));
     hipLaunchKernelGGL(k_sigma_values, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, s,
-                       dcodes.as<uint32_t>(), key->dom->tw_fwd.as<Fr>(), n, fr_u64(7), fr_u64(13),
-                       fr_u64(17), key->sigma_lag.as<Fr>());
+                       dcodes.as<uint32_t>(), key->dom->tw_fwd.as<Fr>(), n, perm_k(1), perm_k(2),
+                       perm_k(3), key->sigma_lag.as<Fr>());
     PLK_HIP_TRY(hipGetLastError());
     TRY(key->sigma_coef.alloc(4 * n * sizeof(Fr)));
     Fr* sc = key->sigma_coef.as<Fr>();
@@ -834,10 +820,9 @@ int plk_key_compile(plk_srs* srs, const plk_composer* cs, const char* label, plk
       TRY(ntt_run(key->dom, key->sigma_lag.as<Fr>() + c * n, sc + c * n, n, -1, 0, nullptr, s, 1));
 
     // 3. commitments (key.rs:138-159): selectors swallow errors, sigmas propagate
-    const int order[11] = {QM, QL, QR, QO, QC, Q4, QARITH, QRANGE, QLOGIC, QFIXED, QVAR};
     std::vector<const Fr*> ptrs;
     std::vector<size_t> lens;
-    for (int q : order) {
+    for (int q : kKeyCommSel) {
       ptrs.push_back(qc + q * n);
       lens.push_back(n);
     }
@@ -1100,7 +1085,6 @@ int plk_prover_prove(plk_prover* P, const plk_composer* cs, uint64_t seed, plk_p
     const uint64_t nq = (uint64_t)QB * n;  // quotient domain (prover.hpp)
     Rng rng{seed};
     const Fr one = fe_one<FrCfg>();
-    const Fr K1 = fr_u64(7), K2 = fr_u64(13), K3 = fr_u64(17);
 
     // scratch (allocated once per prover)
     TRY(P->witness.alloc(std::max<size_t>(cs->witness.size(), 1) * sizeof(Fr)));
@@ -1132,16 +1116,7 @@ int plk_prover_prove(plk_prover* P, const plk_composer* cs, uint64_t seed, plk_p
     Fr* nsc = P->ntt_scratch.as<Fr>();
 
     // transcript seeded like Prover::new (prover.rs:54-55): Transcript::base(label, vk, m)
-    Transcript tr(key->label);
-    {
-      const char dom[] = "circuit_size";
-      tr.append_message("dom-sep", reinterpret_cast<const uint8_t*>(dom), sizeof(dom) - 1);
-      tr.append_u64("n", m);
-      const char* labels[15] = {"q_m", "q_l", "q_r", "q_o", "q_c", "q_4", "q_arith", "q_range",
-                                "q_logic", "q_fixed_group_add", "q_variable_group_add",
-                                "s_sigma_1", "s_sigma_2", "s_sigma_3", "s_sigma_4"};
-      for (int i = 0; i < 15; ++i) tr.append_commitment(labels[i], key->comms[i]);
-    }
+    Transcript tr = Transcript::base(key->label, key->comms, m);
     // public inputs (prover.rs:90-105)
     std::vector<std::pair<uint64_t, Fr>> pis;
     for (uint64_t i = 0; i < m; ++i)
@@ -1239,8 +1214,8 @@ int plk_prover_prove(plk_prover* P, const plk_composer* cs, uint64_t seed, plk_p
     const Fr gamma = tr.challenge_scalar("gamma");
     Fr* num = P->num.as<Fr>();
     Fr* den = P->den.as<Fr>();
-    TRY(pk_perm_numden(wl, S, key->sigma_lag.as<Fr>(), key->dom->tw_fwd.as<Fr>(), n, beta, gamma, K1,
-                       K2, K3, num, den, s));
+    TRY(pk_perm_numden(wl, S, key->sigma_lag.as<Fr>(), key->dom->tw_fwd.as<Fr>(), n, beta, gamma,
+                       perm_k(1), perm_k(2), perm_k(3), num, den, s));
     Fr* st = P->scan_tmp.as<Fr>();
     TRY(pk_scan(num, num, n, true, false, true, st, s));   // N_i = prod_{j<i} num_j
     TRY(pk_scan(den, den, n, true, true, false, st, s));   // S_i = prod_{j>=i} den_j
@@ -1329,7 +1304,6 @@ int plk_prover_prove(plk_prover* P, const plk_composer* cs, uint64_t seed, plk_p
     } else if (!pis.empty()) {
       TRY(coset_fwd(P->pi_coef.as<Fr>(), ev + 5 * nq, n, key->coset_pi));
     }
-    const Fr alpha2 = fe_sqr(alpha);
     QuotientArgs qa{};
     qa.z = ev;
     qa.a = ev + nq;
@@ -1395,128 +1369,74 @@ int plk_prover_prove(plk_prover* P, const plk_composer* cs, uint64_t seed, plk_p
     struct RTerm {
       const Fr* p;
       uint64_t len;
-      int ev;  // index of p(z) in the evaluation batch
+      int ev;   // index of p(z) in the evaluation batch
+      int lin;  // its scalar s_t: the term of linearisation_scalars (protocol.hpp)
     };
     std::vector<RTerm> rt;
     EvalBatch eb{};
-    const Fr* polys[16] = {tc, wc, wc + S, wc + 2 * S, wc + 3 * S, sc, sc + n, sc + 2 * n,
-                           qc + QARITH * n, qc + QC * n, qc + QL * n, qc + QR * n,
-                           wc, wc + S, wc + 3 * S, zc};
-    const uint64_t lens[16] = {3 * n + t4_len, n + 2, n + 2, n + 2, n + 2, n, n, n, n, n, n, n,
-                               n + 2, n + 2, n + 2, n + 3};
+    // the batch begins with the proof's 16 evaluations in plk_proof order (Eval); r's place holds
+    // t(z) until r(z) is formed from the others
+    const Fr* polys[EV_COUNT] = {wc, wc + S, wc + 2 * S, wc + 3 * S, wc, wc + S, wc + 3 * S,
+                                 qc + QARITH * n, qc + QC * n, qc + QL * n, qc + QR * n,
+                                 sc, sc + n, sc + 2 * n, tc, zc};
+    const uint64_t lens[EV_COUNT] = {n + 2, n + 2, n + 2, n + 2, n + 2, n + 2, n + 2, n, n, n, n,
+                                     n, n, n, 3 * n + t4_len, n + 3};
     uint32_t ne = 0;
-    for (int i = 0; i < 16; ++i, ++ne) {
+    for (int i = 0; i < EV_COUNT; ++i, ++ne) {
       eb.poly[i] = polys[i];
       eb.len[i] = lens[i];
-      eb.x[i] = i < 12 ? zeta : zw;
+      eb.x[i] = i == EV_A_NEXT || i == EV_B_NEXT || i == EV_D_NEXT || i == EV_PERM ? zw : zeta;
     }
-    auto rterm = [&](const Fr* p, uint64_t len, int have) {
+    auto rterm = [&](const Fr* p, uint64_t len, int lin, int have = -1) {
       if (have < 0) {  // a new evaluation at z
         eb.poly[ne] = p;
         eb.len[ne] = len;
         eb.x[ne] = zeta;
         have = (int)ne++;
       }
-      rt.push_back(RTerm{p, len, have});
+      rt.push_back(RTerm{p, len, have, lin});
     };
-    // in the order the scalars are formed below
-    rterm(qc + QM * n, n, -1);
-    rterm(qc + QL * n, n, 10);
-    rterm(qc + QR * n, n, 11);
-    rterm(qc + QO * n, n, -1);
-    rterm(qc + Q4 * n, n, -1);
-    rterm(qc + QC * n, n, 9);
-    if (key->has_range) rterm(qc + QRANGE * n, n, -1);
-    if (key->has_logic) rterm(qc + QLOGIC * n, n, -1);
-    if (key->has_fixed) rterm(qc + QFIXED * n, n, -1);
-    if (key->has_var) rterm(qc + QVAR * n, n, -1);
-    rterm(zc, n + 3, -1);
-    rterm(sc + 3 * n, n, -1);
+    rterm(qc + QM * n, n, KC_QM);
+    rterm(qc + QL * n, n, KC_QL, EV_Q_L);
+    rterm(qc + QR * n, n, KC_QR, EV_Q_R);
+    rterm(qc + QO * n, n, KC_QO);
+    rterm(qc + Q4 * n, n, KC_Q4);
+    rterm(qc + QC * n, n, KC_QC, EV_Q_C);
+    if (key->has_range) rterm(qc + QRANGE * n, n, KC_QRANGE);
+    if (key->has_logic) rterm(qc + QLOGIC * n, n, KC_QLOGIC);
+    if (key->has_fixed) rterm(qc + QFIXED * n, n, KC_QFIXED);
+    if (key->has_var) rterm(qc + QVAR * n, n, KC_QVAR);
+    rterm(zc, n + 3, LIN_Z);
+    rterm(sc + 3 * n, n, KC_S4);
     // the evaluations land in host memory (no copy dispatch): read once the stream is done
     TRY(pk_eval(eb, ne, 3 * n + t4_len, P->eval_partial.as<Fr>(), static_cast<Fr*>(P->eval_dev), s));
     Fr evs[kMaxEval];
     PLK_HIP_TRY(stream_wait(s));
     std::memcpy(evs, P->eval_out.ptr, ne * sizeof(Fr));
-    const Fr t_eval = evs[0], a_e = evs[1], b_e = evs[2], c_e = evs[3], d_e = evs[4];
-    const Fr s1_e = evs[5], s2_e = evs[6], s3_e = evs[7];
-    const Fr qar_e = evs[8], qc_e = evs[9], ql_e = evs[10], qr_e = evs[11];
-    const Fr an_e = evs[12], bn_e = evs[13], dn_e = evs[14], perm_e = evs[15];
-    // the scalars s_t of r(X) = arithmetic::linearize + range::linearize + ... + permutation
+    const Fr t_eval = evs[EV_R];
+    // the scalars s_t of r(X) = arithmetic::linearize + range::linearize + ... + permutation,
+    // those of the terms this key has, in the terms' order
+    Fr ch[CH_COUNT] = {};
+    ch[CH_BETA] = beta, ch[CH_GAMMA] = gamma, ch[CH_ALPHA] = alpha, ch[CH_Z] = zeta;
+    ch[CH_RANGE] = range_sep, ch[CH_LOGIC] = logic_sep, ch[CH_FIXED] = fixed_sep, ch[CH_VAR] = var_sep;
+    AtZ at;  // z^n and L1(z)
+    (void)at_z(zeta, key->k, key->dom->n_inv, one, at);
+    Fr lin[LIN_Z + 1];
+    linearisation_scalars(evs, ch, at.l1, qa.edwards_d, [&](int t, const Fr& v) { lin[t] = v; });
     std::vector<Fr> rs;
-    rs.push_back(fe_mul(qar_e, fe_mul(a_e, b_e)));  // q_m
-    rs.push_back(fe_mul(qar_e, a_e));               // q_l
-    rs.push_back(fe_mul(qar_e, b_e));               // q_r
-    rs.push_back(fe_mul(qar_e, c_e));               // q_o
-    rs.push_back(fe_mul(qar_e, d_e));               // q_4
-    rs.push_back(qar_e);                            // q_c
-    if (key->has_range) {
-      const Fr two = fe_dbl(one), three = fe_add(two, one);
-      auto delta = [&](const Fr& f) {
-        return fe_mul(fe_mul(f, fe_sub(f, one)), fe_mul(fe_sub(f, two), fe_sub(f, three)));
-      };
-      auto four = [](const Fr& v) { return fe_dbl(fe_dbl(v)); };
-      Fr r = delta(fe_sub(c_e, four(d_e)));
-      r = fe_add(r, fe_mul(delta(fe_sub(b_e, four(c_e))), qa.kappa));
-      r = fe_add(r, fe_mul(delta(fe_sub(a_e, four(b_e))), qa.kappa2));
-      r = fe_add(r, fe_mul(delta(fe_sub(dn_e, four(a_e))), qa.kappa3));
-      rs.push_back(fe_mul(r, range_sep));
-    }
-    if (key->has_logic) {  // logic::linearize: q_logic(X) * sep * (...) at the evaluations
-      const Fr two = fe_dbl(one), three = fe_add(two, one), four = fe_dbl(two);
-      auto delta = [&](const Fr& f) {
-        return fe_mul(fe_mul(f, fe_sub(f, one)), fe_mul(fe_sub(f, two), fe_sub(f, three)));
-      };
-      const Fr qa_ = fe_sub(an_e, fe_mul(four, a_e));
-      const Fr qb_ = fe_sub(bn_e, fe_mul(four, b_e));
-      const Fr qd_ = fe_sub(dn_e, fe_mul(four, d_e));
-      Fr r = delta(qa_);
-      r = fe_add(r, fe_mul(delta(qb_), qa.lk));
-      r = fe_add(r, fe_mul(delta(qd_), qa.lk2));
-      r = fe_add(r, fe_mul(fe_sub(c_e, fe_mul(qa_, qb_)), qa.lk3));
-      r = fe_add(r, fe_mul(logic_xor_and(qa_, qb_, c_e, qd_, qc_e), qa.lk4));
-      rs.push_back(fe_mul(r, logic_sep));
-    }
-    if (key->has_fixed) {  // curve_scalar::linearize at the evaluations (q_l/q_r/q_c evals)
-      const Fr w = widget_fixed_base(a_e, an_e, b_e, bn_e, c_e, d_e, dn_e, ql_e, qr_e, qc_e,
-                                     qa.fk, qa.fk2, qa.fk3, qa.edwards_d);
-      rs.push_back(fe_mul(w, fixed_sep));
-    }
-    if (key->has_var) {  // curve_addtion::linearize
-      const Fr w = widget_var_base(a_e, an_e, b_e, bn_e, c_e, d_e, dn_e, qa.vk, qa.vk2,
-                                   qa.edwards_d);
-      rs.push_back(fe_mul(w, var_sep));
-    }
-    // z(X) * [(a + b z + g)(b + b K1 z + g)(c + b K2 z + g)(d + b K3 z + g) alpha + L1(z) alpha^2]
-    const Fr bz = fe_mul(beta, zeta);
-    Fr idc = fe_mul(fe_add(fe_add(a_e, bz), gamma), fe_add(fe_add(b_e, fe_mul(K1, bz)), gamma));
-    idc = fe_mul(idc, fe_add(fe_add(c_e, fe_mul(K2, bz)), gamma));
-    idc = fe_mul(idc, fe_add(fe_add(d_e, fe_mul(K3, bz)), gamma));
-    idc = fe_mul(idc, alpha);
-    const Fr zh = fe_sub(fe_pow_u64(zeta, n), one);  // Z_H(z)
-    const Fr l1 = fe_mul(zh, fe_inv(fe_mul(fr_u64(n), fe_sub(zeta, one))));
-    rs.push_back(fe_add(idc, fe_mul(l1, alpha2)));
-    // -sigma_4(X) * (a + b s1 + g)(b + b s2 + g)(c + b s3 + g) beta perm_eval alpha
-    Fr cpc = fe_add(fe_add(a_e, fe_mul(beta, s1_e)), gamma);
-    cpc = fe_mul(cpc, fe_add(fe_add(b_e, fe_mul(beta, s2_e)), gamma));
-    cpc = fe_mul(cpc, fe_add(fe_add(c_e, fe_mul(beta, s3_e)), gamma));
-    cpc = fe_mul(fe_mul(cpc, fe_mul(beta, perm_e)), alpha);
-    rs.push_back(fe_neg(cpc));
-    if (rs.size() != rt.size()) return PLK_E_DEVICE;  // the two lists are built in one order
+    for (const RTerm& t : rt) rs.push_back(lin[t.lin]);
     Fr r_e = fe_zero<FrCfg>();  // r(z) = sum_t s_t p_t(z)
     for (size_t t = 0; t < rt.size(); ++t) r_e = fe_add(r_e, fe_mul(rs[t], evs[rt[t].ev]));
+    evs[EV_R] = r_e;  // evs[0 .. EV_COUNT) are the proof's evaluations from here on
 
-    const char* elabels[17] = {"a_eval", "b_eval", "c_eval", "d_eval", "a_next_eval",
-                               "b_next_eval", "d_next_eval", "s_sigma_1_eval", "s_sigma_2_eval",
-                               "s_sigma_3_eval", "q_arith_eval", "q_c_eval", "q_l_eval",
-                               "q_r_eval", "perm_eval", "t_eval", "r_eval"};
-    const Fr evals17[17] = {a_e, b_e, c_e, d_e, an_e, bn_e, dn_e, s1_e, s2_e, s3_e,
-                            qar_e, qc_e, ql_e, qr_e, perm_e, t_eval, r_e};
-    for (int i = 0; i < 17; ++i) tr.append_scalar(elabels[i], evals17[i]);
+    for (const Step& st : kScript)
+      if (st.kind == STEP_EVAL) tr.append_scalar(st.label, evs[st.id]);
+      else if (st.kind == STEP_T_EVAL) tr.append_scalar(st.label, t_eval);
 
     // ---- openings (prover.rs:407-452): both v challenges precede both commits
     const Fr v1 = tr.challenge_scalar("v_challenge");
     const Fr v2 = tr.challenge_scalar("v_challenge");
-    const Fr zn = fe_pow_u64(zeta, n), z2n = fe_sqr(zn), z3n = fe_mul(z2n, zn);
+    const Fr zn = at.zn, z2n = fe_sqr(zn), z3n = fe_mul(z2n, zn);
     // W(X) = (sum v1^i p_i(X)) / (X - z), p = [quot, r, a, b, c, d, s1, s2, s3]
     // with quot = t_low + z^n t_mid + z^2n t_high + z^3n t_4 and r = sum_t s_t p_t expanded
     // in place (scalars v1 s_t)
@@ -1583,22 +1503,8 @@ int plk_prover_prove(plk_prover* P, const plk_composer* cs, uint64_t seed, plk_p
     proof->t_4_comm = tcom[3];
     proof->w_z_chall_comm = wcm[0];
     proof->w_z_chall_w_comm = wcm[1];
-    proof->a_eval = fr_to_abi(a_e);
-    proof->b_eval = fr_to_abi(b_e);
-    proof->c_eval = fr_to_abi(c_e);
-    proof->d_eval = fr_to_abi(d_e);
-    proof->a_next_eval = fr_to_abi(an_e);
-    proof->b_next_eval = fr_to_abi(bn_e);
-    proof->d_next_eval = fr_to_abi(dn_e);
-    proof->q_arith_eval = fr_to_abi(qar_e);
-    proof->q_c_eval = fr_to_abi(qc_e);
-    proof->q_l_eval = fr_to_abi(ql_e);
-    proof->q_r_eval = fr_to_abi(qr_e);
-    proof->s_sigma_1_eval = fr_to_abi(s1_e);
-    proof->s_sigma_2_eval = fr_to_abi(s2_e);
-    proof->s_sigma_3_eval = fr_to_abi(s3_e);
-    proof->r_poly_eval = fr_to_abi(r_e);
-    proof->perm_eval = fr_to_abi(perm_e);
+    plk_fr* pev = &proof->a_eval;  // Eval is plk_proof's order (protocol.hpp)
+    for (int i = 0; i < EV_COUNT; ++i) pev[i] = fr_to_abi(evs[i]);
     return PLK_OK;
   PLK_API_END
 }

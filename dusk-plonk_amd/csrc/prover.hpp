@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "internal.hpp"
+#include "protocol.hpp"
 
 namespace plk {
 
@@ -29,10 +30,6 @@ struct BlindBatch {
   BlindArgs b[4];
   uint32_t npoly;
 };
-
-// selector rows of the quotient-domain evaluation table
-enum { SEL_QM = 0, SEL_QL, SEL_QR, SEL_QO, SEL_Q4, SEL_QC, SEL_QARITH, SEL_QRANGE, SEL_QLOGIC,
-       SEL_QFIXED, SEL_QVAR, SEL_COUNTQ };
 
 // The quotient domain (round 3). The reference evaluates the quotient over the coset g H_8n
 // (quotient_poly.rs:52-58,115). The numerator (z times four wire factors, degree <= 5n + 6) is
@@ -84,7 +81,7 @@ struct QuotientArgs {
   Fr logic_sep, lk, lk2, lk3, lk4;  // logic separation challenge and its kappa powers
   Fr fixed_sep, fk, fk2, fk3;        // fixed-base scalar mul: sep, kappa = sep^2, ^2, ^3
   Fr var_sep, vk, vk2;               // variable-base addition: sep, kappa = sep^2, ^2
-  Fr edwards_d;                      // JubJub d = -10240/10241
+  Fr edwards_d;                      // JubJub d (protocol.hpp edwards_d)
   int has_range, has_logic, has_fixed, has_var;
   Fr vh_inv[kQBlocksMax];  // 1 / v_h of block m
   // k_quotient runs in the redundant form (ffr.hpp): a value with exponent e is stored as
@@ -126,69 +123,6 @@ struct LinComb {
   Fr s[kMaxTerms];
   uint32_t terms;
 };
-
-// delta_xor_and: 3(a + b + c) - 2 f + q_c (9c - 3(a + b)) with
-// f = w (w (4w - 18(a + b) + 81) + 18(a^2 + b^2) - 81(a + b) + 83) = 6 (a AND b) for quads
-PLK_HD Fr logic_xor_and(const Fr& a, const Fr& b, const Fr& w, const Fr& c,
-                                            const Fr& qc) {
-  auto k = [](uint32_t v) {
-    Fr x = fe_zero<FrCfg>();
-    x.v[0] = v;
-    return fe_to_mont(x);
-  };
-  const Fr ab = fe_add(a, b);
-  Fr f = fe_sub(fe_mul(k(4), w), fe_mul(k(18), ab));
-  f = fe_add(f, k(81));
-  f = fe_mul(w, f);
-  f = fe_add(f, fe_mul(k(18), fe_add(fe_sqr(a), fe_sqr(b))));
-  f = fe_sub(f, fe_mul(k(81), ab));
-  f = fe_add(f, k(83));
-  f = fe_mul(w, f);
-  const Fr e = fe_sub(fe_mul(k(3), fe_add(ab, c)), fe_dbl(f));
-  const Fr bb = fe_mul(qc, fe_sub(fe_mul(k(9), c), fe_mul(k(3), ab)));
-  return fe_add(bb, e);
-}
-
-// Fixed-base scalar multiplication widget (dusk-plonk ecc/scalar_mul/fixed_base; zksnarks
-// curve_scalar, un-vendored): accumulators (a, b) = point, d = scalar accumulator,
-// c = xy_alpha, q_l / q_r / q_c = x_beta / y_beta / x_beta y_beta of the gate's multiple.
-//   bit = d' - 2d;  bit (bit - 1)(bit + 1) + (bit q_c - c) k + x-check k^2 + y-check k^3
-PLK_HD Fr widget_fixed_base(const Fr& ax, const Fr& ax_n, const Fr& ay, const Fr& ay_n,
-                            const Fr& xy_alpha, const Fr& acc, const Fr& acc_n,
-                            const Fr& x_beta, const Fr& y_beta, const Fr& xy_beta, const Fr& k,
-                            const Fr& k2, const Fr& k3, const Fr& d) {
-  const Fr one = fe_one<FrCfg>();
-  const Fr bit = fe_sub(acc_n, fe_dbl(acc));
-  const Fr bit_consistency = fe_mul(fe_mul(bit, fe_sub(bit, one)), fe_add(bit, one));
-  const Fr y_alpha = fe_add(fe_mul(fe_sqr(bit), fe_sub(y_beta, one)), one);
-  const Fr x_alpha = fe_mul(x_beta, bit);
-  const Fr xy_consistency = fe_mul(fe_sub(fe_mul(bit, xy_beta), xy_alpha), k);
-  const Fr prod = fe_mul(fe_mul(fe_mul(xy_alpha, ax), ay), d);
-  const Fr x_lhs = fe_add(ax_n, fe_mul(ax_n, prod));
-  const Fr x_rhs = fe_add(fe_mul(ax, y_alpha), fe_mul(ay, x_alpha));
-  const Fr y_lhs = fe_sub(ay_n, fe_mul(ay_n, prod));
-  const Fr y_rhs = fe_add(fe_mul(ay, y_alpha), fe_mul(ax, x_alpha));
-  Fr id = fe_add(bit_consistency, xy_consistency);
-  id = fe_add(id, fe_mul(fe_sub(x_lhs, x_rhs), k2));
-  id = fe_add(id, fe_mul(fe_sub(y_lhs, y_rhs), k3));
-  return id;
-}
-
-// Variable-base addition widget (dusk-plonk ecc/curve_addition; zksnarks curve_addtion):
-// gate (x1, y1, x2, y2), next row (x3, y3, ., x1 y2):
-//   (x1 y2 - x1y2') + (x1y2' + y1 x2 - x3 (1 + d x1y2' y1 x2)) k
-//                   + (y1 y2 + x1 x2 - y3 (1 - d x1y2' y1 x2)) k^2
-PLK_HD Fr widget_var_base(const Fr& x1, const Fr& x3, const Fr& y1, const Fr& y3, const Fr& x2,
-                          const Fr& y2, const Fr& x1y2, const Fr& k, const Fr& k2, const Fr& d) {
-  const Fr xy_consistency = fe_sub(fe_mul(x1, y2), x1y2);
-  const Fr y1x2 = fe_mul(y1, x2);
-  const Fr y1y2 = fe_mul(y1, y2);
-  const Fr x1x2 = fe_mul(x1, x2);
-  const Fr dprod = fe_mul(fe_mul(d, x1y2), y1x2);
-  const Fr x3c = fe_sub(fe_add(x1y2, y1x2), fe_add(x3, fe_mul(x3, dprod)));
-  const Fr y3c = fe_sub(fe_add(y1y2, x1x2), fe_sub(y3, fe_mul(y3, dprod)));
-  return fe_add(fe_add(xy_consistency, fe_mul(x3c, k)), fe_mul(y3c, k2));
-}
 
 // out[col * stride + i] (col < 4, i < n): the wire's witness, zero for i >= m
 int pk_gather_wires(const Fr* witness, const uint32_t* idx, uint64_t m, uint64_t n, Fr* out,

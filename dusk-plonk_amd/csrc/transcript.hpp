@@ -9,6 +9,7 @@
 
 #include "abi.hpp"
 #include "g1.hpp"
+#include "protocol.hpp"
 
 namespace plk {
 
@@ -181,6 +182,16 @@ class Transcript {
   static void g1_compress(const plk_g1& p, uint8_t* out) {
     const G1Abi a = g1_load<false>(&p);
     g1_compress_bytes(a.x, a.y, a.inf, out);
+  }
+
+  // Transcript::base(label, vk, constraints) (prover.rs:54-55, verifier.rs:33-34): what every
+  // proof of a circuit starts from, the prover's transcript and the verifier's alike
+  static Transcript base(const std::string& label, const plk_g1 comms[KC_COUNT], uint64_t m) {
+    Transcript t(label);
+    t.append_message("dom-sep", reinterpret_cast<const uint8_t*>("circuit_size"), 12);
+    t.append_u64("n", m);
+    for (int i = 0; i < KC_COUNT; ++i) t.append_commitment(kKeyCommLabel[i], comms[i]);
+    return t;
   }
 
   const Strobe128& strobe() const { return s_; }

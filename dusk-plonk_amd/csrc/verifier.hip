@@ -5,9 +5,11 @@
 // One proof's check is e(C, H) == e(W, [tau]H) with C and W linear combinations of the 15 key
 // commitments, the generator and the proof's 11 commitments. Any number of proofs fold into
 // one such pair with random weights rho_j: (sum_j rho_j C_j, sum_j rho_j W_j).
-//  1. Host: the merlin replay of every proof (transcript.hpp), spread over up to 16 threads.
-//     t_eval is absorbed in mid-replay, so the host computes it — with Z_H(z), L_1(z) and the
-//     barycentric PI(z), their inversions batched into one per proof.
+// The protocol itself — the transcript's order, t_eval and the scalars of the linearisation — is
+// stated in protocol.hpp; this file walks it.
+//  1. Host: the merlin replay of every proof (transcript.hpp over protocol.hpp's kScript), spread
+//     over up to 16 threads. t_eval is absorbed in mid-replay, so the host computes it
+//     (proof_at_z: Z_H(z), L_1(z) and the barycentric PI(z) with one inversion per proof).
 //  2. GPU, k_fold_scalars: one lane per proof expands C_j and W_j into scalars on the points
 //     — t_comm, r_comm, both AggregateProof::flatten sums and the u batching flattened, so no
 //     intermediate point is formed. k_fold_shared sums the 16 shared scalars (key commitments
@@ -45,156 +47,70 @@ using namespace plk;
 namespace plk {
 namespace {
 
-constexpr int kShared = 16;  // 15 key commitments + the generator
-constexpr int kPerProof = 11;
+constexpr int kShared = KC_COUNT + 1;  // 15 key commitments + the generator
+constexpr int kGenerator = KC_COUNT;
+constexpr int kPerProof = PC_COUNT;
 
 struct FoldConst {
-  Fr omega, ed;  // the domain generator; the JubJub d = -10240 / 10241
+  Fr omega, ed;  // the domain generator; edwards_d()
 };
 
-PLK_HD Fr fr_small(uint32_t k) {
-  Fr r = fe_zero<FrCfg>();
-  r.v[0] = k;
-  return fe_to_mont(r);
-}
-
-PLK_HD Fr fr_delta(const Fr& f) {  // f (f - 1) (f - 2) (f - 3)
-  const Fr one = fe_one<FrCfg>();
-  const Fr f1 = fe_sub(f, one), f2 = fe_sub(f1, one), f3 = fe_sub(f2, one);
-  return fe_mul(fe_mul(f, f1), fe_mul(f2, f3));
-}
-
 // The scalars of rho (C_j, W_j) on the points (tests/verifier_pair.py states the same algebra):
-// shared[0..14] on the key commitments (q_m q_l q_r q_o q_c q_4 q_arith q_range q_logic
-// q_fixed_group_add q_variable_group_add s_sigma_1..4), shared[15] on the generator, pr[0..10] on
-// the proof's commitments in plk_proof order, ws[0..1] on (w_z_chall_comm, w_z_chall_w_comm) for W.
+// shared[KC_*] on the key commitments, shared[kGenerator] on the generator, pr[PC_*] on the
+// proof's commitments, ws[0..1] on (w_z_chall_comm, w_z_chall_w_comm) for W.
 PLK_HD void fold_scalars(const FoldIn& in, const FoldConst& k, Fr* shared, size_t shared_stride,
                         Fr* pr, Fr* ws) {
 #define M fe_mul
 #define A fe_add
-#define S fe_sub
-  const Fr &beta = in.ch[0], &gamma = in.ch[1], &alpha = in.ch[2], &rs = in.ch[3], &ls = in.ch[4],
-           &fs = in.ch[5], &vs = in.ch[6], &z = in.ch[7], &va = in.ch[8], &vb = in.ch[9],
-           &u = in.ch[10];
-  const Fr &a = in.ev[0], &b = in.ev[1], &c = in.ev[2], &d = in.ev[3], &an = in.ev[4],
-           &bn = in.ev[5], &dn = in.ev[6], &qar = in.ev[7], &qc = in.ev[8], &ql = in.ev[9],
-           &qr = in.ev[10], &s1 = in.ev[11], &s2 = in.ev[12], &s3 = in.ev[13], &rp = in.ev[14],
-           &pe = in.ev[15];
-  const Fr one = fe_one<FrCfg>();
+  const Fr &z = in.ch[CH_Z], &va = in.ch[CH_VA], &vb = in.ch[CH_VB], &u = in.ch[CH_U];
+  const Fr* e = in.ev;
   // every scalar leaves through these, times the proof's weight
   auto SH = [&](int i, const Fr& val) { shared[(size_t)i * shared_stride] = fe_mul(val, in.rho); };
   auto PR = [&](int i, const Fr& val) { pr[i] = fe_mul(val, in.rho); };
+  // r_comm (proof.rs:459-527), every term times va (its place in the aggregate): on the key
+  // commitments, but for z's scalar, which joins z_comm's below
+  Fr zc;
+  linearisation_scalars(e, in.ch, in.l1, k.ed, [&](int term, const Fr& val) {
+    if (term == LIN_Z)
+      zc = val;
+    else
+      SH(term, M(va, val));
+  });
   const Fr va2 = M(va, va), va3 = M(va2, va), va4 = M(va2, va2), va5 = M(va4, va), va6 = M(va3, va3),
            va7 = M(va6, va), va8 = M(va4, va4);
   const Fr vb2 = M(vb, vb), vb3 = M(vb2, vb);
-  const Fr four = fr_small(4);
-  // r_comm (proof.rs:459-527), every term times va (its place in the aggregate)
-  const Fr vq = M(va, qar);
-  SH(0, M(vq, M(a, b)));
-  SH(1, M(vq, a));
-  SH(2, M(vq, b));
-  SH(3, M(vq, c));
-  SH(4, vq);
-  SH(5, M(vq, d));
-  SH(6, fe_zero<FrCfg>());
-  {  // range::linearize
-    const Fr kap = M(rs, rs), kap2 = M(kap, kap), kap3 = M(kap2, kap);
-    Fr rr = fr_delta(S(c, M(four, d)));
-    rr = A(rr, M(fr_delta(S(b, M(four, c))), kap));
-    rr = A(rr, M(fr_delta(S(a, M(four, b))), kap2));
-    rr = A(rr, M(fr_delta(S(dn, M(four, a))), kap3));
-    SH(7, M(va, M(rr, rs)));
-  }
-  {  // logic::linearize
-    const Fr k1 = M(ls, ls), k2 = M(k1, k1), k3 = M(k2, k1), k4 = M(k2, k2);
-    const Fr qa = S(an, M(four, a)), qb = S(bn, M(four, b)), qd = S(dn, M(four, d));
-    const Fr& w = c;
-    const Fr c18 = fr_small(18), c81 = fr_small(81), c83 = fr_small(83), c9 = fr_small(9),
-             c3 = fr_small(3), c2 = fr_small(2);
-    const Fr sab = A(qa, qb);
-    // f = w (w (4 w - 18 (qa + qb) + 81) + 18 (qa^2 + qb^2) - 81 (qa + qb) + 83)
-    Fr f = A(S(M(four, w), M(c18, sab)), c81);
-    f = M(w, f);
-    f = A(f, M(c18, A(M(qa, qa), M(qb, qb))));
-    f = A(S(f, M(c81, sab)), c83);
-    f = M(w, f);
-    // 3 (qa + qb + qd) - 2 f + q_c (9 qd - 3 (qa + qb))
-    Fr xa = S(M(c3, A(sab, qd)), M(c2, f));
-    xa = A(xa, M(qc, S(M(c9, qd), M(c3, sab))));
-    Fr lt = fr_delta(qa);
-    lt = A(lt, M(fr_delta(qb), k1));
-    lt = A(lt, M(fr_delta(qd), k2));
-    lt = A(lt, M(S(w, M(qa, qb)), k3));
-    lt = A(lt, M(xa, k4));
-    SH(8, M(va, M(lt, ls)));
-  }
-  {  // curve_scalar::linearize (fixed base)
-    const Fr k1 = M(fs, fs), k2 = M(k1, k1), k3 = M(k2, k1);
-    const Fr &ax = a, &axn = an, &ay = b, &ayn = bn, &xya = c, &acc = d, &accn = dn;
-    const Fr &xb = ql, &yb = qr, &xyb = qc;
-    const Fr bit = S(accn, A(acc, acc));
-    const Fr ya = A(M(M(bit, bit), S(yb, one)), one);
-    const Fr xa = M(xb, bit);
-    const Fr prod = M(M(xya, ax), M(ay, k.ed));
-    Fr w = M(M(bit, S(bit, one)), A(bit, one));
-    w = A(w, M(S(M(bit, xyb), xya), k1));
-    w = A(w, M(S(A(axn, M(axn, prod)), A(M(ax, ya), M(ay, xa))), k2));
-    w = A(w, M(S(S(ayn, M(ayn, prod)), A(M(ay, ya), M(ax, xa))), k3));
-    SH(9, M(va, M(w, fs)));
-  }
-  {  // curve_addition::linearize (variable base)
-    const Fr k1 = M(vs, vs), k2 = M(k1, k1);
-    const Fr &x1 = a, &x3 = an, &y1 = b, &y3 = bn, &x2 = c, &y2 = d, &x1y2 = dn;
-    const Fr dp = M(M(k.ed, x1y2), M(y1, x2));
-    Fr w = S(M(x1, y2), x1y2);
-    w = A(w, M(S(A(x1y2, M(y1, x2)), A(x3, M(x3, dp))), k1));
-    w = A(w, M(S(A(M(y1, y2), M(x1, x2)), S(y3, M(y3, dp))), k2));
-    SH(10, M(va, M(w, vs)));
-  }
-  // permutation::linearize
-  const Fr b0 = A(A(a, M(beta, s1)), gamma), b1 = A(A(b, M(beta, s2)), gamma),
-           b2 = A(A(c, M(beta, s3)), gamma);
-  const Fr bz = M(beta, z);
-  Fr x = M(A(A(a, bz), gamma), A(A(b, M(fr_small(7), bz)), gamma));
-  x = M(x, A(A(c, M(fr_small(13), bz)), gamma));
-  x = M(x, A(A(d, M(fr_small(17), bz)), gamma));
-  x = M(x, alpha);
-  const Fr zc = A(x, M(in.l1, M(alpha, alpha)));  // on z_comm, inside r_comm
-  const Fr y = fe_neg(M(M(M(b0, b1), M(b2, beta)), M(pe, alpha)));
-  SH(11, va6);
-  SH(12, va7);
-  SH(13, va8);
-  SH(14, M(va, y));
+  SH(KC_S1, va6);
+  SH(KC_S2, va7);
+  SH(KC_S3, va8);
   // the evaluations of both flattened aggregates go on the generator, negated
-  Fr eva = A(in.t_eval, M(va, rp));
-  eva = A(eva, M(va2, a));
-  eva = A(eva, M(va3, b));
-  eva = A(eva, M(va4, c));
-  eva = A(eva, M(va5, d));
-  eva = A(eva, M(va6, s1));
-  eva = A(eva, M(va7, s2));
-  eva = A(eva, M(va8, s3));
-  Fr evb = A(pe, M(vb, an));
-  evb = A(evb, M(vb2, bn));
-  evb = A(evb, M(vb3, dn));
-  SH(15, fe_neg(A(eva, M(u, evb))));
+  Fr eva = A(in.t_eval, M(va, e[EV_R]));
+  eva = A(eva, M(va2, e[EV_A]));
+  eva = A(eva, M(va3, e[EV_B]));
+  eva = A(eva, M(va4, e[EV_C]));
+  eva = A(eva, M(va5, e[EV_D]));
+  eva = A(eva, M(va6, e[EV_S1]));
+  eva = A(eva, M(va7, e[EV_S2]));
+  eva = A(eva, M(va8, e[EV_S3]));
+  Fr evb = A(e[EV_PERM], M(vb, e[EV_A_NEXT]));
+  evb = A(evb, M(vb2, e[EV_B_NEXT]));
+  evb = A(evb, M(vb3, e[EV_D_NEXT]));
+  SH(kGenerator, fe_neg(A(eva, M(u, evb))));
   const Fr zn2 = M(in.zn, in.zn);
-  PR(0, A(va2, M(u, vb)));    // a_comm
-  PR(1, A(va3, M(u, vb2)));   // b_comm
-  PR(2, va4);                 // c_comm
-  PR(3, A(va5, M(u, vb3)));   // d_comm
-  PR(4, A(M(va, zc), u));        // z_comm
-  PR(5, one);                    // t_low .. t_4: [t] = sum_i z^(i n) t_i, times va^0
-  PR(6, in.zn);
-  PR(7, zn2);
-  PR(8, M(zn2, in.zn));
-  PR(9, z);                      // w_z_chall_comm at z
-  PR(10, M(u, M(z, k.omega)));   // w_z_chall_w_comm at z omega, times u
+  PR(PC_A, A(va2, M(u, vb)));
+  PR(PC_B, A(va3, M(u, vb2)));
+  PR(PC_C, va4);
+  PR(PC_D, A(va5, M(u, vb3)));
+  PR(PC_Z, A(M(va, zc), u));
+  PR(PC_T_LOW, fe_one<FrCfg>());  // t_low .. t_4: [t] = sum_i z^(i n) t_i, times va^0
+  PR(PC_T_MID, in.zn);
+  PR(PC_T_HIGH, zn2);
+  PR(PC_T_4, M(zn2, in.zn));
+  PR(PC_W_Z, z);                       // at z
+  PR(PC_W_ZW, M(u, M(z, k.omega)));    // at z omega, times u
   ws[0] = in.rho;
   ws[1] = M(u, in.rho);
 #undef M
 #undef A
-#undef S
 }
 
 // scalars: [16 shared][11 per proof][2 per proof]; tmp[k * count + j] = proof j's share of
@@ -349,7 +265,8 @@ namespace {
 // z = 1.
 int replay(const plk_verifier* v, const plk_proof& p, const plk_fr* pis, FoldIn& o) {
   const plk_fr* evals = &p.a_eval;
-  for (int i = 0; i < 16; ++i) {
+  const plk_g1* comms = &p.a_comm;
+  for (int i = 0; i < EV_COUNT; ++i) {
     if (!abi_canonical<FrCfg>(evals[i].l)) return PLK_E_ARG;
     o.ev[i] = fr_from_abi(evals[i]);
   }
@@ -360,98 +277,23 @@ int replay(const plk_verifier* v, const plk_proof& p, const plk_fr* pis, FoldIn&
     pi[i] = fr_from_abi(pis[i]);
   }
   Transcript t = v->base;
-  for (size_t i = 0; i < npi; ++i) t.append_scalar("pi", pi[i]);
-  t.append_commitment("a_w", p.a_comm);
-  t.append_commitment("b_w", p.b_comm);
-  t.append_commitment("c_w", p.c_comm);
-  t.append_commitment("d_w", p.d_comm);
-  const Fr beta = t.challenge_scalar("beta");
-  t.append_scalar("beta", beta);
-  const Fr gamma = t.challenge_scalar("gamma");
-  t.append_commitment("z", p.z_comm);
-  const Fr alpha = t.challenge_scalar("alpha");
-  o.ch[0] = beta;
-  o.ch[1] = gamma;
-  o.ch[2] = alpha;
-  o.ch[3] = t.challenge_scalar("range separation challenge");
-  o.ch[4] = t.challenge_scalar("logic separation challenge");
-  o.ch[5] = t.challenge_scalar("fixed base separation challenge");
-  o.ch[6] = t.challenge_scalar("variable base separation challenge");
-  t.append_commitment("t_low", p.t_low_comm);
-  t.append_commitment("t_mid", p.t_mid_comm);
-  t.append_commitment("t_high", p.t_high_comm);
-  t.append_commitment("t_4", p.t_4_comm);
-  const Fr z = t.challenge_scalar("z_challenge");
-  o.ch[7] = z;
-
-  const Fr one = fe_one<FrCfg>();
-  Fr zn = z;
-  for (uint32_t i = 0; i < v->log_n; ++i) zn = fe_sqr(zn);
-  const Fr z_h = fe_sub(zn, one), zm1 = fe_sub(z, one);
-  if (fe_is_zero(z_h) || fe_is_zero(zm1)) return PLK_E_ARG;
-  // one inversion for z_h, z - 1 and the barycentric denominators omega^-i z - 1 (none is zero:
-  // z is not in the domain). Zero public inputs are skipped, as in the reference (proof.rs:558).
-  std::vector<Fr> den;
-  den.reserve(npi + 2);
-  den.push_back(z_h);
-  den.push_back(zm1);
-  for (size_t i = 0; i < npi; ++i)
-    if (!fe_is_zero(pi[i])) den.push_back(fe_sub(fe_mul(v->pi_winv[i], z), one));
-  std::vector<Fr> pref(den.size());
-  Fr acc = one;
-  for (size_t i = 0; i < den.size(); ++i) {
-    pref[i] = acc;
-    acc = fe_mul(acc, den[i]);
-  }
-  Fr inv = fe_inv(acc);
-  for (size_t i = den.size(); i-- > 0;) {
-    const Fr di = den[i];
-    den[i] = fe_mul(inv, pref[i]);
-    inv = fe_mul(inv, di);
-  }
-  const Fr zh_inv = den[0];
-  const Fr l1 = fe_mul(fe_mul(z_h, v->n_inv), den[1]);  // z_h / (n (z - 1))
-  Fr pi_eval = fe_zero<FrCfg>();
-  size_t k = 2;
-  for (size_t i = 0; i < npi; ++i)
-    if (!fe_is_zero(pi[i])) pi_eval = fe_add(pi_eval, fe_mul(pi[i], den[k++]));
-  pi_eval = fe_mul(pi_eval, fe_mul(z_h, v->n_inv));
-  // t_eval (proof.rs:386-440)
-  const Fr *e = o.ev, &a = e[0], &b = e[1], &c = e[2], &d = e[3], &s1 = e[11], &s2 = e[12],
-           &s3 = e[13], &rp = e[14], &pe = e[15];
-  const Fr b0 = fe_add(fe_add(a, fe_mul(beta, s1)), gamma);
-  const Fr b1 = fe_add(fe_add(b, fe_mul(beta, s2)), gamma);
-  const Fr b2 = fe_add(fe_add(c, fe_mul(beta, s3)), gamma);
-  const Fr b3 = fe_mul(fe_mul(fe_add(d, gamma), pe), alpha);
-  const Fr b_term = fe_mul(fe_mul(b0, b1), fe_mul(b2, b3));
-  const Fr c_term = fe_mul(l1, fe_mul(alpha, alpha));
-  const Fr t_eval = fe_mul(fe_sub(fe_sub(fe_add(rp, pi_eval), b_term), c_term), zh_inv);
-  o.t_eval = t_eval;
-  o.l1 = l1;
-  o.zn = zn;
-  t.append_scalar("a_eval", e[0]);
-  t.append_scalar("b_eval", e[1]);
-  t.append_scalar("c_eval", e[2]);
-  t.append_scalar("d_eval", e[3]);
-  t.append_scalar("a_next_eval", e[4]);
-  t.append_scalar("b_next_eval", e[5]);
-  t.append_scalar("d_next_eval", e[6]);
-  t.append_scalar("s_sigma_1_eval", e[11]);
-  t.append_scalar("s_sigma_2_eval", e[12]);
-  t.append_scalar("s_sigma_3_eval", e[13]);
-  t.append_scalar("q_arith_eval", e[7]);
-  t.append_scalar("q_c_eval", e[8]);
-  t.append_scalar("q_l_eval", e[9]);
-  t.append_scalar("q_r_eval", e[10]);
-  t.append_scalar("perm_eval", e[15]);
-  t.append_scalar("t_eval", t_eval);
-  t.append_scalar("r_eval", e[14]);
-  o.ch[8] = t.challenge_scalar("v_challenge");
-  o.ch[9] = t.challenge_scalar("v_challenge");
-  t.append_commitment("w_z", p.w_z_chall_comm);
-  t.append_commitment("w_z_w", p.w_z_chall_w_comm);
-  o.ch[10] = t.challenge_scalar("batch");
-  o.rho = one;
+  for (const Step& st : kScript) switch (st.kind) {
+      case STEP_PI:
+        for (size_t i = 0; i < npi; ++i) t.append_scalar(st.label, pi[i]);
+        break;
+      case STEP_COMM: t.append_commitment(st.label, comms[st.id]); break;
+      case STEP_CHAL:
+        o.ch[st.id] = t.challenge_scalar(st.label);
+        if (st.id == CH_Z &&
+            !proof_at_z(o.ev, o.ch, o.ch[CH_Z], v->log_n, v->n_inv, pi.data(), v->pi_winv.data(),
+                        (uint32_t)npi, o.zn, o.l1, o.t_eval))
+          return PLK_E_ARG;
+        break;
+      case STEP_BETA: t.append_scalar(st.label, o.ch[CH_BETA]); break;
+      case STEP_EVAL: t.append_scalar(st.label, o.ev[st.id]); break;
+      case STEP_T_EVAL: t.append_scalar(st.label, o.t_eval); break;
+    }
+  o.rho = fe_one<FrCfg>();
   return PLK_OK;
 }
 
@@ -471,7 +313,7 @@ int random_weights(std::vector<FoldIn>& in) {
   os_entropy(seed);
   Transcript t("plk-verifier-fold");
   t.append_u64("count", in.size());
-  for (const FoldIn& f : in) t.append_scalar("u", f.ch[10]);
+  for (const FoldIn& f : in) t.append_scalar("u", f.ch[CH_U]);
   t.append_message("entropy", seed, sizeof seed);
   for (size_t j = 1; j < in.size(); ++j) {
     uint8_t b[16];
@@ -527,7 +369,7 @@ std::vector<plk_g1> batch_points(const plk_verifier* v, const plk_proof* proofs,
   const size_t n_c = kShared + (size_t)kPerProof * count;
   std::vector<plk_g1> pts(n_c + 2 * count);
   std::memcpy(pts.data(), v->comms, sizeof v->comms);
-  pts[15] = g1_generator_abi();
+  pts[kGenerator] = g1_generator_abi();
   for (size_t j = 0; j < count; ++j) {
     std::memcpy(&pts[kShared + kPerProof * j], &proofs[j].a_comm, kPerProof * sizeof(plk_g1));
     pts[n_c + 2 * j] = proofs[j].w_z_chall_comm;
@@ -563,7 +405,7 @@ int check_canonical(const plk_verifier* v, const plk_proof* proofs, const plk_fr
   const size_t npi = v->pi_idx.size();
   for (size_t j = 0; j < count; ++j) {
     const plk_fr* evals = &proofs[j].a_eval;
-    for (int i = 0; i < 16; ++i)
+    for (int i = 0; i < EV_COUNT; ++i)
       if (!abi_canonical<FrCfg>(evals[i].l)) return PLK_E_ARG;
   }
   for (size_t i = 0; i < npi * count; ++i)
@@ -605,7 +447,7 @@ int replay_on_device(plk_ctx* ctx, plk_verifier* v, const plk_proof* proofs, con
   const size_t n_c = kShared + (size_t)kPerProof * count, n_pts = n_c + 2 * count;
   std::vector<plk_g1> pts(n_pts);
   std::memcpy(pts.data(), v->comms, sizeof v->comms);
-  pts[15] = g1_generator_abi();
+  pts[kGenerator] = g1_generator_abi();
   std::vector<plk_fr> evals(16 * count);
   for (size_t j = 0; j < count; ++j) {
     std::memcpy(&pts[kShared + kPerProof * j], &proofs[j].a_comm, kPerProof * sizeof(plk_g1));
@@ -793,17 +635,8 @@ int plk_verifier_create(const char* label, uint64_t n, uint64_t m, const plk_g1 
   for (size_t i = 0; i < pi_count; ++i) v->pi_winv[i] = fe_pow_u64(winv, pi_indexes[i]);
   v->n_inv = fe_inv(fr_small((uint32_t)n));
   v->consts.omega = v->omega;
-  v->consts.ed = fe_neg(fe_mul(fr_small(10240), fe_inv(fr_small(10241))));
-  // Transcript::base(label, vk, constraints) (prover.rs:54-55, verifier.rs:33-34)
-  Transcript t(v->label);
-  static const char dom[] = "circuit_size";
-  t.append_message("dom-sep", reinterpret_cast<const uint8_t*>(dom), sizeof(dom) - 1);
-  t.append_u64("n", m);
-  static const char* labels[15] = {"q_m", "q_l", "q_r", "q_o", "q_c", "q_4", "q_arith", "q_range",
-                                   "q_logic", "q_fixed_group_add", "q_variable_group_add",
-                                   "s_sigma_1", "s_sigma_2", "s_sigma_3", "s_sigma_4"};
-  for (int i = 0; i < 15; ++i) t.append_commitment(labels[i], v->comms[i]);
-  v->base = t;
+  v->consts.ed = edwards_d();
+  v->base = Transcript::base(v->label, v->comms, m);
   *out = v.release();
   return PLK_OK;
   PLK_API_END
@@ -835,7 +668,7 @@ int plk_verifier_challenges(const plk_verifier* v, const plk_proof* proof, const
   FoldIn in;
   const int st = replay(v, *proof, public_inputs, in);
   if (st != PLK_OK) return st;
-  for (int i = 0; i < 11; ++i) out[i] = fr_to_abi(in.ch[i]);
+  for (int i = 0; i < CH_COUNT; ++i) out[i] = fr_to_abi(in.ch[i]);
   return PLK_OK;
   PLK_API_END
 }
@@ -986,7 +819,7 @@ int plk_verifier_challenges_batch(plk_ctx* ctx, plk_verifier* v, const plk_proof
   (void)hipEventElapsedTime(&v->replay_kernel_ms, v->e2, v->e3);
   if (status) return PLK_E_ARG;  // z_h(z) = 0 or z = 1 in some proof
   for (size_t j = 0; j < count; ++j)
-    for (int i = 0; i < 11; ++i) out[11 * j + i] = fr_to_abi(in[j].ch[i]);
+    for (int i = 0; i < CH_COUNT; ++i) out[CH_COUNT * j + i] = fr_to_abi(in[j].ch[i]);
   return PLK_OK;
   PLK_API_END
 }

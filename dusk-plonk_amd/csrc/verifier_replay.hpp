@@ -1,17 +1,19 @@
 // verifier_replay.hpp — the batch verifier's transcript replay on the GPU (verifier_replay.hip),
-// one proof per lane, and the per-proof fold weights. verifier.hip's replay() is the contract.
+// one proof per lane, and the per-proof fold weights. protocol.hpp states what is replayed: the
+// host's replay() (verifier.hip) and the compiled schedule here walk the same kScript.
 #pragma once
 #include <vector>
 
 #include "internal.hpp"
+#include "protocol.hpp"
 #include "transcript_dev.hpp"
 
 namespace plk {
 
 // What the replay hands to the scalar kernel for one proof (Montgomery form).
 struct FoldIn {
-  Fr ev[16];  // plk_proof order: a b c d a_next b_next d_next q_arith q_c q_l q_r s1 s2 s3 r perm
-  Fr ch[11];  // beta gamma alpha range logic fixed variable z v_a v_b u
+  Fr ev[EV_COUNT];  // indexed by Eval (plk_proof order)
+  Fr ch[CH_COUNT];  // indexed by Chal
   Fr t_eval, l1, zn, rho;
 };
 
@@ -21,9 +23,9 @@ struct ReplayLayout {
   uint32_t npi;
   PLK_HD uint32_t pi(uint32_t i) const { return 32u * i; }
   PLK_HD uint32_t comm(uint32_t c) const { return 32u * npi + 48u * c; }
-  PLK_HD uint32_t beta() const { return comm(11); }
+  PLK_HD uint32_t beta() const { return comm(PC_COUNT); }
   PLK_HD uint32_t eval(uint32_t e) const { return beta() + 32u + 32u * e; }
-  PLK_HD uint32_t t_eval() const { return eval(16); }
+  PLK_HD uint32_t t_eval() const { return eval(EV_COUNT); }
   PLK_HD uint32_t rows() const { return (t_eval() + 32u) / 4u + 2u; }  // a padding row at either end
 };
 
