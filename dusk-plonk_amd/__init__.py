@@ -9,7 +9,7 @@ from .plonk import (  # noqa: F401
     PLK_E_DEVICE, PLK_E_NODEV, PLK_E_OOM, PLK_OK, PlonkError, PlonkParams, PointsValue, build_info, check_build,
     debug_pairing, device_count, g1_decompress, g1_subgroup_check, g1_sum, ingest_last_ms, msm_points, msm_points_ranges, msm_sharded,
     SrsVerdict, debug_glv_split, g1_mul, g1_mul_last_ms, g2_from_bytes, g2_to_bytes,
-    check_last_ms, debug_f12_op, debug_miller,
+    check_last_ms, debug_f12_op, debug_miller, debug_g1_ntt, kzg_last_open_ms,
 )
 from .prover import CircuitReport, GateFailure  # noqa: F401,E402
 
@@ -21,5 +21,5 @@ __all__ = [
     "msm_points_ranges", "msm_sharded",
     "SrsVerdict", "debug_glv_split", "g1_mul", "g1_mul_last_ms", "g2_from_bytes", "g2_to_bytes",
     "CircuitReport", "GateFailure", "check_last_ms", "debug_f12_op",
-    "debug_miller",
+    "debug_miller", "debug_g1_ntt", "kzg_last_open_ms",
 ]

@@ -300,6 +300,7 @@ int plk_srs_setup_range(plk_ctx* ctx, const plk_fr* tau, uint64_t start, size_t 
   if ((st = srs_alloc(ctx, n_points, s))) return st;
   if ((st = srs_generate(s.get(), fr_from_abi(*tau), start, ctx->stream))) return st;
   if ((st = srs_finish(s.get()))) return st;
+  s->g1_prefix = n_points;  // multiples of the generator
   if (out_points && (st = plk_srs_points(s.get(), 0, n_points, out_points))) return st;
   *out = s.release();
   return PLK_OK;

@@ -106,6 +106,31 @@ struct DevBuf {
   }
 };
 
+// Stream-ordered scratch freed on the same stream when the scope ends.
+struct AsyncBuf {
+  void* ptr = nullptr;
+  hipStream_t s = nullptr;
+  AsyncBuf() = default;
+  AsyncBuf(const AsyncBuf&) = delete;
+  AsyncBuf& operator=(const AsyncBuf&) = delete;
+  int alloc(size_t bytes, hipStream_t st) {
+    s = st;
+    if (hipMallocAsync(&ptr, bytes > 32 ? bytes : 32, st) != hipSuccess) {
+      ptr = nullptr;
+      return PLK_E_OOM;
+    }
+    return PLK_OK;
+  }
+  ~AsyncBuf() {
+    if (ptr) (void)hipFreeAsync(ptr, s);
+  }
+  Fr* fr() const { return static_cast<Fr*>(ptr); }
+  template <class T>
+  T* as() const {
+    return static_cast<T*>(ptr);
+  }
+};
+
 struct NttPass {
   uint32_t lp, lr, lt;  // log2 of: sub-transform length so far, radix, columns per block
 };
@@ -150,6 +175,12 @@ struct MsmStats {
 };
 }
 
+namespace plk {
+struct KzgTable {
+  DevBuf points, inf;  // G1Affine / uint8, 2n entries
+};
+}
+
 struct plk_srs {
   plk_ctx* ctx = nullptr;
   size_t n = 0;              // number of SRS points
@@ -171,6 +202,12 @@ struct plk_srs {
   // plk_srs_setup leave both false, so plk_srs_verify runs every step on their SRS
   bool points_checked = false, subgroup_checked = false;
   double verify_fold_ms = 0.0, verify_pairing_ms = 0.0;  // the most recent plk_srs_verify
+  // the leading points known to lie in G1 without a test (plk_srs_setup computes multiples of the
+  // generator) or by the prefix test of plk_kzg_open_domain; subgroup_checked covers every point
+  size_t g1_prefix = 0;
+  // plk_kzg_open_domain's tables, one per log_n (kzg.hip): the 2n-point transform of the reversed,
+  // identity-padded SRS prefix in affine form, 2n * 97 bytes each, built on first use
+  std::map<uint32_t, plk::KzgTable> kzg_tables;
   plk::DevBuf staging;       // host-scalar entry points stage through it
   // the workspace of the SRS's own entry points (plk_msm / plk_commit*: one thread at a
   // time); concurrent provers sharing this SRS each bring their own (plk_prover)
@@ -202,6 +239,9 @@ struct plk_ctx {
   // the most recent check or diagnosis on this context (measurement only)
   plk::CheckWs* check_ws = nullptr;
   float check_ms = 0.f;
+  // HIP-event times of the most recent plk_kzg_open_domain (kzg.hip; measurement only): the
+  // transforms, the pointwise multiplication, the table build (0 when the table was cached)
+  float kzg_transform_ms = 0.f, kzg_mul_ms = 0.f, kzg_table_ms = 0.f;
 };
 
 namespace plk {
@@ -363,6 +403,21 @@ int srs_generate(plk_srs* s, const Fr& tau_mont, uint64_t start, hipStream_t str
 // scalars canonical Montgomery. Waits for the stream.
 int g1_mul_dev(plk_ctx* ctx, const G1Affine* pts, const uint8_t* inf, const Fr* scal, uint64_t n,
                G1Affine* out, uint8_t* out_inf, hipStream_t s);
+// The transform over G1 of 2^log_n device-resident XYZZ points (g1_ntt.hip), in place, natural
+// order in and out: dir = +1 forward, -1 inverse (with n^-1 unless scale is false). kXyzz: the
+// twiddle multiplication inside the butterfly on XYZZ points, stream-ordered, exact for any points
+// of the curve. kGlv: affine between the levels, the multiplications through g1_mul_dev (waits for
+// the stream at every level); the points must lie in G1.
+enum class G1NttForm { kXyzz, kGlv };
+int g1_ntt_run(plk_ctx* ctx, G1xyzz* points, uint32_t log_n, int dir, hipStream_t stream, bool scale = true,
+               G1NttForm form = G1NttForm::kXyzz);
+// out[i] = pts[first + i] (rev: pts[first - i]) for i < m as XYZZ, the identity for m <= i < n
+int g1_xyzz_load(const G1Affine* pts, const uint8_t* inf, uint64_t first, bool rev, uint64_t m, uint64_t n,
+                 G1xyzz* out, hipStream_t stream);
+// The canonical / on-curve pass and the subgroup kernel over the first n points of an SRS not yet
+// known to be in G1 there (srs_io.hip): *any with the smallest offending index; the SRS's flags
+// (or g1_prefix, for n < srs->n) record a clean pass.
+int srs_ensure_g1_prefix(plk_srs* srs, uint64_t n, bool* any, uint64_t* idx);
 // d_out[i] = s^i, i < n (Montgomery), stream-ordered
 int fr_powers_dev(const Fr& s_mont, uint64_t n, Fr* d_out, hipStream_t s);
 }  // namespace plk

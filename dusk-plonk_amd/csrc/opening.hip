@@ -27,24 +27,6 @@ using namespace plk;
 
 namespace {
 
-// Stream-ordered scratch freed on the same stream when the scope ends.
-struct AsyncBuf {
-  void* ptr = nullptr;
-  hipStream_t s = nullptr;
-  int alloc(size_t bytes, hipStream_t st) {
-    s = st;
-    if (hipMallocAsync(&ptr, std::max<size_t>(bytes, 32), st) != hipSuccess) {
-      ptr = nullptr;
-      return PLK_E_OOM;
-    }
-    return PLK_OK;
-  }
-  ~AsyncBuf() {
-    if (ptr) (void)hipFreeAsync(ptr, s);
-  }
-  Fr* fr() const { return static_cast<Fr*>(ptr); }
-};
-
 // W = (sum_i v^i p_i) / (X - point) on `s`; out receives max(lens) - 1 coefficients.
 int aggregate_witness(const Fr* const* polys, const size_t* lens, size_t count, const Fr& point,
                       const Fr& v, Fr* out, uint64_t max_len, hipStream_t s) {

@@ -327,6 +327,35 @@ int srs_ensure_g1(plk_srs* srs, bool* any, uint64_t* idx) {
 }
 
 }  // namespace
+
+// The same two passes over the first n points only (plk_kzg_open_domain, which reads no others).
+// A clean pass is recorded in g1_prefix; the flags of the whole SRS are srs_ensure_g1's.
+int srs_ensure_g1_prefix(plk_srs* srs, uint64_t n, bool* any, uint64_t* idx) {
+  *any = false;
+  if (srs->subgroup_checked || srs->g1_prefix >= n) return PLK_OK;
+  if (n > srs->n) return PLK_E_ARG;
+  hipStream_t s = srs->ctx->stream;
+  const G1Affine* pts = srs->points.as<G1Affine>();
+  const uint8_t* inf = srs->inf.as<uint8_t>();
+  BadWord bad;
+  uint8_t code;
+  int st;
+  if (!srs->points_checked) {
+    if ((st = bad.reset(s))) return st;
+    hipLaunchKernelGGL(k_srs_validate, dim3(cdiv(n, kBlock)), dim3(kBlock), 0, s, pts, inf, n, bad.dev());
+    PLK_HIP_TRY(hipGetLastError());
+    if ((st = bad.read(s, any, idx, &code))) return st;
+    if (*any) return PLK_OK;
+  }
+  if ((st = bad.reset(s))) return st;
+  hipLaunchKernelGGL(k_srs_subgroup, dim3(cdiv(n, kBlock)), dim3(kBlock), 0, s, pts, inf, n, bad.dev());
+  PLK_HIP_TRY(hipGetLastError());
+  if ((st = bad.read(s, any, idx, &code))) return st;
+  if (*any) return PLK_OK;
+  srs->g1_prefix = n;
+  return PLK_OK;
+}
+
 }  // namespace plk
 
 extern "C" {

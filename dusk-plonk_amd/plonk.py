@@ -50,6 +50,11 @@ _SRS_UPDATE_SYMBOLS = (
 # the entry points of csrc/circuit_check.hip (bound only when the loaded library has them, as above)
 _CHECK_SYMBOLS = ("plk_composer_check", "plk_prover_diagnose", "plk_key_diagnose", "plk_check_last_ms")
 
+# the entry points of csrc/kzg.hip and csrc/g1_ntt.hip (bound only when the loaded library has
+# them, as above)
+_KZG_SYMBOLS = ("plk_kzg_open", "plk_kzg_open_domain", "plk_kzg_last_open_ms", "plk_kzg_fold",
+                "plk_debug_g1_ntt")
+
 # Symbols declared in include/plk.h (checked by tests/test_abi.py)
 ABI_SYMBOLS = (
     "plk_abi_version", "plk_status_str", "plk_build_info", "plk_device_count", "plk_ctx_create",
@@ -99,6 +104,8 @@ ABI_SYMBOLS = (
     *_SRS_UPDATE_SYMBOLS,
     # the circuit check and the prover's diagnosis (Plonk.check / Prover.diagnose in prover.py)
     *_CHECK_SYMBOLS,
+    # KZG openings (PlonkParams.open / open_domain, OpeningKey.fold_openings) and the G1 transform
+    *_KZG_SYMBOLS,
 )
 
 # per-item status of the ingest calls (include/plk.h PLK_INGEST_*)
@@ -219,9 +226,16 @@ def _lib():
             "plk_g2_from_bytes": (i32, [vp, i32, vp]),
             "plk_debug_glv_split": (i32, [vp, vp, sz, vp]),
             "plk_check_last_ms": (i32, [vp, C.POINTER(C.c_float)]),
+            "plk_kzg_open": (i32, [vp, vp, sz, vp, sz, vp, vp]),
+            "plk_kzg_open_domain": (i32, [vp, u32, vp, sz, vp, vp, C.POINTER(u64)]),
+            "plk_kzg_last_open_ms": (i32, [vp, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                           C.POINTER(C.c_float)]),
+            "plk_kzg_fold": (i32, [vp, vp, vp, vp, vp, vp, sz, vp, vp]),
+            "plk_debug_g1_ntt": (i32, [vp, vp, u32, i32, vp]),
         }
         for name, (res, args) in sig.items():
-            if name in _SRS_IO_SYMBOLS + _SRS_UPDATE_SYMBOLS + _CHECK_SYMBOLS and not hasattr(lib, name):
+            if (name in _SRS_IO_SYMBOLS + _SRS_UPDATE_SYMBOLS + _CHECK_SYMBOLS + _KZG_SYMBOLS
+                    and not hasattr(lib, name)):
                 continue  # a PLK_LIB build from before srs_io.hip still loads; a use fails loudly
             f = getattr(lib, name)
             f.restype, f.argtypes = res, args
@@ -695,6 +709,28 @@ def g2_from_bytes(blob, fmt: str = "compressed") -> np.ndarray:
     return out
 
 
+def kzg_last_open_ms(ctx: "Context | None" = None):
+    """(transform ms, multiplication ms, table-build ms) of the most recent
+    PlonkParams.open_domain on the context (HIP events; the table build is 0 when it was cached)."""
+    ctx = ctx or Context.default()
+    a, b, c = C.c_float(), C.c_float(), C.c_float()
+    _check(_lib().plk_kzg_last_open_ms(ctx.handle, C.byref(a), C.byref(b), C.byref(c)),
+           "plk_kzg_last_open_ms")
+    return a.value, b.value, c.value
+
+
+def debug_g1_ntt(points, k: int, direction: int, ctx: "Context | None" = None) -> np.ndarray:
+    """Test support (plk_debug_g1_ntt): the transform over G1 of uint64[2^k, 13] ABI points,
+    direction +1 / -1 (the inverse with n^-1), natural order, as uint64[2^k, 13]."""
+    ctx = ctx or Context.default()
+    pts = np.ascontiguousarray(np.asarray(points, dtype=np.uint64).reshape(-1, 13))
+    if pts.shape[0] != 1 << k:
+        raise ValueError("debug_g1_ntt: 2^k points")
+    out = np.zeros_like(pts)
+    _check(_lib().plk_debug_g1_ntt(ctx.handle, _ptr(pts), k, direction, _ptr(out)), "plk_debug_g1_ntt")
+    return out
+
+
 def _fr_limbs(s) -> np.ndarray:
     """A canonical int or uint64[4] Montgomery limbs -> uint64[4] Montgomery limbs (an int is NOT
     reduced: a value >= r reaches the library as it is and is refused there)."""
@@ -982,6 +1018,49 @@ class PlonkParams:
                                             _ptr(out), C.byref(n_out)), "compute_aggregate_witness")
         return Coefficients(out[: n_out.value])
 
+    def open(self, poly, points):
+        """Open one polynomial at arbitrary points (plk_kzg_open): (values uint64[m, 4], witnesses
+        uint64[m, 13]) with values[j] = poly(points[j]) and witnesses[j] the commitment to
+        (poly - values[j]) / (X - points[j]). PlonkError(PLK_E_DEGREE) when the polynomial is
+        longer than the SRS, PLK_E_ARG for a scalar >= r."""
+        vals = _as_fr_array(poly.values if isinstance(poly, Coefficients) else poly)
+        pts = np.ascontiguousarray(np.asarray(points, dtype=np.uint64).reshape(-1, 4))
+        m = pts.shape[0]
+        values = np.zeros((max(m, 1), 4), dtype=np.uint64)
+        wit = np.zeros((max(m, 1), 13), dtype=np.uint64)
+        _check(_lib().plk_kzg_open(self._h, _ptr(vals), vals.shape[0], _ptr(pts), m, _ptr(values),
+                                   _ptr(wit)), "plk_kzg_open")
+        return values[:m], wit[:m]
+
+    def open_domain(self, k: int, poly):
+        """Open one polynomial of at most 2^k coefficients at every point of the 2^k domain
+        (plk_kzg_open_domain, Feist-Khovratovich on the GPU): (PointsValue of the values,
+        witnesses uint64[2^k, 13]), entry i for Fft(k).generator^i. The first call per k builds
+        and caches a table of 2^(k+1) points in this SRS. PlonkError(PLK_E_ARG) with bad_index
+        when an SRS point is not in G1."""
+        vals = _as_fr_array(poly.values if isinstance(poly, Coefficients) else poly)
+        n = 1 << k if 1 <= k <= 20 else 1  # outside the range the library refuses before it writes
+        values = np.zeros((n, 4), dtype=np.uint64)
+        wit = np.zeros((n, 13), dtype=np.uint64)
+        idx = C.c_uint64(0xFFFFFFFFFFFFFFFF)
+        st = _lib().plk_kzg_open_domain(self._h, k, _ptr(vals), vals.shape[0], _ptr(values), _ptr(wit),
+                                        C.byref(idx))
+        if st == PLK_E_ARG and idx.value != 0xFFFFFFFFFFFFFFFF:
+            raise PlonkError(st, f"plk_kzg_open_domain: point {idx.value} is not a point of G1",
+                             bad_index=idx.value)
+        _check(st, "plk_kzg_open_domain")
+        return PointsValue(values), wit
+
+    def open_multiple(self, polys, point, challenge):
+        """The reference's aggregate opening (commitment_scheme.rs open_multiple): (values
+        uint64[t, 4] of every polynomial at `point`, the Commitment to
+        (sum_i challenge^i polys[i]) / (X - point)). Composed from compute_aggregate_witness and
+        commit; the values through open()."""
+        pt = _as_fr_array(point).reshape(1, 4)
+        values = np.stack([self.open(p, pt)[0][0] for p in polys])
+        w = self.compute_aggregate_witness(polys, point, challenge)
+        return values, self.commit(w)
+
     def compute_aggregate_witness_dev(self, ptrs_lens, point, challenge, d_out: int,
                                       stream: int = 0) -> int:
         """Device form (plk_aggregate_witness_dev): [(ptr, len)] -> d_out; returns its length."""
@@ -1118,6 +1197,38 @@ class OpeningKey:
         _check(_lib().plk_pairing_check_batch(ctx.handle, self._h, _ptr(a), a.shape[0], _ptr(ok)),
                "plk_pairing_check_batch")
         return ok.astype(bool)
+
+    def fold_openings(self, g, commitments, points, values, witnesses, weights=None,
+                      ctx: "Context | None" = None) -> np.ndarray:
+        """(C, W) as uint64[2, 13] for n openings (commitments uint64[n, 13], points and values
+        uint64[n, 4], witnesses uint64[n, 13]) of commitments on the base point g (uint64[13]):
+        C = sum rho_k (C_k - y_k g + z_k W_k), W = sum rho_k W_k (plk_kzg_fold). weights=None draws
+        128-bit weights inside the library (the sound form); explicit weights uint64[n, 4] are for
+        callers with their own Fiat-Shamir. All openings hold iff check((C, W)), up to 2^-128."""
+        ctx = ctx or Context.default()
+        gp = np.ascontiguousarray(np.asarray(g, dtype=np.uint64).reshape(13))
+        cm = np.ascontiguousarray(np.asarray(commitments, dtype=np.uint64).reshape(-1, 13))
+        n = cm.shape[0]
+        zs = np.ascontiguousarray(np.asarray(points, dtype=np.uint64).reshape(-1, 4))
+        ys = np.ascontiguousarray(np.asarray(values, dtype=np.uint64).reshape(-1, 4))
+        ws = np.ascontiguousarray(np.asarray(witnesses, dtype=np.uint64).reshape(-1, 13))
+        if not (zs.shape[0] == ys.shape[0] == ws.shape[0] == n):
+            raise ValueError("fold_openings: one point, value and witness per commitment")
+        wp = None
+        if weights is not None:
+            wt = np.ascontiguousarray(np.asarray(weights, dtype=np.uint64).reshape(-1, 4))
+            if wt.shape[0] != n:
+                raise ValueError("fold_openings: one weight per opening")
+            wp = _ptr(wt)
+        out = np.zeros((2, 13), dtype=np.uint64)
+        _check(_lib().plk_kzg_fold(ctx.handle, _ptr(gp), _ptr(cm), _ptr(zs), _ptr(ys), _ptr(ws), n, wp,
+                                   _ptr(out)), "plk_kzg_fold")
+        return out
+
+    def check_openings(self, g, commitments, points, values, witnesses, weights=None,
+                       ctx: "Context | None" = None) -> bool:
+        """Do all the openings hold? fold_openings, then check on the pair."""
+        return self.check(self.fold_openings(g, commitments, points, values, witnesses, weights, ctx))
 
     def last_pairing_ms(self) -> float:
         """HIP-event milliseconds of the pairing kernel of the most recent device check."""

@@ -763,7 +763,60 @@ int plk_srs_verify_update(plk_ctx* ctx, const plk_g1* prev_tau_g1, plk_srs* new_
 int plk_g2_to_bytes(const plk_g2* q, int format, uint8_t* out);
 int plk_g2_from_bytes(const uint8_t* in, int format, plk_g2* out);
 
+/* ---- KZG openings (csrc/kzg.hip, csrc/g1_ntt.hip) --------------------------------------------
+ * The scheme's other operations beside plk_commit (the reference's src/commitment_scheme.rs and
+ * docs/notes-KZG10.md: open, check, batch check). The witness of f at z is the commitment to
+ * (f(X) - f(z)) / (X - z); the opening (C, z, y, W) holds iff e(C - y g + z W, H) = e(W, [tau]H).
+ * Scalars are Montgomery Fr, canonical (a value >= r is PLK_E_ARG); host buffers; one call at a
+ * time per SRS. */
+/* Opens one polynomial at `count` arbitrary points: values[k] = f(points[k]), witnesses[k] the
+ * witness there. The polynomial is uploaded once; per point one evaluation and one Ruffini
+ * division on the device, the quotients committed 16 at a time through the SRS's batch MSM.
+ * PLK_E_DEGREE when the polynomial (trailing zeros ignored) has more coefficients than the SRS
+ * points, as plk_commit. len <= 1 gives the value f_0 (or 0) and the identity. */
+int plk_kzg_open(plk_srs* srs, const plk_fr* coeffs, size_t len, const plk_fr* points, size_t count,
+                 plk_fr* values, plk_g1* witnesses);
+/* Opens one polynomial of len <= n = 2^log_n coefficients at all n points of the domain, entry i
+ * for omega^i (omega = plk_domain_info's generator): values[i] = f(omega^i) and witnesses[i],
+ * the same points plk_kzg_open returns, from three transforms over G1 and 2n scalar
+ * multiplications (Feist-Khovratovich) instead of n divisions and n MSMs. 1 <= log_n <= 20,
+ * len > n is PLK_E_ARG, an SRS of fewer than n points PLK_E_DEGREE.
+ * The first call per (SRS, log_n) builds a table of 2n affine points, the transform of the
+ * reversed SRS prefix: 2n * 97 bytes of device memory (194 MiB at log_n = 20), kept in the SRS
+ * and freed with it. Before the first build the first n SRS points pass the canonical / on-curve
+ * and subgroup kernels unless the SRS is known to be in G1 (plk_srs_setup, plk_srs_load_bytes
+ * with check_subgroup, plk_srs_update, a passed plk_srs_verify): the multiplication's scalar
+ * split is valid on G1 only. A bad point is PLK_E_ARG with *bad_index (nullable) the smallest
+ * offending index, as plk_srs_load_bytes reports; otherwise *bad_index = UINT64_MAX. */
+int plk_kzg_open_domain(plk_srs* srs, uint32_t log_n, const plk_fr* coeffs, size_t len, plk_fr* values,
+                        plk_g1* witnesses, uint64_t* bad_index);
+/* HIP-event milliseconds of the most recent plk_kzg_open_domain on this context (measurement
+ * only): the transforms (Fr and G1), the pointwise multiplication (with its batch inversion),
+ * and the table build (0 when the table was cached). Each pointer nullable. */
+int plk_kzg_last_open_ms(plk_ctx* ctx, float* transform_ms, float* mul_ms, float* table_ms);
+/* Folds `count` openings (commitments[k], points[k], values[k], witnesses[k]) of commitments
+ * made on the base point g (g1[0] of the SRS) into one pair with weights rho_k:
+ *   C = sum rho_k (C_k - y_k g + z_k W_k),   W = sum rho_k W_k.
+ * All the openings hold iff e(C, H) = e(W, [tau]H) (plk_pairing_check), up to 2^-128 for random
+ * weights. One plk_msm_points_ranges batch: 2 count + 1 points for C (sum rho_k y_k accumulated
+ * on the scalar side) and count for W. weights = NULL: rho_0 = 1 and 128-bit rho_k from a merlin
+ * transcript over the count, every z_k and y_k and 32 bytes of OS entropy (the verifier fold's
+ * derivation; the sound form). Explicit weights (count of them) serve callers with their own
+ * Fiat-Shamir; count = 1 with weight 1 gives (C - y g + z W, W), the opening's own pair, so
+ * per-opening verdicts come from plk_pairing_check_batch over such pairs.
+ * PLK_E_ARG: count = 0, a non-canonical scalar, a finite point off the curve or not canonical,
+ * an infinity word other than 0 / 1. Subgroup membership is the caller's (plk_verifier_fold's
+ * contract). One call at a time per context. */
+int plk_kzg_fold(plk_ctx* ctx, const plk_g1* g, const plk_g1* commitments, const plk_fr* points,
+                 const plk_fr* values, const plk_g1* witnesses, size_t count, const plk_fr* weights,
+                 plk_kzg_pair* out);
+
 /* ---- test support ---------------------------------------------------------------- */
+/* The transform over G1 of csrc/g1_ntt.hip through the product's own launcher: out_i = sum_j
+ * omega^(dir ij) in_j over the 2^log_n domain (log_n <= 20), natural order, dir = +1 / -1, the
+ * inverse with n^-1. Points follow plk_msm_points' rules (PLK_E_ARG otherwise); they need not
+ * lie in G1. */
+int plk_debug_g1_ntt(plk_ctx* ctx, const plk_g1* in, uint32_t log_n, int dir, plk_g1* out);
 /* The scalar split of csrc/g1_mul.hip: out[4 i .. 4 i + 3] = a_lo, a_hi, b_lo, b_hi of scalar i
  * (canonical Montgomery; otherwise PLK_E_ARG) with a = z - (k mod z), b = floor(k / z) + 1.
  * ctx = NULL: the host mirror; otherwise the device function the kernel calls. */
