@@ -10,6 +10,7 @@ from .plonk import (  # noqa: F401
     debug_pairing, device_count, g1_decompress, g1_subgroup_check, g1_sum, ingest_last_ms, msm_points, msm_points_ranges, msm_sharded,
     SrsVerdict, debug_glv_split, g1_mul, g1_mul_last_ms, g2_from_bytes, g2_to_bytes,
     check_last_ms, debug_f12_op, debug_miller, debug_g1_ntt, kzg_last_open_ms,
+    debug_g1_ntt_batch, debug_g1_colsum,
 )
 from .prover import CircuitReport, GateFailure  # noqa: F401,E402
 
@@ -21,5 +22,5 @@ __all__ = [
     "msm_points_ranges", "msm_sharded",
     "SrsVerdict", "debug_glv_split", "g1_mul", "g1_mul_last_ms", "g2_from_bytes", "g2_to_bytes",
     "CircuitReport", "GateFailure", "check_last_ms", "debug_f12_op",
-    "debug_miller", "debug_g1_ntt", "kzg_last_open_ms",
+    "debug_miller", "debug_g1_ntt", "kzg_last_open_ms", "debug_g1_ntt_batch", "debug_g1_colsum",
 ]

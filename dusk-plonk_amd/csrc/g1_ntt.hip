@@ -42,12 +42,14 @@ namespace {
 
 constexpr uint32_t kMaxLog = 27;  // plk_domain_get's range
 
-// One level over blocks of len = 2^log_len: butterfly t of n / 2. tw_fwd: omega^e, e < n (R domain,
-// Montgomery), so omega_len^j = tw_fwd[j n / len] and omega_len^-j = tw_fwd[(n - j n / len) mod n].
-__global__ void __launch_bounds__(128) k_g1_dif(G1xyzz* __restrict__ a, uint64_t n, uint32_t log_len,
+// One level over blocks of len = 2^log_len: butterfly t of total / 2, total = batch n points (the
+// transforms lie one after the other, and len divides n, so a block never straddles two of them).
+// tw_fwd: omega^e, e < n (R domain, Montgomery), so omega_len^j = tw_fwd[j n / len] and
+// omega_len^-j = tw_fwd[(n - j n / len) mod n].
+__global__ void __launch_bounds__(128) k_g1_dif(G1xyzz* __restrict__ a, uint64_t total, uint64_t n, uint32_t log_len,
                                                 const Fr* __restrict__ tw_fwd, int inverse) {
   const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= n / 2) return;
+  if (t >= total / 2) return;
   const uint64_t half = 1ull << (log_len - 1), j = t & (half - 1);
   const uint64_t i0 = ((t >> (log_len - 1)) << log_len) + j, i1 = i0 + half;
   G1xyzz u, v;
@@ -62,12 +64,14 @@ __global__ void __launch_bounds__(128) k_g1_dif(G1xyzz* __restrict__ a, uint64_t
   st_xyzz(&a[i1], d);
 }
 
-// a[i] <-> a[bitrev(i)], the lane of the smaller index swaps
-__global__ void __launch_bounds__(256) k_g1_bitrev(G1xyzz* __restrict__ a, uint64_t n, uint32_t log_n) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
+// a[i] <-> a[bitrev(i)] inside every transform of 2^log_n points, the lane of the smaller index swaps
+__global__ void __launch_bounds__(256) k_g1_bitrev(G1xyzz* __restrict__ a, uint64_t total, uint32_t log_n) {
+  const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= total) return;
+  const uint64_t i = g & ((1ull << log_n) - 1);
   const uint64_t r = __brevll(i) >> (64 - log_n);
   if (r <= i) return;
+  a += g - i;
   G1xyzz p, q;
   ld_xyzz(&a[i], p);
   ld_xyzz(&a[r], q);
@@ -108,11 +112,11 @@ __global__ void __launch_bounds__(256) k_g1_load(const G1Affine* __restrict__ pt
 // beside it, block b's differences j = 1 .. half - 1 at b (half - 1) + j - 1. One batch inversion
 // brings d to affine form, k_g1_mul (g1_mul.hip: the 128-step chain on the endomorphism split)
 // multiplies, and k_g1_scatter puts the products back. The split is valid on G1 only.
-__global__ void __launch_bounds__(128) k_g1_bfly_split(G1xyzz* __restrict__ a, uint64_t n, uint32_t log_len,
-                                                       const Fr* __restrict__ tw_fwd, int inverse,
+__global__ void __launch_bounds__(128) k_g1_bfly_split(G1xyzz* __restrict__ a, uint64_t total, uint64_t n,
+                                                       uint32_t log_len, const Fr* __restrict__ tw_fwd, int inverse,
                                                        G1xyzz* __restrict__ d, Fr* __restrict__ tw) {
   const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= n / 2) return;
+  if (t >= total / 2) return;
   const uint64_t half = 1ull << (log_len - 1), j = t & (half - 1), blk = t >> (log_len - 1);
   const uint64_t i0 = (blk << log_len) + j, i1 = i0 + half;
   G1xyzz u, v;
@@ -134,10 +138,10 @@ __global__ void __launch_bounds__(128) k_g1_bfly_split(G1xyzz* __restrict__ a, u
 
 // a[i1] = the product of butterfly t's difference (j != 0), from the compact affine array
 __global__ void __launch_bounds__(256) k_g1_scatter(const G1Affine* __restrict__ prod,
-                                                    const uint8_t* __restrict__ prod_inf, uint64_t n,
+                                                    const uint8_t* __restrict__ prod_inf, uint64_t total,
                                                     uint32_t log_len, G1xyzz* __restrict__ a) {
   const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= n / 2) return;
+  if (t >= total / 2) return;
   const uint64_t half = 1ull << (log_len - 1), j = t & (half - 1), blk = t >> (log_len - 1);
   if (j == 0) return;
   const uint64_t k = blk * (half - 1) + j - 1;
@@ -160,9 +164,11 @@ __global__ void __launch_bounds__(256) k_g1_load_abi(const plk_g1* __restrict__ 
   st_xyzz(&out[i], p.inf || !p.ok ? xyzz_infinity() : xyzz_from_affine(G1Affine{p.x, p.y}));
 }
 
-// The glv form of g1_ntt_run on points of G1. g1_mul_dev waits for the stream at every level.
-int run_glv(plk_ctx* ctx, plk_domain* dom, G1xyzz* points, int dir, hipStream_t s, bool scale) {
-  const uint64_t n = dom->n, cap = n;  // the levels need n / 2 slots, the scale pass n
+// The glv form of g1_ntt_run_batch on points of G1: the differences of all `batch` transforms go
+// through one batch inversion and one multiplication per level. g1_mul_dev waits for the stream at
+// every level.
+int run_glv(plk_ctx* ctx, plk_domain* dom, G1xyzz* points, uint64_t batch, int dir, hipStream_t s, bool scale) {
+  const uint64_t n = dom->n, total = batch * n, cap = total;  // the levels need total / 2 slots, the scale pass total
   const uint32_t log_n = dom->log_n;
   AsyncBuf d, tw, aff, inf, pref, prod, prod_inf;
   int st;
@@ -174,28 +180,28 @@ int run_glv(plk_ctx* ctx, plk_domain* dom, G1xyzz* points, int dir, hipStream_t 
   if ((st = prod.alloc(cap * sizeof(G1Affine), s))) return st;
   if ((st = prod_inf.alloc(cap, s))) return st;
   for (uint32_t ll = log_n; ll >= 1; --ll) {
-    hipLaunchKernelGGL(k_g1_bfly_split, dim3(cdiv(n / 2, 128)), dim3(128), 0, s, points, n, ll,
+    hipLaunchKernelGGL(k_g1_bfly_split, dim3(cdiv(total / 2, 128)), dim3(128), 0, s, points, total, n, ll,
                        (const Fr*)dom->tw_fwd.as<Fr>(), dir < 0 ? 1 : 0, d.as<G1xyzz>(), tw.fr());
     PLK_HIP_TRY(hipGetLastError());
-    const uint64_t m = n / 2 - (n >> ll);  // the butterflies with j != 0
+    const uint64_t m = total / 2 - (total >> ll);  // the butterflies with j != 0
     if (m == 0) continue;
     if ((st = srs_batch_affine(d.as<G1xyzz>(), m, pref.as<Fp>(), aff.as<G1Affine>(), inf.as<uint8_t>(), s))) return st;
     if ((st = g1_mul_dev(ctx, aff.as<G1Affine>(), inf.as<uint8_t>(), tw.fr(), m, prod.as<G1Affine>(),
                          prod_inf.as<uint8_t>(), s)))
       return st;
-    hipLaunchKernelGGL(k_g1_scatter, dim3(cdiv(n / 2, 256)), dim3(256), 0, s, (const G1Affine*)prod.as<G1Affine>(),
-                       (const uint8_t*)prod_inf.as<uint8_t>(), n, ll, points);
+    hipLaunchKernelGGL(k_g1_scatter, dim3(cdiv(total / 2, 256)), dim3(256), 0, s, (const G1Affine*)prod.as<G1Affine>(),
+                       (const uint8_t*)prod_inf.as<uint8_t>(), total, ll, points);
     PLK_HIP_TRY(hipGetLastError());
   }
-  hipLaunchKernelGGL(k_g1_bitrev, dim3(cdiv(n, 256)), dim3(256), 0, s, points, n, log_n);
+  hipLaunchKernelGGL(k_g1_bitrev, dim3(cdiv(total, 256)), dim3(256), 0, s, points, total, log_n);
   PLK_HIP_TRY(hipGetLastError());
   if (dir < 0 && scale) {
-    if ((st = srs_batch_affine(points, n, pref.as<Fp>(), aff.as<G1Affine>(), inf.as<uint8_t>(), s))) return st;
-    if ((st = pk_fill(tw.fr(), dom->n_inv, n, s))) return st;
-    if ((st = g1_mul_dev(ctx, aff.as<G1Affine>(), inf.as<uint8_t>(), tw.fr(), n, prod.as<G1Affine>(),
+    if ((st = srs_batch_affine(points, total, pref.as<Fp>(), aff.as<G1Affine>(), inf.as<uint8_t>(), s))) return st;
+    if ((st = pk_fill(tw.fr(), dom->n_inv, total, s))) return st;
+    if ((st = g1_mul_dev(ctx, aff.as<G1Affine>(), inf.as<uint8_t>(), tw.fr(), total, prod.as<G1Affine>(),
                          prod_inf.as<uint8_t>(), s)))
       return st;
-    if ((st = g1_xyzz_load(prod.as<G1Affine>(), prod_inf.as<uint8_t>(), 0, false, n, n, points, s))) return st;
+    if ((st = g1_xyzz_load(prod.as<G1Affine>(), prod_inf.as<uint8_t>(), 0, false, total, total, points, s))) return st;
   }
   return PLK_OK;
 }
@@ -216,19 +222,30 @@ G1NttForm chosen_form(G1NttForm form) {
 // for any points of the curve; kGlv asks for points of G1 (the caller's check).
 int g1_ntt_run(plk_ctx* ctx, G1xyzz* points, uint32_t log_n, int dir, hipStream_t stream, bool scale,
                G1NttForm form) {
+  return g1_ntt_run_batch(ctx, points, log_n, 1, dir, stream, scale, form);
+}
+
+// `batch` transforms of 2^log_n points each, one after the other in `points`: every level, the bit
+// reversal and the scale are one launch over all batch 2^log_n points, so the batch is as deep as
+// one transform. The kernels index a butterfly's block across the whole array and take only the
+// twiddle from the transform's own size; batch = 1 is the single transform, launch for launch.
+int g1_ntt_run_batch(plk_ctx* ctx, G1xyzz* points, uint32_t log_n, uint64_t batch, int dir, hipStream_t stream,
+                     bool scale, G1NttForm form) {
   if (!ctx || !points || log_n > kMaxLog || (dir != 1 && dir != -1)) return PLK_E_ARG;
+  if (batch == 0 || batch > (1ull << kMaxLog) >> log_n) return PLK_E_ARG;
   if (log_n == 0) return PLK_OK;
   plk_domain* dom = nullptr;
   int st;
   if ((st = plk_domain_get(ctx, log_n, &dom))) return st;
-  const uint64_t n = dom->n;
-  if (chosen_form(form) == G1NttForm::kGlv) return run_glv(ctx, dom, points, dir, stream, scale);
+  const uint64_t n = dom->n, total = batch * n;
+  if (chosen_form(form) == G1NttForm::kGlv) return run_glv(ctx, dom, points, batch, dir, stream, scale);
   for (uint32_t ll = log_n; ll >= 1; --ll)
-    hipLaunchKernelGGL(k_g1_dif, dim3(cdiv(n / 2, 128)), dim3(128), 0, stream, points, n, ll,
+    hipLaunchKernelGGL(k_g1_dif, dim3(cdiv(total / 2, 128)), dim3(128), 0, stream, points, total, n, ll,
                        (const Fr*)dom->tw_fwd.as<Fr>(), dir < 0 ? 1 : 0);
-  hipLaunchKernelGGL(k_g1_bitrev, dim3(cdiv(n, 256)), dim3(256), 0, stream, points, n, log_n);
+  hipLaunchKernelGGL(k_g1_bitrev, dim3(cdiv(total, 256)), dim3(256), 0, stream, points, total, log_n);
   if (dir < 0 && scale)
-    hipLaunchKernelGGL(k_g1_scale, dim3(cdiv(n, 128)), dim3(128), 0, stream, points, n, fe_from_mont(dom->n_inv));
+    hipLaunchKernelGGL(k_g1_scale, dim3(cdiv(total, 128)), dim3(128), 0, stream, points, total,
+                       fe_from_mont(dom->n_inv));
   PLK_HIP_TRY(hipGetLastError());
   return PLK_OK;
 }
@@ -248,9 +265,14 @@ using namespace plk;
 extern "C" {
 
 int plk_debug_g1_ntt(plk_ctx* ctx, const plk_g1* in, uint32_t log_n, int dir, plk_g1* out) {
+  return plk_debug_g1_ntt_batch(ctx, in, log_n, 1, dir, out);
+}
+
+int plk_debug_g1_ntt_batch(plk_ctx* ctx, const plk_g1* in, uint32_t log_n, size_t batch, int dir, plk_g1* out) {
   PLK_API_BEGIN
   if (!ctx || !in || !out || log_n > 20 || (dir != 1 && dir != -1)) return PLK_E_ARG;
-  const uint64_t n = 1ull << log_n;
+  if (batch == 0 || batch > ((size_t)1 << 20) >> log_n) return PLK_E_ARG;
+  const uint64_t n = (uint64_t)batch << log_n;  // all the points
   DeviceGuard g(ctx->device);
   hipStream_t s = ctx->stream;
   void* buf = nullptr;  // the ABI points, the XYZZ points, the affine results, prefix products, flags
@@ -268,7 +290,7 @@ int plk_debug_g1_ntt(plk_ctx* ctx, const plk_g1* in, uint32_t log_n, int dir, pl
   if (e == hipSuccess) {
     hipLaunchKernelGGL(k_g1_load_abi, dim3(cdiv(n, 256)), dim3(256), 0, s, (const plk_g1*)base, n, pts,
                        reinterpret_cast<uint32_t*>(base + o_b));
-    st = g1_ntt_run(ctx, pts, log_n, dir, s, true);
+    st = g1_ntt_run_batch(ctx, pts, log_n, batch, dir, s, true);
     if (st == PLK_OK)
       st = srs_batch_affine(pts, n, reinterpret_cast<Fp*>(base + o_p), reinterpret_cast<G1Affine*>(base + o_a),
                             base + o_f, s);

@@ -206,7 +206,9 @@ struct plk_srs {
   // generator) or by the prefix test of plk_kzg_open_domain; subgroup_checked covers every point
   size_t g1_prefix = 0;
   // plk_kzg_open_domain's tables, one per log_n (kzg.hip): the 2n-point transform of the reversed,
-  // identity-padded SRS prefix in affine form, 2n * 97 bytes each, built on first use
+  // identity-padded SRS prefix in affine form, 2n * 97 bytes each, built on first use. The tables
+  // of plk_kzg_open_cosets sit beside them under log_n | log_l << 8: 2^log_l transforms of 2r
+  // points, residue a's at [a 2r, (a + 1) 2r); log_l = 0 is open_domain's own table
   std::map<uint32_t, plk::KzgTable> kzg_tables;
   plk::DevBuf staging;       // host-scalar entry points stage through it
   // the workspace of the SRS's own entry points (plk_msm / plk_commit*: one thread at a
@@ -239,7 +241,7 @@ struct plk_ctx {
   // the most recent check or diagnosis on this context (measurement only)
   plk::CheckWs* check_ws = nullptr;
   float check_ms = 0.f;
-  // HIP-event times of the most recent plk_kzg_open_domain (kzg.hip; measurement only): the
+  // HIP-event times of the most recent plk_kzg_open_domain / _cosets (kzg.hip; measurement only): the
   // transforms, the pointwise multiplication, the table build (0 when the table was cached)
   float kzg_transform_ms = 0.f, kzg_mul_ms = 0.f, kzg_table_ms = 0.f;
 };
@@ -411,6 +413,19 @@ int g1_mul_dev(plk_ctx* ctx, const G1Affine* pts, const uint8_t* inf, const Fr* 
 enum class G1NttForm { kXyzz, kGlv };
 int g1_ntt_run(plk_ctx* ctx, G1xyzz* points, uint32_t log_n, int dir, hipStream_t stream, bool scale = true,
                G1NttForm form = G1NttForm::kXyzz);
+// `batch` independent transforms of 2^log_n points each, one after the other in `points`: one launch
+// per level over all of them, so the batch is one multiplication chain per level deep, not `batch`.
+// batch = 1 is g1_ntt_run.
+int g1_ntt_run_batch(plk_ctx* ctx, G1xyzz* points, uint32_t log_n, uint64_t batch, int dir, hipStream_t stream,
+                     bool scale = true, G1NttForm form = G1NttForm::kXyzz);
+// out[t] = sum_{a < rows} pts[a * cols + t] as XYZZ, by the complete group law (g1_colsum.hip);
+// stream-ordered with its own stream-ordered scratch
+int g1_colsum_dev(const G1Affine* pts, const uint8_t* inf, uint64_t rows, uint64_t cols, G1xyzz* out,
+                  hipStream_t stream);
+// out[i] = sum_{k < count} rho[k] zinv[k]^i c[k * l + i], i < l (g1_colsum.hip): the fold of coset
+// interpolants (kzg.hip); Montgomery scalars on the device, stream-ordered
+int fr_interp_reduce_dev(const Fr* c, const Fr* rho, const Fr* zinv, uint64_t count, uint64_t l, Fr* out,
+                         hipStream_t stream);
 // out[i] = pts[first + i] (rev: pts[first - i]) for i < m as XYZZ, the identity for m <= i < n
 int g1_xyzz_load(const G1Affine* pts, const uint8_t* inf, uint64_t first, bool rev, uint64_t m, uint64_t n,
                  G1xyzz* out, hipStream_t stream);

@@ -53,7 +53,8 @@ _CHECK_SYMBOLS = ("plk_composer_check", "plk_prover_diagnose", "plk_key_diagnose
 # the entry points of csrc/kzg.hip and csrc/g1_ntt.hip (bound only when the loaded library has
 # them, as above)
 _KZG_SYMBOLS = ("plk_kzg_open", "plk_kzg_open_domain", "plk_kzg_last_open_ms", "plk_kzg_fold",
-                "plk_debug_g1_ntt")
+                "plk_debug_g1_ntt", "plk_kzg_open_cosets", "plk_kzg_fold_cosets",
+                "plk_debug_g1_ntt_batch", "plk_debug_g1_colsum")
 
 # Symbols declared in include/plk.h (checked by tests/test_abi.py)
 ABI_SYMBOLS = (
@@ -232,6 +233,10 @@ def _lib():
                                            C.POINTER(C.c_float)]),
             "plk_kzg_fold": (i32, [vp, vp, vp, vp, vp, vp, sz, vp, vp]),
             "plk_debug_g1_ntt": (i32, [vp, vp, u32, i32, vp]),
+            "plk_kzg_open_cosets": (i32, [vp, u32, u32, vp, sz, vp, vp, C.POINTER(u64)]),
+            "plk_kzg_fold_cosets": (i32, [vp, u32, vp, vp, vp, vp, sz, vp, vp]),
+            "plk_debug_g1_ntt_batch": (i32, [vp, vp, u32, sz, i32, vp]),
+            "plk_debug_g1_colsum": (i32, [vp, vp, sz, sz, vp]),
         }
         for name, (res, args) in sig.items():
             if (name in _SRS_IO_SYMBOLS + _SRS_UPDATE_SYMBOLS + _CHECK_SYMBOLS + _KZG_SYMBOLS
@@ -468,6 +473,16 @@ class Coefficients:
 
 class PointsValue(Coefficients):
     """poly_commit::PointsValue<Fr> — evaluations over a domain."""
+
+    def cosets(self, log_l: int) -> np.ndarray:
+        """The n = 2^k values in the domain's natural order as the cosets of l = 2^log_l points
+        PlonkParams.open_cosets opens: a view uint64[r, l, 4], r = n / l, whose row j holds
+        f(omega^(j + r i)), i < l, the values on omega^j <omega^r> in the order
+        OpeningKey.fold_cosets takes them."""
+        n, l = self.values.shape[0], 1 << log_l
+        if n == 0 or n & (n - 1) or l > n:
+            raise ValueError("cosets: 2^k values and l <= 2^k")
+        return self.values.reshape(l, n // l, 4).transpose(1, 0, 2)
 
 
 # ------------------------------------------------------------------------------- Fft
@@ -728,6 +743,31 @@ def debug_g1_ntt(points, k: int, direction: int, ctx: "Context | None" = None) -
         raise ValueError("debug_g1_ntt: 2^k points")
     out = np.zeros_like(pts)
     _check(_lib().plk_debug_g1_ntt(ctx.handle, _ptr(pts), k, direction, _ptr(out)), "plk_debug_g1_ntt")
+    return out
+
+
+def debug_g1_ntt_batch(points, k: int, batch: int, direction: int, ctx: "Context | None" = None) -> np.ndarray:
+    """Test support (plk_debug_g1_ntt_batch): `batch` transforms of 2^k points each, one after the
+    other in uint64[batch * 2^k, 13], through the batched launcher; otherwise as debug_g1_ntt."""
+    ctx = ctx or Context.default()
+    pts = np.ascontiguousarray(np.asarray(points, dtype=np.uint64).reshape(-1, 13))
+    if pts.shape[0] != batch << k:
+        raise ValueError("debug_g1_ntt_batch: batch * 2^k points")
+    out = np.zeros_like(pts)
+    _check(_lib().plk_debug_g1_ntt_batch(ctx.handle, _ptr(pts), k, batch, direction, _ptr(out)),
+           "plk_debug_g1_ntt_batch")
+    return out
+
+
+def debug_g1_colsum(points, rows: int, cols: int, ctx: "Context | None" = None) -> np.ndarray:
+    """Test support (plk_debug_g1_colsum): out[t] = sum_a points[a * cols + t] over uint64[rows *
+    cols, 13] ABI points (any points of the curve), as uint64[cols, 13]."""
+    ctx = ctx or Context.default()
+    pts = np.ascontiguousarray(np.asarray(points, dtype=np.uint64).reshape(-1, 13))
+    if pts.shape[0] != rows * cols:
+        raise ValueError("debug_g1_colsum: rows * cols points")
+    out = np.zeros((cols, 13), dtype=np.uint64)
+    _check(_lib().plk_debug_g1_colsum(ctx.handle, _ptr(pts), rows, cols, _ptr(out)), "plk_debug_g1_colsum")
     return out
 
 
@@ -1051,6 +1091,39 @@ class PlonkParams:
         _check(st, "plk_kzg_open_domain")
         return PointsValue(values), wit
 
+    def open_cosets(self, k: int, log_l: int, poly):
+        """Open one polynomial of at most n = 2^k coefficients on every coset of l = 2^log_l points
+        of the 2^k domain (plk_kzg_open_cosets, the Feist-Khovratovich multiproofs on the GPU):
+        (PointsValue of the n values in the domain's natural order, witnesses uint64[r, 13]),
+        r = n / l. Witness j is the commitment to poly div (X^l - w^(l j)), one point for the l
+        values values.cosets(log_l)[j] on the coset w^j <w^r>, w = Fft(k).generator. log_l = 0
+        is open_domain. The first call per (k, log_l) builds and caches a table of 2^(k+1) points
+        in this SRS. Verify with OpeningKey.check_cosets on the key of tau^l.
+        PlonkError(PLK_E_ARG) with bad_index when an SRS point is not in G1."""
+        vals = _as_fr_array(poly.values if isinstance(poly, Coefficients) else poly)
+        ok = 1 <= k <= 20 and 0 <= log_l <= k  # outside the range the library refuses before it writes
+        n = 1 << k if ok else 1
+        values = np.zeros((n, 4), dtype=np.uint64)
+        wit = np.zeros((n >> log_l if ok else 1, 13), dtype=np.uint64)
+        idx = C.c_uint64(0xFFFFFFFFFFFFFFFF)
+        st = _lib().plk_kzg_open_cosets(self._h, k, log_l if log_l >= 0 else 0xFFFFFFFF, _ptr(vals),
+                                        vals.shape[0], _ptr(values), _ptr(wit), C.byref(idx))
+        if st == PLK_E_ARG and idx.value != 0xFFFFFFFFFFFFFFFF:
+            raise PlonkError(st, f"plk_kzg_open_cosets: point {idx.value} is not a point of G1",
+                             bad_index=idx.value)
+        _check(st, "plk_kzg_open_cosets")
+        return PointsValue(values), wit
+
+    def power_key_matches(self, key: "OpeningKey", log_l: int) -> bool:
+        """Is `key` the opening key of tau^l, l = 2^log_l, for this SRS's tau? e(g1[l], H) ==
+        e(g1[0], key.beta_h) through plk_pairing_check on the pair (g1[l], g1[0]): a key read
+        from a ceremony's G2 powers need not be taken on faith before OpeningKey.check_cosets
+        relies on it. The SRS must hold more than l points."""
+        l = 1 << log_l
+        if l >= self.n:
+            raise PlonkError(PLK_E_ARG, "power_key_matches: the SRS holds no point g1[2^log_l]")
+        return key.check(np.stack([self.points(l, 1)[0], self.points(0, 1)[0]]))
+
     def open_multiple(self, polys, point, challenge):
         """The reference's aggregate opening (commitment_scheme.rs open_multiple): (values
         uint64[t, 4] of every polynomial at `point`, the Commitment to
@@ -1229,6 +1302,47 @@ class OpeningKey:
                        ctx: "Context | None" = None) -> bool:
         """Do all the openings hold? fold_openings, then check on the pair."""
         return self.check(self.fold_openings(g, commitments, points, values, witnesses, weights, ctx))
+
+    def fold_cosets(self, pp: "PlonkParams", log_l: int, commitments, shifts, values, witnesses,
+                    weights=None) -> np.ndarray:
+        """(C, W) as uint64[2, 13] for n coset openings on the SRS pp (plk_kzg_fold_cosets):
+        opening k says that the polynomial committed in commitments[k] takes the l = 2^log_l
+        values[k] (uint64[n, l, 4], row k = f(z_k w^i), i < l, w the l-point domain's generator;
+        a row of PointsValue.cosets(log_l)) on the coset z_k <w>, z_k = shifts[k] any non-zero
+        scalar (for PlonkParams.open_cosets: Fft(k).generator^j for coset j), with the witness
+        witnesses[k]. One commitment (uint64[13]) may stand for all openings.
+        C = sum rho_k (C_k + z_k^l W_k) - sum_i P_i g1[i], W = sum rho_k W_k, the interpolants
+        reduced to the l scalars P_i on the GPU. All openings hold iff check((C, W)) on the key
+        of tau^l, up to 2^-128: self must be OpeningKey.setup(tau^l) or a ceremony's l-th G2
+        power (OpeningKey.load / from_bytes; PlonkParams.power_key_matches tells), NOT the key
+        of tau that check_openings wants. After an SRS update by s that key follows by
+        update(s^l) (plk_opening_key_update(key_l, s^l)). weights as fold_openings."""
+        l = 1 << log_l if 0 <= log_l <= 20 else 1  # outside the range the library refuses
+        zs = np.ascontiguousarray(np.asarray(shifts, dtype=np.uint64).reshape(-1, 4))
+        n = zs.shape[0]
+        cm = np.ascontiguousarray(np.asarray(commitments, dtype=np.uint64).reshape(-1, 13))
+        if cm.shape[0] == 1 and n > 1:
+            cm = np.ascontiguousarray(np.tile(cm, (n, 1)))
+        ys = np.ascontiguousarray(np.asarray(values, dtype=np.uint64).reshape(-1, 4))
+        ws = np.ascontiguousarray(np.asarray(witnesses, dtype=np.uint64).reshape(-1, 13))
+        if not (cm.shape[0] == ws.shape[0] == n and ys.shape[0] == n * l):
+            raise ValueError("fold_cosets: one shift, witness and row of 2^log_l values per opening")
+        wp = None
+        if weights is not None:
+            wt = np.ascontiguousarray(np.asarray(weights, dtype=np.uint64).reshape(-1, 4))
+            if wt.shape[0] != n:
+                raise ValueError("fold_cosets: one weight per opening")
+            wp = _ptr(wt)
+        out = np.zeros((2, 13), dtype=np.uint64)
+        _check(_lib().plk_kzg_fold_cosets(pp._h, log_l, _ptr(cm), _ptr(zs), _ptr(ys), _ptr(ws), n, wp,
+                                          _ptr(out)), "plk_kzg_fold_cosets")
+        return out
+
+    def check_cosets(self, pp: "PlonkParams", log_l: int, commitments, shifts, values, witnesses,
+                     weights=None) -> bool:
+        """Do all the coset openings hold? fold_cosets, then check on the pair; self is the key
+        of tau^l (see fold_cosets)."""
+        return self.check(self.fold_cosets(pp, log_l, commitments, shifts, values, witnesses, weights))
 
     def last_pairing_ms(self) -> float:
         """HIP-event milliseconds of the pairing kernel of the most recent device check."""

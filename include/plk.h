@@ -810,8 +810,50 @@ int plk_kzg_last_open_ms(plk_ctx* ctx, float* transform_ms, float* mul_ms, float
 int plk_kzg_fold(plk_ctx* ctx, const plk_g1* g, const plk_g1* commitments, const plk_fr* points,
                  const plk_fr* values, const plk_g1* witnesses, size_t count, const plk_fr* weights,
                  plk_kzg_pair* out);
+/* Opens one polynomial of len <= n = 2^log_n coefficients on every coset of l = 2^log_l points of
+ * the domain (a KZG multiproof per coset; the second half of Feist-Khovratovich). With r = n / l,
+ * coset j < r is omega^j <omega^r>, its vanishing polynomial X^l - omega^(l j), and witnesses[j]
+ * (r entries) the commitment to f(X) div (X^l - omega^(l j)). values holds the n entries
+ * f(omega^i) in the domain's natural order, as plk_kzg_open_domain returns them: the i-th value
+ * of coset j is entry j + r i. The same 2n scalar multiplications as plk_kzg_open_domain, then a
+ * column sum over the l residues and G1 transforms of 2r and r points instead of 2n and n.
+ * log_l = log_n gives the one witness O; log_l = 0 gives plk_kzg_open_domain's output byte for
+ * byte and shares its table. Arguments, refusals, the table per (SRS, log_n, log_l) of 2n affine
+ * points, the G1 test of the SRS prefix and *bad_index as plk_kzg_open_domain; log_l > log_n is
+ * PLK_E_ARG. plk_kzg_last_open_ms reports the most recent open of either kind. */
+int plk_kzg_open_cosets(plk_srs* srs, uint32_t log_n, uint32_t log_l, const plk_fr* coeffs, size_t len,
+                        plk_fr* values, plk_g1* witnesses, uint64_t* bad_index);
+/* Folds `count` coset openings (commitments[k], shifts[k], the l = 2^log_l values of row k,
+ * witnesses[k]) into one pair. Row k holds v_(k,i) = f(z_k w^i), i < l, w the generator of the
+ * l-point domain and z_k = shifts[k] any non-zero scalar. With c_k = IDFT_l(row k), the
+ * interpolant of opening k is I_k = sum_i c_(k,i) z_k^-i X^i, and the opening holds iff
+ * e(C_k - [I_k(tau)]G + z_k^l W_k, H) = e(W_k, [tau^l]H). The fold with weights rho_k is
+ *   C = sum rho_k (C_k + z_k^l W_k) - sum_{i<l} P_i g1[i],   W = sum rho_k W_k,
+ *   P_i = sum_k rho_k z_k^-i c_(k,i),
+ * to be checked with plk_pairing_check against the opening key of tau^l (plk_opening_key_setup
+ * (tau^l), or a ceremony's l-th G2 power through plk_opening_key_load), not the key of tau. The
+ * inverse transforms of the rows and the reduction to P run on the device, C and W are one
+ * plk_msm_points_ranges batch with the first l SRS points as variable-base points. weights = NULL:
+ * rho_0 = 1 and 128-bit rho_k from a merlin transcript (label "plk-kzg-fold-cosets") over count,
+ * log_l, every shift, every value and 32 bytes of OS entropy. At log_l = 0 with explicit weights
+ * the pair is plk_kzg_fold's byte for byte. PLK_E_ARG: count = 0, log_l > 20, a zero shift, a
+ * non-canonical scalar, a bad point by plk_kzg_fold's rules, an SRS of fewer than l points. One
+ * call at a time per SRS. */
+int plk_kzg_fold_cosets(plk_srs* srs, uint32_t log_l, const plk_g1* commitments, const plk_fr* shifts,
+                        const plk_fr* values, const plk_g1* witnesses, size_t count,
+                        const plk_fr* weights, plk_kzg_pair* out);
 
 /* ---- test support ---------------------------------------------------------------- */
+/* `batch` independent transforms of 2^log_n points each, laid out one after the other, through
+ * the batched launcher of csrc/g1_ntt.hip (one launch per level over all of them); otherwise as
+ * plk_debug_g1_ntt. batch >= 1, batch * 2^log_n <= 2^20. */
+int plk_debug_g1_ntt_batch(plk_ctx* ctx, const plk_g1* in, uint32_t log_n, size_t batch, int dir,
+                           plk_g1* out);
+/* The column sum over G1 of csrc/g1_colsum.hip through the product's own launcher: out[t] =
+ * sum_{a < rows} points[a * cols + t], t < cols, as affine ABI points. Points follow
+ * plk_msm_points' rules (PLK_E_ARG otherwise); they need not lie in G1. rows, cols >= 1,
+ * rows * cols <= 2^21. */
+int plk_debug_g1_colsum(plk_ctx* ctx, const plk_g1* points, size_t rows, size_t cols, plk_g1* out);
 /* The transform over G1 of csrc/g1_ntt.hip through the product's own launcher: out_i = sum_j
  * omega^(dir ij) in_j over the 2^log_n domain (log_n <= 20), natural order, dir = +1 / -1, the
  * inverse with n^-1. Points follow plk_msm_points' rules (PLK_E_ARG otherwise); they need not
