@@ -47,13 +47,7 @@ PLK_HD GateVerdict gate_check(const Fr* q, const Fr& a, const Fr& b, const Fr& c
   GateVerdict v;
   v.mask = 0;
   {  // q_arith (q_m a b + q_l a + q_r b + q_o c + q_4 d + q_c) + PI
-    Fr t = fe_mul(fe_mul(q[SEL_QM], a), b);
-    t = fe_add(t, fe_mul(q[SEL_QL], a));
-    t = fe_add(t, fe_mul(q[SEL_QR], b));
-    t = fe_add(t, fe_mul(q[SEL_QO], c));
-    t = fe_add(t, fe_mul(q[SEL_Q4], d));
-    t = fe_add(t, q[SEL_QC]);
-    v.residual = fe_add(fe_mul(q[SEL_QARITH], t), pi);
+    v.residual = fe_add(widget_arith(q, a, b, c, d), pi);
     if (!fe_is_zero(v.residual)) v.mask |= PLK_GATE_ARITH;
   }
   if (!fe_is_zero(q[SEL_QRANGE])) {

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstring>
 #include <vector>
 
 #include "g1r.hpp"
@@ -290,7 +291,7 @@ int run_rows(plk_ctx* ctx, K kern, const RowArg (&in)[NA], uint32_t* out, size_t
 // ---- plk_debug_prover_stage: the prover's pk_* launchers on caller arrays ----------------
 enum : int {
   kStPermNumDen = 0, kStScan, kStQuotient, kStPiSparse, kStPiCoef, kStCosetCombine, kStEval,
-  kStLinComb, kStScalePowers, kStRuffini, kStCount
+  kStLinComb, kStScalePowers, kStRuffini, kStQuotientTop, kStCosetCombineTop, kStCount
 };
 
 struct StageCall {
@@ -484,8 +485,67 @@ int run_stage(plk_ctx* ctx, const StageCall& c) {
       if ((st = pk_ruffini(in(0), len, sc(0), dout.as<Fr>(), tmp.as<Fr>(), scan.as<Fr>(), s))) return st;
       return finish(dout.as<Fr>(), len - 1);
     }
+    case kStCosetCombineTop: {
+      // in: 4 x n coefficients (the inverse block transforms); sc: the 16 matrix entries (R', row
+      // major), Q[7], p_0 .. p_4 (quotient_top.hpp quotient_patch) -> 4n + 8 coefficients of t
+      if (c.n_in != 1 || c.n_par != 0 || c.n_sc != 16 + kTop + kQBlocksTop + 1 || c.len[0] % kQBlocksTop)
+        return PLK_E_ARG;
+      const uint64_t n = c.len[0] / kQBlocksTop;
+      if (n == 0) return PLK_OK;
+      if (n <= (uint64_t)kTop || c.out_cap < 4 * n + 8) return PLK_E_ARG;
+      CombineMat mat{};
+      for (int k = 0; k < 16; ++k) mat.m[k] = sc(k);
+      Fr q[kTop], p[kQBlocksTop + 1];
+      for (int j = 0; j < kTop; ++j) q[j] = sc(16 + j);
+      for (int l = 0; l <= kQBlocksTop; ++l) p[l] = sc(16 + kTop + l);
+      QuotientPatch patch;
+      quotient_patch(q, p, patch);
+      if ((st = dout.alloc((4 * n + 8) * sizeof(Fr)))) return st;
+      if ((st = pk_coset_combine_top(in(0), n, mat, patch, dout.as<Fr>(), s))) return st;
+      return finish(dout.as<Fr>(), 4 * n + 8);
+    }
     default: return PLK_E_ARG;
   }
+}
+
+// Stage kStQuotientTop, host code only (no context): quotient_top (quotient_top.hpp) on the
+// caller's top coefficients. in: wires (4 x 7), z (7), selectors (11 x 7, SEL_* order), sigmas
+// (4 x 7), L1 (7), each row seven coefficients in ascending order; sc: alpha beta gamma range_sep
+// logic_sep fixed_sep var_sep, omega, then the public-input values; par: log2 n, the has_* flags,
+// then one gate index per public input -> Q[7] = t[4n .. 4n + 6]
+int run_quotient_top(const StageCall& c) {
+  const size_t want[5] = {4 * kTop, kTop, SEL_COUNTQ * kTop, 4 * kTop, kTop};
+  if (c.n_in != 5 || c.n_sc < 8 || c.n_par != 2 + (c.n_sc - 8) || c.out_cap < (size_t)kTop)
+    return PLK_E_ARG;
+  for (int k = 0; k < 5; ++k)
+    if (c.len[k] != want[k]) return PLK_E_ARG;
+  if (c.par[0] < 4 || c.par[0] > 27 || c.par[1] > 15) return PLK_E_ARG;
+  const uint64_t n = 1ull << c.par[0];
+  const size_t npi = c.n_sc - 8;
+  QuotientTopIn ti;
+  Fr* rows[5] = {&ti.wire[0][0], ti.z, &ti.sel[0][0], &ti.sigma[0][0], ti.l1};
+  for (int k = 0; k < 5; ++k) std::memcpy(rows[k], c.in[k], want[k] * sizeof(Fr));
+  Fr ch[CH_COUNT] = {};
+  ch[CH_ALPHA] = fr_from_abi(c.sc[0]), ch[CH_BETA] = fr_from_abi(c.sc[1]);
+  ch[CH_GAMMA] = fr_from_abi(c.sc[2]), ch[CH_RANGE] = fr_from_abi(c.sc[3]);
+  ch[CH_LOGIC] = fr_from_abi(c.sc[4]), ch[CH_FIXED] = fr_from_abi(c.sc[5]);
+  ch[CH_VAR] = fr_from_abi(c.sc[6]);
+  const Fr omega = fr_from_abi(c.sc[7]);
+  if (fe_is_zero(omega)) return PLK_E_ARG;
+  Fr nf = fe_zero<FrCfg>();
+  nf.v[0] = (uint32_t)n;
+  const Fr n_inv = fe_inv(fe_to_mont(nf));
+  std::vector<Fr> pi(npi), wi(npi);
+  for (size_t i = 0; i < npi; ++i) {
+    if (c.par[2 + i] >= n) return PLK_E_ARG;
+    pi[i] = fr_from_abi(c.sc[8 + i]);
+    wi[i] = fe_pow_u64(omega, c.par[2 + i]);
+  }
+  const Top pit = top_public_inputs(pi.data(), wi.data(), npi, n_inv, n);
+  Fr q[kTop];
+  quotient_top(ti, pit, n, omega, fe_inv(omega), ch, (unsigned)c.par[1], q);
+  std::memcpy(c.out, q, sizeof q);
+  return PLK_OK;
 }
 
 }  // namespace
@@ -562,24 +622,36 @@ extern "C" int plk_debug_block_eval(plk_key* key, const uint64_t* coef, size_t l
   using plk::last_hip_error;
   try {
     if (!key) return PLK_E_ARG;
-    if (blocks_out) *blocks_out = key->qb;
+    // the cosets m < 5 (6 for n = 8), whatever number of them the prover's round 3 uses: a coset
+    // table of this call's own, made as the key's is (prover.hip)
+    const int blocks = key->n >= 16 ? plk::kQBlocks : plk::kQBlocksSmall;
+    if (blocks_out) *blocks_out = blocks;
     if (!out) return PLK_OK;
-    const uint64_t n = key->n, total = (uint64_t)key->qb * n;
+    const uint64_t n = key->n, total = (uint64_t)blocks * n;
     if (!coef || len == 0 || len > n + 8 || out_cap < total) return PLK_E_ARG;
     plk::DeviceGuard g(key->ctx->device);
     hipStream_t s = key->ctx->stream;
-    plk::DevBuf din, dout;
+    plk::DevBuf din, dout, table;
     int st;
-    if ((st = din.alloc(len * sizeof(plk::Fr))) || (st = dout.alloc(total * sizeof(plk::Fr))))
+    if ((st = din.alloc(len * sizeof(plk::Fr))) || (st = dout.alloc(total * sizeof(plk::Fr))) ||
+        (st = table.alloc(blocks * (n + 8) * sizeof(plk::Fr))))
       return st;
     PLK_HIP_TRY(hipMemcpyAsync(din.ptr, coef, len * sizeof(plk::Fr), hipMemcpyHostToDevice, s));
+    plk::Fr w8n, sm = key->dom->g;
+    plk::fr_root_of_unity(key->k + 3, w8n);
+    for (int mb = 0; mb < blocks; ++mb) {
+      if ((st = plk::ntt_power_table(table.as<plk::Fr>() + mb * (n + 8), sm, plk::fe_one<plk::FrCfg>(),
+                                     n + 8, true, s)))
+        return st;
+      sm = plk::fe_mul(sm, w8n);
+    }
     plk::NttBatch b;
     b.in_stride = 0;
     b.out_stride = n;
-    b.pre = key->coset_s.as<plk::Fr>();
+    b.pre = table.as<plk::Fr>();
     b.pre_stride = n + 8;
     if ((st = plk::ntt_run_batch(key->dom, din.as<plk::Fr>(), dout.as<plk::Fr>(), len, 1, 1,
-                                 nullptr, s, (uint32_t)key->qb, b)))
+                                 nullptr, s, (uint32_t)blocks, b)))
       return st;
     PLK_HIP_TRY(hipMemcpyAsync(out, dout.ptr, total * sizeof(plk::Fr), hipMemcpyDeviceToHost, s));
     PLK_HIP_TRY(plk::stream_wait(s));
@@ -595,15 +667,52 @@ extern "C" int plk_debug_prover_stage(plk_ctx* ctx, int stage, const uint64_t* c
                                       size_t n_scalars, const uint64_t* params, size_t n_params,
                                       uint64_t* out, size_t out_cap) {
   try {
-    if (!ctx || stage < 0 || stage >= plk::kStCount) return PLK_E_ARG;
+    if (stage < 0 || stage >= plk::kStCount) return PLK_E_ARG;
     if ((n_in && (!in || !in_len)) || (n_scalars && !scalars) || (n_params && !params) ||
         (out_cap && !out) || n_in > 32)
       return PLK_E_ARG;
     for (size_t k = 0; k < n_in; ++k)
       if (in_len[k] > ((size_t)1 << 28) || (in_len[k] && !in[k])) return PLK_E_ARG;
     const plk::StageCall c{stage, in, in_len, n_in, scalars, n_scalars, params, n_params, out, out_cap};
+    if (stage == plk::kStQuotientTop) return plk::run_quotient_top(c);  // host only: ctx unused
+    if (!ctx) return PLK_E_ARG;
     plk::DeviceGuard g(ctx->device);
     return plk::run_stage(ctx, c);
+  } catch (...) {
+    return PLK_E_DEVICE;
+  }
+}
+
+// The polynomials of the prover's last round 3 (test support): out = alpha beta gamma range_sep
+// logic_sep fixed_sep var_sep | the 11 selectors' n coefficients (SEL_* order) | the 4 sigmas' |
+// the 4 blinded wires' n + 2 | z's n + 3 | t's 4n + 8 — 24n + 26 elements. PLK_E_ARG unless the
+// prover's last plk_prover_prove reached round 3 on a key with n >= 16.
+extern "C" int plk_debug_prover_round3(plk_prover* p, uint64_t* out, size_t out_cap) {
+  using plk::Fr;
+  using plk::last_hip_error;
+  try {
+    if (!p || !out || !p->have_round3 || p->key->qb != plk::kQBlocksTop) return PLK_E_ARG;
+    const plk_key* key = p->key;
+    const uint64_t n = key->n, S = n + 8;
+    if (out_cap < 24 * n + 26) return PLK_E_ARG;
+    plk::DeviceGuard g(key->ctx->device);
+    hipStream_t s = p->stream;
+    Fr* o = reinterpret_cast<Fr*>(out);
+    std::memcpy(o, p->last_ch, sizeof p->last_ch);
+    o += 7;
+    auto d2h = [&](const Fr* src, uint64_t count) {
+      const hipError_t e = hipMemcpyAsync(o, src, count * sizeof(Fr), hipMemcpyDeviceToHost, s);
+      o += count;
+      return e;
+    };
+    // q_coef rows are in the gate's selector order, which is SEL_* order
+    PLK_HIP_TRY(d2h(key->q_coef.as<Fr>(), 11 * n));
+    PLK_HIP_TRY(d2h(key->sigma_coef.as<Fr>(), 4 * n));
+    for (int c = 0; c < 4; ++c) PLK_HIP_TRY(d2h(p->wires_coef.as<Fr>() + c * S, n + 2));
+    PLK_HIP_TRY(d2h(p->z_coef.as<Fr>(), n + 3));
+    PLK_HIP_TRY(d2h(p->t_coef.as<Fr>(), 4 * n + 8));
+    PLK_HIP_TRY(plk::stream_wait(s));
+    return PLK_OK;
   } catch (...) {
     return PLK_E_DEVICE;
   }

@@ -149,14 +149,22 @@ PLK_HD Fr edwards_d() {
 // the coset representatives K1, K2, K3 of the wire columns b, c, d (permutation.rs:28-30)
 PLK_HD Fr perm_k(int i) { return fr_small(i == 1 ? 7u : i == 2 ? 13u : 17u); }
 
+// The widgets and the quotient numerator are templates on the scalar type T: Fr for a row's
+// values (k_quotient_ext, the verifier's linearisation, the circuit check) and Top
+// (quotient_top.hpp) for the top coefficients of the polynomials themselves (the prover's round
+// 3). Constants (kappa powers, edwards d, small integers) stay Fr; T supplies fe_add / fe_sub /
+// fe_mul / fe_sqr / fe_dbl among T and with an Fr.
+
 // f (f - 1)(f - 2)(f - 3): zero exactly on a quad
-PLK_HD Fr fr_delta(const Fr& f) {
+template <class T>
+PLK_HD T fr_delta(const T& f) {
   const Fr one = fe_one<FrCfg>();
-  const Fr f1 = fe_sub(f, one), f2 = fe_sub(f1, one), f3 = fe_sub(f2, one);
+  const T f1 = fe_sub(f, one), f2 = fe_sub(f1, one), f3 = fe_sub(f2, one);
   return fe_mul(fe_mul(f, f1), fe_mul(f2, f3));
 }
 
-PLK_HD Fr fe_quad(const Fr& x) { return fe_dbl(fe_dbl(x)); }
+template <class T>
+PLK_HD T fe_quad(const T& x) { return fe_dbl(fe_dbl(x)); }
 
 // A widget's terms are separated by the powers of kappa = sep^2
 struct SepPowers {
@@ -172,10 +180,23 @@ PLK_HD SepPowers sep_powers(const Fr& sep) {
 }
 
 // ---- the widgets: a gate's row (and the next row's), then the kappa powers ----------------------
+// Arithmetic: q_arith (q_m a b + q_l a + q_r b + q_o c + q_4 d + q_c), q in SEL_* order
+template <class T>
+PLK_HD T widget_arith(const T* q, const T& a, const T& b, const T& c, const T& d) {
+  T t = fe_mul(fe_mul(q[SEL_QM], a), b);
+  t = fe_add(t, fe_mul(q[SEL_QL], a));
+  t = fe_add(t, fe_mul(q[SEL_QR], b));
+  t = fe_add(t, fe_mul(q[SEL_QO], c));
+  t = fe_add(t, fe_mul(q[SEL_Q4], d));
+  t = fe_add(t, q[SEL_QC]);
+  return fe_mul(q[SEL_QARITH], t);
+}
+
 // Range: D(c - 4d) + D(b - 4c) k + D(a - 4b) k^2 + D(d_next - 4a) k^3
-PLK_HD Fr widget_range(const Fr& a, const Fr& b, const Fr& c, const Fr& d, const Fr& d_n,
-                       const Fr& k, const Fr& k2, const Fr& k3) {
-  Fr r = fr_delta(fe_sub(c, fe_quad(d)));
+template <class T>
+PLK_HD T widget_range(const T& a, const T& b, const T& c, const T& d, const T& d_n,
+                      const Fr& k, const Fr& k2, const Fr& k3) {
+  T r = fr_delta(fe_sub(c, fe_quad(d)));
   r = fe_add(r, fe_mul(fr_delta(fe_sub(b, fe_quad(c))), k));
   r = fe_add(r, fe_mul(fr_delta(fe_sub(a, fe_quad(b))), k2));
   return fe_add(r, fe_mul(fr_delta(fe_sub(d_n, fe_quad(a))), k3));
@@ -183,27 +204,29 @@ PLK_HD Fr widget_range(const Fr& a, const Fr& b, const Fr& c, const Fr& d, const
 
 // delta_xor_and: 3(a + b + c) - 2 f + q_c (9c - 3(a + b)) with
 // f = w (w (4w - 18(a + b) + 81) + 18(a^2 + b^2) - 81(a + b) + 83) = 6 (a AND b) for quads
-PLK_HD Fr logic_xor_and(const Fr& a, const Fr& b, const Fr& w, const Fr& c, const Fr& qc) {
-  const Fr ab = fe_add(a, b);
-  Fr f = fe_sub(fe_quad(w), fe_mul(fr_small(18), ab));
+template <class T>
+PLK_HD T logic_xor_and(const T& a, const T& b, const T& w, const T& c, const T& qc) {
+  const T ab = fe_add(a, b);
+  T f = fe_sub(fe_quad(w), fe_mul(fr_small(18), ab));
   f = fe_add(f, fr_small(81));
   f = fe_mul(w, f);
   f = fe_add(f, fe_mul(fr_small(18), fe_add(fe_sqr(a), fe_sqr(b))));
   f = fe_sub(f, fe_mul(fr_small(81), ab));
   f = fe_add(f, fr_small(83));
   f = fe_mul(w, f);
-  const Fr e = fe_sub(fe_mul(fr_small(3), fe_add(ab, c)), fe_dbl(f));
-  const Fr bb = fe_mul(qc, fe_sub(fe_mul(fr_small(9), c), fe_mul(fr_small(3), ab)));
+  const T e = fe_sub(fe_mul(fr_small(3), fe_add(ab, c)), fe_dbl(f));
+  const T bb = fe_mul(qc, fe_sub(fe_mul(fr_small(9), c), fe_mul(fr_small(3), ab)));
   return fe_add(bb, e);
 }
 
 // Logic (dusk-plonk logic gate; zksnarks, un-vendored): quads qa = a_next - 4a, qb = b_next - 4b,
 // qd = d_next - 4d, w = c:  D(qa) + D(qb) k + D(qd) k^2 + (w - qa qb) k^3 + xor_and k^4
-PLK_HD Fr widget_logic(const Fr& a, const Fr& a_n, const Fr& b, const Fr& b_n, const Fr& c,
-                       const Fr& d, const Fr& d_n, const Fr& q_c, const Fr& k, const Fr& k2,
-                       const Fr& k3, const Fr& k4) {
-  const Fr qa = fe_sub(a_n, fe_quad(a)), qb = fe_sub(b_n, fe_quad(b)), qd = fe_sub(d_n, fe_quad(d));
-  Fr r = fr_delta(qa);
+template <class T>
+PLK_HD T widget_logic(const T& a, const T& a_n, const T& b, const T& b_n, const T& c,
+                      const T& d, const T& d_n, const T& q_c, const Fr& k, const Fr& k2,
+                      const Fr& k3, const Fr& k4) {
+  const T qa = fe_sub(a_n, fe_quad(a)), qb = fe_sub(b_n, fe_quad(b)), qd = fe_sub(d_n, fe_quad(d));
+  T r = fr_delta(qa);
   r = fe_add(r, fe_mul(fr_delta(qb), k));
   r = fe_add(r, fe_mul(fr_delta(qd), k2));
   r = fe_add(r, fe_mul(fe_sub(c, fe_mul(qa, qb)), k3));
@@ -214,22 +237,23 @@ PLK_HD Fr widget_logic(const Fr& a, const Fr& a_n, const Fr& b, const Fr& b_n, c
 // curve_scalar, un-vendored): accumulators (a, b) = point, d = scalar accumulator,
 // c = xy_alpha, q_l / q_r / q_c = x_beta / y_beta / x_beta y_beta of the gate's multiple.
 //   bit = d' - 2d;  bit (bit - 1)(bit + 1) + (bit q_c - c) k + x-check k^2 + y-check k^3
-PLK_HD Fr widget_fixed_base(const Fr& ax, const Fr& ax_n, const Fr& ay, const Fr& ay_n,
-                            const Fr& xy_alpha, const Fr& acc, const Fr& acc_n,
-                            const Fr& x_beta, const Fr& y_beta, const Fr& xy_beta, const Fr& k,
-                            const Fr& k2, const Fr& k3, const Fr& d) {
+template <class T>
+PLK_HD T widget_fixed_base(const T& ax, const T& ax_n, const T& ay, const T& ay_n,
+                           const T& xy_alpha, const T& acc, const T& acc_n,
+                           const T& x_beta, const T& y_beta, const T& xy_beta, const Fr& k,
+                           const Fr& k2, const Fr& k3, const Fr& d) {
   const Fr one = fe_one<FrCfg>();
-  const Fr bit = fe_sub(acc_n, fe_dbl(acc));
-  const Fr bit_consistency = fe_mul(fe_mul(bit, fe_sub(bit, one)), fe_add(bit, one));
-  const Fr y_alpha = fe_add(fe_mul(fe_sqr(bit), fe_sub(y_beta, one)), one);
-  const Fr x_alpha = fe_mul(x_beta, bit);
-  const Fr xy_consistency = fe_mul(fe_sub(fe_mul(bit, xy_beta), xy_alpha), k);
-  const Fr prod = fe_mul(fe_mul(fe_mul(xy_alpha, ax), ay), d);
-  const Fr x_lhs = fe_add(ax_n, fe_mul(ax_n, prod));
-  const Fr x_rhs = fe_add(fe_mul(ax, y_alpha), fe_mul(ay, x_alpha));
-  const Fr y_lhs = fe_sub(ay_n, fe_mul(ay_n, prod));
-  const Fr y_rhs = fe_add(fe_mul(ay, y_alpha), fe_mul(ax, x_alpha));
-  Fr id = fe_add(bit_consistency, xy_consistency);
+  const T bit = fe_sub(acc_n, fe_dbl(acc));
+  const T bit_consistency = fe_mul(fe_mul(bit, fe_sub(bit, one)), fe_add(bit, one));
+  const T y_alpha = fe_add(fe_mul(fe_sqr(bit), fe_sub(y_beta, one)), one);
+  const T x_alpha = fe_mul(x_beta, bit);
+  const T xy_consistency = fe_mul(fe_sub(fe_mul(bit, xy_beta), xy_alpha), k);
+  const T prod = fe_mul(fe_mul(fe_mul(xy_alpha, ax), ay), d);
+  const T x_lhs = fe_add(ax_n, fe_mul(ax_n, prod));
+  const T x_rhs = fe_add(fe_mul(ax, y_alpha), fe_mul(ay, x_alpha));
+  const T y_lhs = fe_sub(ay_n, fe_mul(ay_n, prod));
+  const T y_rhs = fe_add(fe_mul(ay, y_alpha), fe_mul(ax, x_alpha));
+  T id = fe_add(bit_consistency, xy_consistency);
   id = fe_add(id, fe_mul(fe_sub(x_lhs, x_rhs), k2));
   id = fe_add(id, fe_mul(fe_sub(y_lhs, y_rhs), k3));
   return id;
@@ -239,16 +263,67 @@ PLK_HD Fr widget_fixed_base(const Fr& ax, const Fr& ax_n, const Fr& ay, const Fr
 // gate (x1, y1, x2, y2), next row (x3, y3, ., x1 y2):
 //   (x1 y2 - x1y2') + (x1y2' + y1 x2 - x3 (1 + d x1y2' y1 x2)) k
 //                   + (y1 y2 + x1 x2 - y3 (1 - d x1y2' y1 x2)) k^2
-PLK_HD Fr widget_var_base(const Fr& x1, const Fr& x3, const Fr& y1, const Fr& y3, const Fr& x2,
-                          const Fr& y2, const Fr& x1y2, const Fr& k, const Fr& k2, const Fr& d) {
-  const Fr xy_consistency = fe_sub(fe_mul(x1, y2), x1y2);
-  const Fr y1x2 = fe_mul(y1, x2);
-  const Fr y1y2 = fe_mul(y1, y2);
-  const Fr x1x2 = fe_mul(x1, x2);
-  const Fr dprod = fe_mul(fe_mul(d, x1y2), y1x2);
-  const Fr x3c = fe_sub(fe_add(x1y2, y1x2), fe_add(x3, fe_mul(x3, dprod)));
-  const Fr y3c = fe_sub(fe_add(y1y2, x1x2), fe_sub(y3, fe_mul(y3, dprod)));
+template <class T>
+PLK_HD T widget_var_base(const T& x1, const T& x3, const T& y1, const T& y3, const T& x2,
+                         const T& y2, const T& x1y2, const Fr& k, const Fr& k2, const Fr& d) {
+  const T xy_consistency = fe_sub(fe_mul(x1, y2), x1y2);
+  const T y1x2 = fe_mul(y1, x2);
+  const T y1y2 = fe_mul(y1, y2);
+  const T x1x2 = fe_mul(x1, x2);
+  const T dprod = fe_mul(fe_mul(d, x1y2), y1x2);
+  const T x3c = fe_sub(fe_add(x1y2, y1x2), fe_add(x3, fe_mul(x3, dprod)));
+  const T y3c = fe_sub(fe_add(y1y2, x1x2), fe_sub(y3, fe_mul(y3, dprod)));
   return fe_add(fe_add(xy_consistency, fe_mul(x3c, k)), fe_mul(y3c, k2));
+}
+
+// ---- the quotient numerator N = t Z_H (quotient_poly.rs:74-114,122-262) ------------------------
+// What k_quotient evaluates point by point in the redundant form, stated once on T: the row's
+// wires w[4] and the next row's wn[4], z and z_next, the 11 selectors q (SEL_* order), the four
+// sigmas, L1, PI and x (the point X itself). ch: alpha .. var separation are read (not z).
+// flags: has_range | 2 has_logic | 4 has_fixed | 8 has_var, the widgets the key carries.
+//   q_arith (...) + PI + sum_widgets sep q_w widget
+//   + alpha [ z prod_c (w_c + beta K_c X + gamma) - z_next prod_c (w_c + beta sigma_c + gamma) ]
+//   + alpha^2 (z - 1) L1
+template <class T>
+PLK_HD T quotient_numerator(const T* w, const T* wn, const T& z, const T& z_next, const T* q,
+                            const T* sigma, const T& l1, const T& pi, const T& x, const Fr* ch,
+                            const Fr& ed, unsigned flags) {
+  const T &a = w[0], &b = w[1], &c = w[2], &d = w[3], &an = wn[0], &bn = wn[1], &dn = wn[3];
+  const Fr &beta = ch[CH_BETA], &gamma = ch[CH_GAMMA], &alpha = ch[CH_ALPHA];
+  T t = fe_add(widget_arith(q, a, b, c, d), pi);
+  if (flags & 1u) {
+    const SepPowers k = sep_powers(ch[CH_RANGE]);
+    t = fe_add(t, fe_mul(fe_mul(widget_range(a, b, c, d, dn, k.k, k.k2, k.k3), q[SEL_QRANGE]),
+                         ch[CH_RANGE]));
+  }
+  if (flags & 2u) {
+    const SepPowers k = sep_powers(ch[CH_LOGIC]);
+    t = fe_add(t, fe_mul(fe_mul(widget_logic(a, an, b, bn, c, d, dn, q[SEL_QC], k.k, k.k2, k.k3,
+                                             k.k4), q[SEL_QLOGIC]), ch[CH_LOGIC]));
+  }
+  if (flags & 4u) {
+    const SepPowers k = sep_powers(ch[CH_FIXED]);
+    t = fe_add(t, fe_mul(fe_mul(widget_fixed_base(a, an, b, bn, c, d, dn, q[SEL_QL], q[SEL_QR],
+                                                  q[SEL_QC], k.k, k.k2, k.k3, ed), q[SEL_QFIXED]),
+                         ch[CH_FIXED]));
+  }
+  if (flags & 8u) {
+    const SepPowers k = sep_powers(ch[CH_VAR]);
+    t = fe_add(t, fe_mul(fe_mul(widget_var_base(a, an, b, bn, c, d, dn, k.k, k.k2, ed),
+                                q[SEL_QVAR]), ch[CH_VAR]));
+  }
+  const T bx = fe_mul(x, beta);
+  T id = fe_mul(fe_add(fe_add(a, bx), gamma), fe_add(fe_add(b, fe_mul(bx, perm_k(1))), gamma));
+  id = fe_mul(id, fe_add(fe_add(c, fe_mul(bx, perm_k(2))), gamma));
+  id = fe_mul(id, fe_add(fe_add(d, fe_mul(bx, perm_k(3))), gamma));
+  id = fe_mul(id, z);
+  T cp = fe_mul(fe_add(fe_add(a, fe_mul(sigma[0], beta)), gamma),
+                fe_add(fe_add(b, fe_mul(sigma[1], beta)), gamma));
+  cp = fe_mul(cp, fe_add(fe_add(c, fe_mul(sigma[2], beta)), gamma));
+  cp = fe_mul(cp, fe_add(fe_add(d, fe_mul(sigma[3], beta)), gamma));
+  cp = fe_mul(cp, z_next);
+  t = fe_add(t, fe_mul(fe_sub(id, cp), alpha));
+  return fe_add(t, fe_mul(fe_mul(fe_sub(z, fe_one<FrCfg>()), l1), fe_sqr(alpha)));
 }
 
 // ---- the linearisation polynomial r (linearization_poly.rs:22-134, proof.rs:459-527) ------------

@@ -406,6 +406,12 @@ Fr d2h_fr(const Fr* p, hipStream_t s) {
   return *pin.as<Fr>();
 }
 
+// quotient_numerator's widget flags of a key
+unsigned top_flags(const plk_key* key) {
+  return (key->has_range ? 1u : 0u) | (key->has_logic ? 2u : 0u) | (key->has_fixed ? 4u : 0u) |
+         (key->has_var ? 8u : 0u);
+}
+
 }  // namespace
 
 namespace plk {
@@ -914,6 +920,37 @@ int plk_key_compile(plk_srs* srs, const plk_composer* cs, const char* label, plk
       TRY(coset_fwd(tmp.as<Fr>(), key->l1q.as<Fr>(), n, key->coset_s));
       PLK_HIP_TRY(stream_wait(s));
     }
+    // 4b. the closed-form top of t (prover.hpp): the key's share of quotient_top's inputs
+    if (QB == kQBlocksTop) {
+      // coefficients n-7 .. n-1 of the 11 selectors and the 4 sigmas
+      std::vector<Fr> top(15 * kTop);
+      PLK_HIP_TRY(hipMemcpy2DAsync(top.data(), kTop * sizeof(Fr), qc + (n - kTop), n * sizeof(Fr),
+                                   kTop * sizeof(Fr), 11, hipMemcpyDeviceToHost, s));
+      PLK_HIP_TRY(hipMemcpy2DAsync(top.data() + 11 * kTop, kTop * sizeof(Fr), sc + (n - kTop),
+                                   n * sizeof(Fr), kTop * sizeof(Fr), 4, hipMemcpyDeviceToHost, s));
+      PLK_HIP_TRY(stream_wait(s));
+      for (int j = 0; j < SEL_COUNTQ; ++j)
+        for (int i = 0; i < kTop; ++i) key->top_in.sel[j][i] = top[sel_src[j] * kTop + i];
+      for (int c = 0; c < 4; ++c)
+        for (int i = 0; i < kTop; ++i) key->top_in.sigma[c][i] = top[(11 + c) * kTop + i];
+      for (int i = 0; i < kTop; ++i) key->top_in.l1[i] = key->dom->n_inv;  // idft(e_0)
+      // P(Y) = prod_{m<4} (Y - c_m)
+      const Fr one = fe_one<FrCfg>();
+      Fr* pl = key->top_p;
+      pl[0] = one;
+      for (int j = 0; j < QB; ++j) {
+        const Fr cj = fe_pow_u64(key->s_m[j], n);
+        pl[j + 1] = fe_zero<FrCfg>();
+        for (int l = j + 1; l >= 1; --l) pl[l] = fe_sub(pl[l - 1], fe_mul(pl[l], cj));
+        pl[0] = fe_neg(fe_mul(pl[0], cj));
+      }
+    }
+    // w^i and w^-i of the public-input rows (PI's top coefficients; proof_at_z's winv)
+    for (uint64_t i = 0; i < m; ++i)
+      if (cs->gates[i].code & kPiBit) {
+        key->pi_w.push_back(fe_pow_u64(key->dom->omega, i));
+        key->pi_winv.push_back(fe_pow_u64(key->dom->omega_inv, i));
+      }
     // 5. wire indices for the per-proof gather (prover.rs:114-119)
     std::vector<uint32_t> idx(4 * n, 0);
     for (uint64_t i = 0; i < m; ++i)
@@ -1072,6 +1109,7 @@ int plk_prover_prove(plk_prover* P, const plk_composer* cs, uint64_t seed, plk_p
   PLK_API_BEGIN
     if (!P) return PLK_E_ARG;
     P->have_witness = false;  // plk_prover_diagnose: a refused call leaves no witness to check
+    P->have_round3 = false;
     if (!cs || !proof) return PLK_E_ARG;
     plk_key* key = P->key;
     // the proving circuit must have the key's structure (prover.rs:114-119 gathers the
@@ -1099,12 +1137,15 @@ int plk_prover_prove(plk_prover* P, const plk_composer* cs, uint64_t seed, plk_p
     TRY(P->pi_coef.alloc(n * sizeof(Fr)));
     TRY(P->evq.alloc(6 * nq * sizeof(Fr)));
     TRY(P->quotq.alloc(nq * sizeof(Fr)));
-    TRY(P->t_coef.alloc(nq * sizeof(Fr)));
+    const bool top4 = QB == kQBlocksTop;  // four blocks and the closed-form top (prover.hpp)
+    const uint64_t t_cap = std::max<uint64_t>(nq, 4 * n + 8);  // t: at most 4n + 7 coefficients
+    TRY(P->t_coef.alloc(t_cap * sizeof(Fr)));
+    TRY(P->pin_top.alloc(5 * kTop * sizeof(Fr)));
     TRY(P->agg.alloc(5 * n * sizeof(Fr)));
     TRY(P->agg2.alloc(S * sizeof(Fr)));
     TRY(P->w_coef.alloc((5 * n + S) * sizeof(Fr)));
     TRY(P->tmp_a.alloc(5 * n * sizeof(Fr)));
-    TRY(P->eval_partial.alloc((size_t)kMaxEval * pk_eval_max_blocks(nq) * sizeof(Fr)));
+    TRY(P->eval_partial.alloc((size_t)kMaxEval * pk_eval_max_blocks(t_cap) * sizeof(Fr)));
     if (!P->eval_out.ptr) {
       TRY(P->eval_out.alloc(kMaxEval * sizeof(Fr),
                             hipHostMallocMapped | hipHostMallocCoherent | hipHostMallocPortable));
@@ -1164,6 +1205,11 @@ int plk_prover_prove(plk_prover* P, const plk_composer* cs, uint64_t seed, plk_p
       bb.b[c].r[1] = rng.fr();
     }
     TRY(pk_blind_batch(bb, n, s));
+    // the wires' coefficients n-5 .. n+1 for round 3's closed-form top: the copy is complete
+    // when the commits below have been read back
+    if (top4)
+      PLK_HIP_TRY(hipMemcpy2DAsync(P->pin_top.ptr, kTop * sizeof(Fr), wc + (n + 2 - kTop),
+                                   S * sizeof(Fr), kTop * sizeof(Fr), 4, hipMemcpyDeviceToHost, s));
     // The commits: from the Lagrange values [w(omega^i) | b_0 b_1] on the key's Lagrange-basis
     // SRS (the same group element as the commit of the blinded coefficients; a zero or sparse
     // column, the bench chain's fourth wire, then has next to no MSM entries), guarded: a wire
@@ -1230,6 +1276,9 @@ int plk_prover_prove(plk_prover* P, const plk_composer* cs, uint64_t seed, plk_p
       for (int i = 0; i < 3; ++i) b.r[i] = rng.fr();
       TRY(pk_blind(zc, n, b, s));
     }
+    if (top4)  // z's coefficients n-4 .. n+2, complete behind the read-back of z's commit
+      PLK_HIP_TRY(hipMemcpyAsync(P->pin_top.as<Fr>() + 4 * kTop, zc + (n + 3 - kTop),
+                                 kTop * sizeof(Fr), hipMemcpyDeviceToHost, s));
     plk_g1 zcom;
     TRY(prover_commit(P, {zc}, {n + 3}, &zcom, nullptr));
     tr.append_commitment("z", zcom);
@@ -1240,6 +1289,9 @@ int plk_prover_prove(plk_prover* P, const plk_composer* cs, uint64_t seed, plk_p
     const Fr logic_sep = tr.challenge_scalar("logic separation challenge");
     const Fr fixed_sep = tr.challenge_scalar("fixed base separation challenge");
     const Fr var_sep = tr.challenge_scalar("variable base separation challenge");
+    Fr ch[CH_COUNT] = {};
+    ch[CH_BETA] = beta, ch[CH_GAMMA] = gamma, ch[CH_ALPHA] = alpha;
+    ch[CH_RANGE] = range_sep, ch[CH_LOGIC] = logic_sep, ch[CH_FIXED] = fixed_sep, ch[CH_VAR] = var_sep;
     Fr* pil = P->pi_lag.as<Fr>();
     // pin_small: the PI values uploaded here (sized once: queued copies keep pointing into it)
     TRY(P->pin_small.alloc(std::max<size_t>(pis.size(), 1) * sizeof(Fr)));
@@ -1335,7 +1387,27 @@ int plk_prover_prove(plk_prover* P, const plk_composer* cs, uint64_t seed, plk_p
       b.post = key->icoset_q.as<Fr>();
       b.post_stride = n;
       TRY(ntt_run_batch(key->dom, P->quotq.as<Fr>(), P->quotq.as<Fr>(), n, -1, 1, nsc, s, QB, b));
-      TRY(pk_coset_combine(P->quotq.as<Fr>(), n, QB, key->comb, tc, s));
+      if (!top4) {
+        TRY(pk_coset_combine(P->quotq.as<Fr>(), n, QB, key->comb, tc, s));
+      } else {
+        // t[4n .. 4n + 6] on the host while the stream runs the transforms queued above
+        // (quotient_top.hpp), then the combine that also places them
+        QuotientTopIn ti = key->top_in;
+        std::memcpy(ti.wire, P->pin_top.ptr, 4 * kTop * sizeof(Fr));
+        std::memcpy(ti.z, P->pin_top.as<Fr>() + 4 * kTop, kTop * sizeof(Fr));
+        const Top pit = top_public_inputs(P->last_pi.data(), key->pi_w.data(), pis.size(),
+                                          key->dom->n_inv, n);
+        Fr q_top[kTop];
+        quotient_top(ti, pit, n, key->dom->omega, key->dom->omega_inv, ch, top_flags(key), q_top);
+        QuotientPatch patch;
+        quotient_patch(q_top, key->top_p, patch);
+        TRY(pk_coset_combine_top(P->quotq.as<Fr>(), n, key->comb, patch, tc, s));
+      }
+    }
+    {
+      const Fr lc[7] = {alpha, beta, gamma, range_sep, logic_sep, fixed_sep, var_sep};
+      std::memcpy(P->last_ch, lc, sizeof lc);
+      P->have_round3 = true;
     }
     // split into t_low, t_mid, t_high (n each) and t_4 = t[3n..] (prover.rs:252-265)
     plk_g1 tcom[4];
@@ -1345,7 +1417,9 @@ int plk_prover_prove(plk_prover* P, const plk_composer* cs, uint64_t seed, plk_p
     // fails for an unsatisfied circuit (its interpolant does not vanish there, prover.hpp)
     // where the reference's commit fails (t_4 past the trimmed SRS, prover.rs:262-265) —
     // including tiny circuits whose trimmed SRS covers all of t[3n..QB n)
-    TRY(prover_commit(P, {tc, tc + n, tc + 2 * n, tc + 3 * n}, {n, n, n, nq - 3 * n}, tcom,
+    // (n >= 16: t_coef holds exactly 4n + 8 coefficients, nothing is left to check here, and
+    // the self-check at zeta below refuses an unsatisfied circuit)
+    TRY(prover_commit(P, {tc, tc + n, tc + 2 * n, tc + 3 * n}, {n, n, n, t_cap - 3 * n}, tcom,
                       nullptr, n + 8));
     // its commit succeeded, so everything past the committed prefix is zero: t and t_4 end at
     // 3n + t4_len for the evaluation and the opening below
@@ -1416,9 +1490,7 @@ int plk_prover_prove(plk_prover* P, const plk_composer* cs, uint64_t seed, plk_p
     const Fr t_eval = evs[EV_R];
     // the scalars s_t of r(X) = arithmetic::linearize + range::linearize + ... + permutation,
     // those of the terms this key has, in the terms' order
-    Fr ch[CH_COUNT] = {};
-    ch[CH_BETA] = beta, ch[CH_GAMMA] = gamma, ch[CH_ALPHA] = alpha, ch[CH_Z] = zeta;
-    ch[CH_RANGE] = range_sep, ch[CH_LOGIC] = logic_sep, ch[CH_FIXED] = fixed_sep, ch[CH_VAR] = var_sep;
+    ch[CH_Z] = zeta;
     AtZ at;  // z^n and L1(z)
     (void)at_z(zeta, key->k, key->dom->n_inv, one, at);
     Fr lin[LIN_Z + 1];
@@ -1428,6 +1500,14 @@ int plk_prover_prove(plk_prover* P, const plk_composer* cs, uint64_t seed, plk_p
     Fr r_e = fe_zero<FrCfg>();  // r(z) = sum_t s_t p_t(z)
     for (size_t t = 0; t < rt.size(); ++t) r_e = fe_add(r_e, fe_mul(rs[t], evs[rt[t].ev]));
     evs[EV_R] = r_e;  // evs[0 .. EV_COUNT) are the proof's evaluations from here on
+    {  // The self-check at zeta (prover.hpp): the quotient value a verifier derives from these
+       // evaluations against t(zeta) from the prover's own coefficients. They differ exactly when
+       // t Z_H is not the numerator, an unsatisfied circuit (up to ~5n / |Fr| over zeta).
+      Fr zn_v, l1_v, t_v;
+      const bool ok = proof_at_z(evs, ch, zeta, key->k, key->dom->n_inv, P->last_pi.data(),
+                                 key->pi_winv.data(), (uint32_t)pis.size(), zn_v, l1_v, t_v);
+      if (ok && !fe_eq(t_v, t_eval)) return PLK_E_DEGREE;
+    }
 
     for (const Step& st : kScript)
       if (st.kind == STEP_EVAL) tr.append_scalar(st.label, evs[st.id]);

@@ -8,6 +8,7 @@
 
 #include "internal.hpp"
 #include "protocol.hpp"
+#include "quotient_top.hpp"
 
 namespace plk {
 
@@ -32,33 +33,53 @@ struct BlindBatch {
 };
 
 // The quotient domain (round 3). The reference evaluates the quotient over the coset g H_8n
-// (quotient_poly.rs:52-58,115). The numerator (z times four wire factors, degree <= 5n + 6) is
-// never interpolated: k_quotient evaluates t(x) = num(x) / Z_H(x) exactly at each point from
-// exact evaluations of the factors, and only t is interpolated. t has degree <= 4n + 6, so ANY
-// 4n + 7 or more distinct points off H give the same coefficients, commitments and proofs, bit
-// for bit. This backend uses kQBlocks = 5 cosets of the n-domain itself, s_m H_n with
-// s_m = g w_8n^m (m < 5): 5n >= 4n + 8 points for n >= 8, every point is point 8u + m of the
-// reference's own g H_8n, and every block transform is an n-point one (key->dom). Every
-// quotient-domain vector is laid out in blocks of n (block m = coset m, natural order in u):
-// evaluation point x(m, u) = s_m w_n^u, the next row (w_n x) is u + 1 in the same block, and
-// v_h(x) = x^n - 1 = c_m - 1 with c_m = s_m^n = g^n w_8^m is constant per block (five distinct
-// values, none equal to 1).
+// (quotient_poly.rs:52-58,115). The numerator N (z times four wire factors, degree <= 5n + 6) is
+// never interpolated: k_quotient evaluates t(x) = N(x) / Z_H(x) exactly at each point from
+// exact evaluations of the factors, and only t is interpolated. t is unique (degree <= 4n + 6),
+// so however its coefficients are found, commitments and proofs are the same bit for bit. The
+// points are cosets of the n-domain itself, s_m H_n with s_m = g w_8n^m: every point is point
+// 8u + m of the reference's own g H_8n, and every block transform is an n-point one (key->dom).
+// Every quotient-domain vector is laid out in blocks of n (block m = coset m, natural order in
+// u): evaluation point x(m, u) = s_m w_n^u, the next row (w_n x) is u + 1 in the same block, and
+// v_h(x) = x^n - 1 = c_m - 1 with c_m = s_m^n = g^n w_8^m is constant per block (distinct values,
+// none equal to 1).
 //
 // Inverse: the inverse block transform m gives r_m = t mod (X^n - c_m), r_m[k] = sum_l c_m^l
 // t_l[k] for the n-coefficient chunks t_l of t; the chunks come back through the inverse
 // Vandermonde matrix of the c_m (pk_coset_combine; the matrix is computed once per key).
 //
-// Unsatisfied circuits: num = q Z_H + rho with rho = num mod Z_H != 0, so the evaluated values
-// are q(x) + rho(x) / (c_m - 1) and the interpolant is q + rho(X) A(X^n), A the polynomial of
-// degree <= kQBlocks - 1 with A(c_m) = 1 / (c_m - 1). Its leading coefficient kappa is not
-// zero (else A(c)(c - 1) - 1, of degree <= kQBlocks - 1, would vanish at kQBlocks points and
-// hence at c = 1, where it is -1). q has degree <= 4n + 6, so the coefficients [4n + 8, 5n) of
-// the interpolant are kappa rho[8..n): the zero check of t_4 past its n + 8 committed points
-// (prover.hip) fails there (PLK_E_DEGREE) as it did on the 6n-point domain used before, by the
-// same argument. n = 8 (the smallest composer) leaves that range empty, so it takes
-// kQBlocksSmall = 6 blocks (the same cosets, m < 6) and the range [40, 48) = kappa rho.
-constexpr int kQBlocks = 5, kQBlocksSmall = 6, kQBlocksMax = 6;
-inline int q_blocks(uint64_t n) { return n >= 16 ? kQBlocks : kQBlocksSmall; }
+// n >= 16: kQBlocksTop = 4 blocks and the top seven coefficients in closed form. 4n points do
+// not determine the 4n + 7 coefficients of t, but the seven that do not fit are known without
+// any transform: t = N / (X^n - 1) with deg N <= 5n + 6 gives t[4n + j] = N[5n + j], j < 7, and
+// the top seven coefficients of a product depend only on the top seven coefficients of its
+// factors (quotient_top.hpp: the widget and permutation formulas of protocol.hpp on a
+// seven-term power series in 1 / X). The factors' top coefficients are seven field elements
+// each: cached per key for the selectors, the sigmas and L1, read back with the round-1 and
+// round-2 commits for the wires and z, computed from the public inputs for PI. With
+// Q(X) = sum_j t[4n + j] X^j, the four blocks give T_4 = t mod P(X^n), P(Y) = prod_{m<4}
+// (Y - c_m) = sum_l p_l Y^l, and t = T_4 + Q(X) P(X^n): the combine adds p_l Q[j] to
+// t[l n + j] (l < 4) and writes Q at 4n (pk_coset_combine_top). This is exact for every circuit.
+//
+// Unsatisfied circuits, n >= 16: N = q Z_H + rho with rho != 0, the four blocks leave no spare
+// coefficient to test, and the prover would hand out some polynomial t' of degree <= 4n + 6
+// that is not N / Z_H. So after round 4 the prover derives, from the evaluations it is about to
+// publish, the quotient value the verifier will derive (proof_at_z, protocol.hpp: N(zeta) /
+// Z_H(zeta)) and compares it with t'(zeta) from its own coefficients: unequal is PLK_E_DEGREE,
+// the status such a circuit always had. For a satisfied circuit the two are equal by
+// construction; for an unsatisfied one N - t' Z_H is a non-zero polynomial of degree <= 5n + 6
+// and zeta, drawn after t' is committed, is a root of it with probability about 5n / |Fr|.
+//
+// n = 8 (the smallest composer) keeps kQBlocksSmall = 6 blocks and the deterministic check:
+// the interpolant over B blocks is q + rho(X) A(X^n), A of degree <= B - 1 with
+// A(c_m) = 1 / (c_m - 1), whose leading coefficient kappa is not zero (else A(c)(c - 1) - 1, of
+// degree <= B - 1, would vanish at B points and hence at c = 1, where it is -1); q has degree
+// <= 4n + 6, so the coefficients [40, 48) are kappa rho and the zero check of t_4 past its
+// n + 8 committed points (prover.hip) fails there. kQBlocks = 5 is the smallest count that
+// determines t for n >= 16 without the closed form: the stage tests and plk_debug_block_eval
+// still run it.
+constexpr int kQBlocksTop = 4, kQBlocks = 5, kQBlocksSmall = 6, kQBlocksMax = 6;
+static_assert(kQBlocksTop == kTopBlocks, "quotient_top.hpp patches a four-block combine");
+inline int q_blocks(uint64_t n) { return n >= 16 ? kQBlocksTop : kQBlocksSmall; }
 // PI over the quotient domain from at most kPiSparse public inputs as rotated reads of the
 // key's L1 table (pk_pi_sparse): L_i(X) = L_0(w^-i X), so PI(s_m w^u) = sum_i pi_i
 // l1q[m][(u - i) mod n] — one product per point and public input, no pk_pi_coef, idft or coset
@@ -152,6 +173,11 @@ struct CombineMat {
 };
 int pk_coset_combine(const Fr* in, uint64_t n, int blocks, const CombineMat& mat, Fr* out,
                      hipStream_t s);
+// the same over kQBlocksTop blocks (mat: 4 x 4), then t = T_4 + Q(X) P(X^n) (prover.hpp top):
+// out[l n + j] += patch.v[l][j] for l < 4 and out[4n + j] = patch.v[4][j], j < 8 (R domain);
+// out holds 4n + 8 coefficients, n >= 8
+int pk_coset_combine_top(const Fr* in, uint64_t n, const CombineMat& mat,
+                         const QuotientPatch& patch, Fr* out, hipStream_t s);
 // out[j] = in[j] * c (packed Montgomery product), j < n
 int pk_scale_copy(const Fr* in, const Fr& c, Fr* out, uint64_t n, hipStream_t s);
 uint32_t pk_eval_max_blocks(uint64_t max_len);
@@ -236,6 +262,13 @@ struct plk_key {
   // public inputs in place of the compile-time value
   plk::DevBuf gate_recs, gate_consts;
   plk::Fr vh_inv[plk::kQBlocksMax];
+  // the closed-form top of t (prover.hpp top; qb == kQBlocksTop): the top seven coefficients of
+  // the selectors, the sigmas and L1 (wire and z rows are filled per proof), the coefficients
+  // p_l of prod_{m<4} (Y - c_m), and w^i / w^-i of every public-input row i (PI's top
+  // coefficients; the self-check at zeta)
+  plk::QuotientTopIn top_in;
+  plk::Fr top_p[plk::kQBlocksTop + 1];
+  std::vector<plk::Fr> pi_w, pi_winv;
   plk_g1 comms[15];         // q_m q_l q_r q_o q_c q_4 q_arith q_range q_logic q_fixed q_var s1..s4
   // the circuit the key was compiled from: plk_prove refuses a circuit whose structure hash
   // differs or whose witness vector does not cover the largest wire index (prover.rs:114-119
@@ -267,6 +300,13 @@ struct plk_prover {
   void* allgather_user = nullptr;
   // per-proof scratch
   plk::PinnedBuf pin_witness, pin_small;  // host staging of the witness upload / small readbacks
+  // the wires' coefficients n-5 .. n+1 (4 x 7) and z's n-4 .. n+2, copied back behind the
+  // round-1 and round-2 commits (quotient_top.hpp)
+  plk::PinnedBuf pin_top;
+  // plk_debug_prover_round3: the last proof's alpha, beta, gamma and separation challenges, set
+  // once its t_coef is queued
+  plk::Fr last_ch[7];
+  bool have_round3 = false;
   // the round-4 evaluations: coherent mapped host memory that k_eval_final writes directly
   plk::PinnedBuf eval_out;
   void* eval_dev = nullptr;  // eval_out's device address

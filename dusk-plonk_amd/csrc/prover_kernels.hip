@@ -4,7 +4,7 @@
 //  * grand product z (permutation.rs:205-300): per-gate numerator/denominator, then
 //    z_i = N_i * S_i / D (exclusive prefix product of numerators, inclusive suffix product
 //    of denominators, ONE inversion) instead of the reference's n inversions + serial scan
-//  * quotient over five n-point cosets of the reference's 8n coset (prover.hpp;
+//  * quotient over four n-point cosets of the reference's 8n coset (prover.hpp;
 //    quotient_poly.rs:74-114,122-262): arithmetic + range widgets + PI + permutation
 //    identity/copy terms + L1 term, divided by v_h, whose one value per coset is inverted
 //    once on the host
@@ -470,6 +470,30 @@ __global__ void __launch_bounds__(256) k_coset_combine(const Fr* __restrict__ in
   }
 }
 
+// The four-block combine with the closed-form top (pk_coset_combine_top, prover.hpp): thread k
+// owns coefficient k of every chunk, so the threads k < 8 add their patch values before the
+// store and write the fifth chunk's eight coefficients; no other thread touches those.
+__global__ void __launch_bounds__(256) k_coset_combine_top(const Fr* __restrict__ in, uint64_t n,
+                                                           CombineMat mat, QuotientPatch patch,
+                                                           Fr* __restrict__ out) {
+  constexpr int B = kQBlocksTop;
+  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  RFr r[B];
+#pragma unroll
+  for (int m = 0; m < B; ++m) r[m] = ldr(&in[m * n + k]);
+#pragma unroll
+  for (int l = 0; l < B; ++l) {
+    const Fr* row = &mat.m[l * B];
+    RFr e = rx_mul_add(r[0], rx_unpack(row[0]), r[1], rx_unpack(row[1]));
+    e = rx_add(e, rx_mul_add(r[2], rx_unpack(row[2]), r[3], rx_unpack(row[3])));
+    Fr v = rx_pack_canonical(e);
+    if (k <= kTop) v = fe_add(v, patch.v[l][k]);
+    stf(&out[l * n + k], v);
+  }
+  if (k <= kTop) stf(&out[B * n + k], patch.v[B][k]);
+}
+
 // ------------------------------------------------------------ scaled table copy
 __global__ void k_scale_copy(const Fr* __restrict__ in, Fr c, Fr* __restrict__ out, uint64_t n) {
   const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -807,6 +831,15 @@ int pk_coset_combine(const Fr* in, uint64_t n, int blocks, const CombineMat& mat
     hipLaunchKernelGGL((k_coset_combine<kQBlocksSmall>), grid, dim3(256), 0, s, in, n, mat, out);
   else
     return PLK_E_ARG;
+  PLK_HIP_TRY(hipGetLastError());
+  return PLK_OK;
+}
+
+int pk_coset_combine_top(const Fr* in, uint64_t n, const CombineMat& mat,
+                         const QuotientPatch& patch, Fr* out, hipStream_t s) {
+  if (n <= (uint64_t)kTop) return PLK_E_ARG;
+  hipLaunchKernelGGL(k_coset_combine_top, dim3(cdiv(n, 256)), dim3(256), 0, s, in, n, mat, patch,
+                     out);
   PLK_HIP_TRY(hipGetLastError());
   return PLK_OK;
 }

@@ -64,7 +64,7 @@ ABI_SYMBOLS = (
     "plk_ntt_dev", "plk_ntt_batch_dev", "plk_srs_setup", "plk_srs_load", "plk_srs_destroy",
     "plk_srs_len", "plk_srs_points", "plk_msm", "plk_commit", "plk_commit_dev",
     "plk_srs_last_msm_stats", "plk_debug_field_op", "plk_debug_rx_op", "plk_debug_g1r_op",
-    "plk_debug_block_eval", "plk_debug_ntt_lazy_op", "plk_debug_prover_stage",
+    "plk_debug_block_eval", "plk_debug_ntt_lazy_op", "plk_debug_prover_stage", "plk_debug_prover_round3",
     "plk_commit_batch_dev",
     "plk_commit_batch_dev_part",
     "plk_srs_setup_range", "plk_g1_sum", "plk_msm_sharded", "plk_srs_msm_stats_reset",
@@ -416,24 +416,14 @@ class Context:
 
     # stage -> code of plk_debug_prover_stage (include/plk.h)
     PROVER_STAGES = {"perm_numden": 0, "scan": 1, "quotient": 2, "pi_sparse": 3, "pi_coef": 4,
-                     "coset_combine": 5, "eval": 6, "lincomb": 7, "scale_powers": 8, "ruffini": 9}
+                     "coset_combine": 5, "eval": 6, "lincomb": 7, "scale_powers": 8, "ruffini": 9,
+                     "quotient_top": 10, "coset_combine_top": 11}
 
     def prover_stage(self, stage, arrays=(), scalars=(), params=(), out_len: int = 0) -> np.ndarray:
         """One pk_* launcher of the prover (csrc/prover_kernels.hip) on host arrays (test
         support): stage a key of PROVER_STAGES (or a raw code), arrays uint64[len, 4] Montgomery
         words each, scalars uint64[k, 4], params integers; returns uint64[out_len, 4]."""
-        code = self.PROVER_STAGES[stage] if isinstance(stage, str) else int(stage)
-        arrs = [np.ascontiguousarray(np.asarray(a, dtype=np.uint64).reshape(-1, 4)) for a in arrays]
-        ptrs = (C.c_void_p * max(len(arrs), 1))(*[a.ctypes.data if a.shape[0] else None for a in arrs])
-        lens = (C.c_size_t * max(len(arrs), 1))(*[a.shape[0] for a in arrs])
-        sc = np.ascontiguousarray(np.asarray(scalars, dtype=np.uint64).reshape(-1, 4))
-        par = np.ascontiguousarray(np.asarray(list(params), dtype=np.uint64).reshape(-1))
-        out = np.zeros((out_len, 4), dtype=np.uint64)
-        _check(_lib().plk_debug_prover_stage(
-            self.handle, code, ptrs if arrs else None, lens if arrs else None, len(arrs),
-            _ptr(sc) if sc.shape[0] else None, sc.shape[0], _ptr(par) if par.shape[0] else None,
-            par.shape[0], _ptr(out) if out_len else None, out_len), "plk_debug_prover_stage")
-        return out
+        return _prover_stage(self.handle, stage, arrays, scalars, params, out_len)
 
     def domain(self, k: int) -> C.c_void_p:
         if k not in self._domains:
@@ -441,6 +431,27 @@ class Context:
             _check(_lib().plk_domain_get(self.handle, k, C.byref(d)), "plk_domain_get")
             self._domains[k] = d
         return self._domains[k]
+
+
+def _prover_stage(handle, stage, arrays, scalars, params, out_len: int) -> np.ndarray:
+    code = Context.PROVER_STAGES[stage] if isinstance(stage, str) else int(stage)
+    arrs = [np.ascontiguousarray(np.asarray(a, dtype=np.uint64).reshape(-1, 4)) for a in arrays]
+    ptrs = (C.c_void_p * max(len(arrs), 1))(*[a.ctypes.data if a.shape[0] else None for a in arrs])
+    lens = (C.c_size_t * max(len(arrs), 1))(*[a.shape[0] for a in arrs])
+    sc = np.ascontiguousarray(np.asarray(scalars, dtype=np.uint64).reshape(-1, 4))
+    par = np.ascontiguousarray(np.asarray(list(params), dtype=np.uint64).reshape(-1))
+    out = np.zeros((out_len, 4), dtype=np.uint64)
+    _check(_lib().plk_debug_prover_stage(
+        handle, code, ptrs if arrs else None, lens if arrs else None, len(arrs),
+        _ptr(sc) if sc.shape[0] else None, sc.shape[0], _ptr(par) if par.shape[0] else None,
+        par.shape[0], _ptr(out) if out_len else None, out_len), "plk_debug_prover_stage")
+    return out
+
+
+def quotient_top(arrays, scalars, params) -> np.ndarray:
+    """Stage "quotient_top" of plk_debug_prover_stage (include/plk.h): the quotient's coefficients
+    4n .. 4n + 6 from the factor polynomials' top coefficients. Host code: no GPU, no Context."""
+    return _prover_stage(None, "quotient_top", arrays, scalars, params, 7)
 
 
 # ------------------------------------------------------------------------ value types

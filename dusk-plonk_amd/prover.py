@@ -1059,6 +1059,24 @@ class ProverLane:
         _check(f(self._h, basis, entries), "plk_prover_commit_info")
         return (["lagrange" if b else "coefficient" for b in basis], [int(e) for e in entries])
 
+    def round3(self) -> dict:
+        """The polynomials of this lane's last round 3 (plk_debug_prover_round3, test support;
+        keys with n >= 16), Montgomery words uint64[., 4]: ch (alpha beta gamma range_sep logic_sep
+        fixed_sep var_sep), sel [11, n], sigma [4, n], wires [4, n + 2], z [n + 3], t [4n + 8]."""
+        n = self.prover.n
+        out = np.zeros((24 * n + 26, 4), dtype=np.uint64)
+        f = _bind().plk_debug_prover_round3
+        f.restype, f.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]
+        _check(f(self._h, _ptr(out), out.shape[0]), "plk_debug_prover_round3")
+        parts, at = {}, 0
+        for name, rows, cols in (("ch", 1, 7), ("sel", 11, n), ("sigma", 4, n), ("wires", 4, n + 2),
+                                 ("z", 1, n + 3), ("t", 1, 4 * n + 8)):
+            parts[name] = out[at:at + rows * cols].reshape(rows, cols, 4)
+            at += rows * cols
+        for name in ("ch", "z", "t"):
+            parts[name] = parts[name][0]
+        return parts
+
     def close(self):
         if self._h:
             _bind().plk_prover_destroy(self._h)

@@ -930,7 +930,8 @@ int plk_debug_g1r_op(plk_ctx* ctx, int op, const uint32_t* p, const uint32_t* q,
  * (Montgomery form) evaluated on the blocks of the key's quotient domain, the cosets
  * g w_8n^m H_n, m < blocks (5; 6 for n = 8): out[m * n + u] = p(g w_8n^m w_n^u), the point
  * 8u + m of the reference's g H_8n. out holds blocks * n values; *blocks_out (may be NULL)
- * receives the block count. out == NULL only reports the block count. */
+ * receives the block count. out == NULL only reports the block count. (The prover's round 3
+ * itself uses the first four of these cosets for n >= 16; this call evaluates on five.) */
 int plk_debug_block_eval(plk_key* key, const uint64_t* coef, size_t len, uint64_t* out,
                          size_t out_cap, int* blocks_out);
 /* One stage of the prover's rounds on caller arrays: the arrays are copied to the device, the
@@ -957,12 +958,25 @@ int plk_debug_block_eval(plk_key* key, const uint64_t* coef, size_t len, uint64_
  *   7 pk_lincomb: up to 24 terms; one scalar each; len_out -> len_out
  *   8 pk_scale_powers: c; x; shift -> c_j x^(j + shift)
  *   9 pk_ruffini: c (len); z (not 0); - -> the len - 1 coefficients of (c(X) - c(z)) / (X - z)
+ *  10 quotient_top (host code, ctx may be NULL): the top seven coefficients, in ascending order, of
+ *     the wires (4 x 7: n-5 .. n+1), z (7: n-4 .. n+2), the selectors (11 x 7, gate order: n-7 ..
+ *     n-1), the sigmas (4 x 7) and L1 (7); alpha beta gamma range_sep logic_sep fixed_sep var_sep,
+ *     omega, then the public-input values; log2 n (>= 4), the has_* flags as in stage 2, then one
+ *     gate index per public input -> t[4n .. 4n + 6], the numerator's coefficients 5n .. 5n + 6
+ *  11 pk_coset_combine_top: 4 x n coefficients (the inverse block transforms); the 16 matrix
+ *     entries (times 2^5, row major), t[4n .. 4n + 6], then p_0 .. p_4 with prod_{m<4} (Y - c_m) =
+ *     sum p_l Y^l; - -> the 4n + 8 coefficients of t
  * PLK_E_ARG: an unknown stage, a NULL array of non-zero length, lengths that do not fit together,
  * out_cap too small, and whatever the launcher itself refuses. A zero-length problem is PLK_OK and
  * writes nothing. */
 int plk_debug_prover_stage(plk_ctx* ctx, int stage, const uint64_t* const* in, const size_t* in_len,
                            size_t n_in, const plk_fr* scalars, size_t n_scalars,
                            const uint64_t* params, size_t n_params, uint64_t* out, size_t out_cap);
+/* The polynomials of the prover's last round 3, Montgomery form: alpha beta gamma range_sep
+ * logic_sep fixed_sep var_sep, the 11 selectors' n coefficients each (gate order), the 4 sigmas',
+ * the 4 blinded wires' n + 2, z's n + 3 and t's 4n + 8: 24n + 26 elements. PLK_E_ARG unless the
+ * prover's last plk_prover_prove reached round 3 on a key with n >= 16, or out_cap is too small. */
+int plk_debug_prover_round3(plk_prover* p, uint64_t* out, size_t out_cap);
 /* The device-mode fold weights (plk_verifier_set_replay) from given entropy and u challenges
  * (Montgomery form): out[j] = rho_j, j < count. ctx = NULL: the host mirror, no GPU; otherwise
  * the kernel the fold runs. PLK_E_ARG: a NULL argument, count = 0, a non-canonical u. */
