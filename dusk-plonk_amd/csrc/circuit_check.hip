@@ -14,12 +14,6 @@
 #include "internal.hpp"
 #include "prover.hpp"
 
-#define TRY(...)                   \
-  do {                             \
-    int _st = (__VA_ARGS__);       \
-    if (_st != PLK_OK) return _st; \
-  } while (0)
-
 namespace plk {
 
 constexpr uint32_t kCheckBlock = 256, kCheckWaves = kCheckBlock / 64;

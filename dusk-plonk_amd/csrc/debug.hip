@@ -616,14 +616,15 @@ extern "C" int plk_debug_field_op(plk_ctx* ctx, int field, int op, const uint64_
   }
 }
 
-// the same call the prover makes for z, the wires and the key's tables (prover.hip coset_fwd)
+// the same call the prover makes for z and PI and key compilation for its tables (key.hip
+// coset_blocks_fwd)
 extern "C" int plk_debug_block_eval(plk_key* key, const uint64_t* coef, size_t len, uint64_t* out,
                                     size_t out_cap, int* blocks_out) {
   using plk::last_hip_error;
   try {
     if (!key) return PLK_E_ARG;
     // the cosets m < 5 (6 for n = 8), whatever number of them the prover's round 3 uses: a coset
-    // table of this call's own, made as the key's is (prover.hip)
+    // table of this call's own, made as the key's is (key.hip)
     const int blocks = key->n >= 16 ? plk::kQBlocks : plk::kQBlocksSmall;
     if (blocks_out) *blocks_out = blocks;
     if (!out) return PLK_OK;
@@ -637,21 +638,14 @@ extern "C" int plk_debug_block_eval(plk_key* key, const uint64_t* coef, size_t l
         (st = table.alloc(blocks * (n + 8) * sizeof(plk::Fr))))
       return st;
     PLK_HIP_TRY(hipMemcpyAsync(din.ptr, coef, len * sizeof(plk::Fr), hipMemcpyHostToDevice, s));
-    plk::Fr w8n, sm = key->dom->g;
-    plk::fr_root_of_unity(key->k + 3, w8n);
-    for (int mb = 0; mb < blocks; ++mb) {
-      if ((st = plk::ntt_power_table(table.as<plk::Fr>() + mb * (n + 8), sm, plk::fe_one<plk::FrCfg>(),
-                                     n + 8, true, s)))
+    plk::Fr sm[plk::kQBlocksMax];
+    plk::coset_shifts(key->dom, blocks, sm);
+    for (int mb = 0; mb < blocks; ++mb)
+      if ((st = plk::ntt_power_table(table.as<plk::Fr>() + mb * (n + 8), sm[mb],
+                                     plk::fe_one<plk::FrCfg>(), n + 8, true, s)))
         return st;
-      sm = plk::fe_mul(sm, w8n);
-    }
-    plk::NttBatch b;
-    b.in_stride = 0;
-    b.out_stride = n;
-    b.pre = table.as<plk::Fr>();
-    b.pre_stride = n + 8;
-    if ((st = plk::ntt_run_batch(key->dom, din.as<plk::Fr>(), dout.as<plk::Fr>(), len, 1, 1,
-                                 nullptr, s, (uint32_t)blocks, b)))
+    if ((st = plk::coset_blocks_fwd(key->dom, din.as<plk::Fr>(), dout.as<plk::Fr>(), len,
+                                    table.as<plk::Fr>(), blocks, nullptr, s)))
       return st;
     PLK_HIP_TRY(hipMemcpyAsync(out, dout.ptr, total * sizeof(plk::Fr), hipMemcpyDeviceToHost, s));
     PLK_HIP_TRY(plk::stream_wait(s));

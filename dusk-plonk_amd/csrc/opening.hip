@@ -5,7 +5,7 @@
 // (/root/reference/src/prover.rs:422-438 at z, :444-450 at z·ω), i.e.
 //   W(X) = (sum_i v^i p_i(X)) / (X - point)        (Ruffini; the remainder is dropped)
 // in the un-vendored zksnarks crate. plk_prove does the same inside the prover (k_lincomb +
-// pk_ruffini, prover.hip); these entries expose it on its own so a patched zksnarks can
+// pk_ruffini, prover.hip round5_openings); these entries expose it on its own so a patched zksnarks can
 // route the call to the GPU at the primitive level, like plk_commit.
 //
 // Device work: ceil(k / 23) k_lincomb passes (a linear combination of up to kMaxTerms

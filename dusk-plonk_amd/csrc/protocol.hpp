@@ -1,4 +1,4 @@
-// protocol.hpp — the PLONK protocol, stated once for the prover (prover.hip, prover_kernels.hip),
+// protocol.hpp — the PLONK protocol, stated once for the prover (key.hip, prover.hip, prover_kernels.hip),
 // the verifier (verifier.hip) and the device replay (verifier_replay.hip): the names of a proof's
 // evaluations, challenges and commitments, the shared constants, the widgets, the scalars of the
 // linearisation polynomial r, the values at z that enter the transcript, and the order in which

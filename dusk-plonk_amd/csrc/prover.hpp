@@ -1,14 +1,22 @@
-// prover.hpp — composer, proving key and prover objects behind the plk_composer / plk_key /
-// plk_prove entry points of include/plk.h, and the kernel-argument structs of
-// prover_kernels.hip.
+// prover.hpp — proving key and prover objects behind the plk_key / plk_prove entry points of
+// include/plk.h (key.hip, commit.hip, prover.hip; the composer is composer.hpp), and the
+// kernel-argument structs of prover_kernels.hip.
 #pragma once
 #include <map>
 #include <string>
 #include <vector>
 
+#include "composer.hpp"
 #include "internal.hpp"
 #include "protocol.hpp"
 #include "quotient_top.hpp"
+
+// return a PLK_* status other than PLK_OK to the caller
+#define TRY(...)                   \
+  do {                             \
+    int _st = (__VA_ARGS__);       \
+    if (_st != PLK_OK) return _st; \
+  } while (0)
 
 namespace plk {
 
@@ -74,7 +82,7 @@ struct BlindBatch {
 // A(c_m) = 1 / (c_m - 1), whose leading coefficient kappa is not zero (else A(c)(c - 1) - 1, of
 // degree <= B - 1, would vanish at B points and hence at c = 1, where it is -1); q has degree
 // <= 4n + 6, so the coefficients [40, 48) are kappa rho and the zero check of t_4 past its
-// n + 8 committed points (prover.hip) fails there. kQBlocks = 5 is the smallest count that
+// n + 8 committed points (prover.hip round3_quotient) fails there. kQBlocks = 5 is the smallest count that
 // determines t for n >= 16 without the closed form: the stage tests and plk_debug_block_eval
 // still run it.
 constexpr int kQBlocksTop = 4, kQBlocks = 5, kQBlocksSmall = 6, kQBlocksMax = 6;
@@ -188,47 +196,21 @@ int pk_scale_powers(const Fr* c, uint64_t len, const Fr& x, uint64_t shift, Fr* 
 int pk_ruffini(const Fr* c, uint64_t len, const Fr& z, Fr* q, Fr* tmp, Fr* scan_tmp,
                hipStream_t s);
 
-// ---- composer (host) ---------------------------------------------------------------
-// One width-4 gate: q_m a b + q_l a + q_r b + q_o o + q_4 d + q_c + PI = 0 (lib.rs:546)
-struct Gate {
-  Fr q[11];  // q_m q_l q_r q_o q_4 q_c q_arith q_range q_logic q_fixed_group_add q_variable_group_add
-  uint32_t w[4];  // a, b, o, d witness indices
-  bool has_pi;
-  Fr pi;
-};
-
-// The composer stores a gate as 24 bytes instead of Gate's 416: the four wires, a 2-bit
-// code per selector (kSelZero / kSelOne / kSelMinusOne / kSelPooled) with bit kPiBit set
-// when the gate carries a public input, and `ext`, the index in plk_composer::consts of
-// the gate's pooled selectors (in selector order) followed by its PI value. Circuits are
-// dominated by 0/±1 selectors, so synthesis writes ~17x fewer bytes per gate.
-enum : uint32_t { kSelZero = 0, kSelOne = 1, kSelMinusOne = 2, kSelPooled = 3 };
-constexpr uint32_t kPiBit = 1u << 22;
 struct CheckWs;  // circuit_check.hpp
-struct GateRec {
-  uint32_t w[4];
-  uint32_t code;
-  uint32_t ext;
-};
-PLK_HD uint32_t sel_code(uint32_t code, int q) { return (code >> (2 * q)) & 3u; }
+
+// ---- the quotient domain's block transforms (key.hip) ------------------------------
+// s_m[m] = g w_8n^m, m < blocks: the shifts of the cosets s_m H_n of dom
+PLK_LOCAL void coset_shifts(const plk_domain* dom, int blocks, Fr* s_m);
+// The forward coset transforms of one polynomial (len <= n + 8 coefficients, folded onto the
+// block) onto `blocks` cosets in one launch per pass: block m to out + m n, pre-multiplied by
+// row m of `table` (rows of n + 8: s_m^j, scaled or not). Key compilation, the prover's
+// round 3 and plk_debug_block_eval all transform through here.
+PLK_LOCAL int coset_blocks_fwd(plk_domain* dom, const Fr* in, Fr* out, uint64_t len,
+                               const Fr* table, int blocks, Fr* scratch, hipStream_t s);
+// out[0 .. count] = the coefficients of prod_{j < count} (X - c[j]), lowest first
+PLK_LOCAL void poly_from_roots(const Fr* c, int count, Fr* out);
 
 }  // namespace plk
-
-struct plk_composer {
-  std::vector<plk::Fr> witness;
-  std::vector<plk::GateRec> gates;
-  std::vector<plk::Fr> consts;  // pooled selector / PI values (see GateRec)
-  // witness -> its wires in insertion order (permutation.rs:21-25,72-104), wire = 4*gate+col,
-  // as flat singly linked lists (no per-witness allocation): head/tail per witness, next
-  // per wire; kNoWire terminates.
-  static constexpr uint32_t kNoWire = 0xffffffffu;
-  std::vector<uint32_t> wire_head, wire_tail, wire_next;
-  // running hash of the circuit's structure (every gate's wires, selector codes, pooled
-  // selector values and public-input position — not witness or public-input values),
-  // updated as gates are appended: plk_prove compares it with the key's in O(1)
-  static constexpr uint64_t kHashInit = 0x6a09e667f3bcc908ull;
-  uint64_t struct_hash = kHashInit;
-};
 
 struct plk_key {
   plk_ctx* ctx = nullptr;
@@ -255,6 +237,7 @@ struct plk_key {
   plk::DevBuf coset_s, coset_w, coset_pi;
   plk::DevBuf icoset_q;     // qb rows of n: n^-1 s_m^-k (R'), inverse blocks
   plk::Fr s_m[plk::kQBlocksMax];  // g w_8n^m (R domain)
+  plk::Fr c_m[plk::kQBlocksMax];  // s_m^n (R domain)
   plk::CombineMat comb;     // pk_coset_combine's matrix (R')
   plk::DevBuf wire_idx;     // 4 x n witness indices per gate (u32)
   // the compact gate table of plk_prover_diagnose (circuit_check.hpp): the composer's m gate
@@ -325,3 +308,23 @@ struct plk_prover {
       pi_coef, evq, quotq, t_coef, agg, agg2, w_coef, eval_partial, ntt_scratch;
   ~plk_prover();
 };
+
+// ---- commit paths (commit.hip) -----------------------------------------------------
+namespace plk {
+// commit a batch of device polys against the key's trimmed SRS (key.rs:81-82): a poly whose
+// non-zero part is longer than the trimmed SRS fails with PLK_E_DEGREE. `ws` / `s`: the
+// calling prover's MSM workspace and stream. cap: commit at most `cap` points, the rest of each
+// polynomial must be zero (else PLK_E_DEGREE) — the quotient chunks' bound
+PLK_LOCAL int key_commit(plk_key* key, MsmWorkspace& ws, const std::vector<const Fr*>& ptrs,
+                         const std::vector<size_t>& lens, plk_g1* outs, int* statuses,
+                         hipStream_t s, size_t cap = SIZE_MAX, MsmSlotInfo* info = nullptr);
+// the same for a prover: over the ranks of a sharded one, else key_commit on its stream
+PLK_LOCAL int prover_commit(plk_prover* P, const std::vector<const Fr*>& ptrs,
+                            const std::vector<size_t>& lens, plk_g1* outs, int* statuses,
+                            size_t cap = SIZE_MAX);
+// Round 1's four wire commits, each from its Lagrange values [w(omega^i) | b_0 b_1] (lag + c
+// stride) unless that wire is hot, else from its blinded coefficients (coef + c stride); fills
+// P->commit_basis / commit_entries
+PLK_LOCAL int commit_wires(plk_prover* P, const Fr* lag, const Fr* coef, uint64_t stride,
+                           plk_g1 out[4]);
+}  // namespace plk

@@ -5,7 +5,8 @@
  * structs of un-vendored crates (no FFI exists there); each entry point
  * below replaces one of those calls. The host-side mirror that calls this ABI with the
  * reference's names is dusk-plonk_amd/plonk.py + dusk-plonk_amd/prover.py (Python, used by
- * the tests and bench.py); the C++ prover behind plk_prove is dusk-plonk_amd/csrc/prover.hip.
+ * the tests and bench.py); the C++ prover behind plk_prove is dusk-plonk_amd/csrc/prover.hip
+ * (composer: composer.hip, proving key: key.hip, commits: commit.hip).
  * INTEGRATION.md shows the Rust-side binding.
  *
  * Conventions

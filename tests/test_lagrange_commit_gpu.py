@@ -1,4 +1,4 @@
-"""Round 1's wire commits from Lagrange values (lagrange.hip, prover.hip).
+"""Round 1's wire commits from Lagrange values (lagrange.hip, commit.hip).
 
 Basis: the Lagrange-basis SRS of a 2^k domain (n + 3 points: [L_i(tau)]G1, then the three
 blinder points [tau^(n+t)]G1 - [tau^t]G1) commits [values | blinders] to the same point, bit for
