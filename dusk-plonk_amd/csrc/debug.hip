@@ -3,15 +3,18 @@
 // ffr.hpp on raw limb rows; plk_debug_ntt_lazy_op: the NTT pass' lazy butterfly helpers (the
 // kernel is in ntt.hip); plk_debug_g1r_op: the XYZZ group law of g1r.hpp on raw limb rows;
 // plk_debug_block_eval: the prover's forward block transform onto a key's quotient domain;
-// plk_debug_prover_stage: one pk_* launcher of prover_kernels.hip on caller arrays.
+// plk_debug_prover_stage: one pk_* launcher of prover_kernels.hip on caller arrays;
+// plk_debug_msm_snapshot: one fixed-base MSM batch and what it left in its workspace.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstring>
+#include <memory>
 #include <vector>
 
 #include "g1r.hpp"
 #include "internal.hpp"
+#include "msm_common.hpp"
 #include "prover.hpp"
 
 namespace plk {
@@ -707,6 +710,98 @@ extern "C" int plk_debug_prover_round3(plk_prover* p, uint64_t* out, size_t out_
     PLK_HIP_TRY(d2h(p->t_coef.as<Fr>(), 4 * n + 8));
     PLK_HIP_TRY(plk::stream_wait(s));
     return PLK_OK;
+  } catch (...) {
+    return PLK_E_DEVICE;
+  }
+}
+
+// One batch of the fixed-base MSM on a workspace of this call's own, then the workspace's buffers
+// as the batch left them (include/plk.h). msm_run_batch is the library's, unchanged: it reports
+// what it derived in MsmWorkspace::last.
+extern "C" int plk_debug_msm_snapshot(plk_srs* s, const plk_fr* const* scalars, const size_t* lens,
+                                      size_t count, plk_msm_snapshot* snap, plk_g1* outs,
+                                      int* statuses) {
+  using namespace plk;
+  try {
+    if (!s || !lens || !snap || !outs || !statuses || count == 0 || count > kMaxSlots ||
+        (!scalars && count) || snap->tail_quad > 2)
+      return PLK_E_ARG;
+    for (size_t k = 0; k < count; ++k)
+      if (!scalars[k] && lens[k]) return PLK_E_ARG;
+    DeviceGuard g(s->ctx->device);
+    hipStream_t st = s->ctx->stream;
+    DevBuf dsc[kMaxSlots];
+    const Fr* ptrs[kMaxSlots];
+    size_t use[kMaxSlots], chk[kMaxSlots];
+    int r;
+    for (size_t k = 0; k < count; ++k) {
+      if ((r = dsc[k].alloc(std::max<size_t>(lens[k], 1) * sizeof(Fr)))) return r;
+      if (lens[k])
+        PLK_HIP_TRY(hipMemcpyAsync(dsc[k].ptr, scalars[k], lens[k] * sizeof(Fr), hipMemcpyHostToDevice, st));
+      ptrs[k] = dsc[k].as<Fr>();
+      chk[k] = lens[k];
+      use[k] = std::min(lens[k], s->n);
+    }
+    struct WsDelete {
+      void operator()(MsmWorkspace* w) const { msm_workspace_delete(w); }
+    };
+    std::unique_ptr<MsmWorkspace, WsDelete> ws(msm_workspace_new());
+    MsmWorkspace& w = *ws;
+    w.shared_chip = snap->shared_chip != 0;
+    w.tail_quad = (int)snap->tail_quad;
+    r = msm_run_batch(s, w, ptrs, use, chk, count, outs, statuses, st, snap->part, snap->parts,
+                      snap->guard_limit);
+    if (r != PLK_OK && r != PLK_E_DEGREE) return r;
+    const MsmDerived& d = w.last;
+    const uint64_t hdr[PLK_MSM_SNAPSHOT_HDR] = {
+        d.B, d.W, d.narrow, d.c, d.chunk, d.rb, d.fb, d.NC, d.NR, d.G, d.nbits, d.nout, d.wide,
+        d.sort_one, d.hold, w.task_stride, w.sorted_stride, d.max_tasks_used, d.b_lo, s->n, d.gen,
+        snap->part, snap->parts, s->has_inf ? 1u : 0u};
+    std::memcpy(snap->hdr, hdr, sizeof hdr);
+    const size_t B = d.B, row = sizeof(G1xyzz);
+    static_assert(sizeof(G1xyzz) == 48 * 4, "packed XYZZ row");
+    auto d2h = [&](uint32_t* dst, const void* src, size_t off_bytes, size_t bytes) -> hipError_t {
+      if (!dst || !bytes) return hipSuccess;
+      return hipMemcpy(dst, static_cast<const uint8_t*>(src) + off_bytes, bytes, hipMemcpyDeviceToHost);
+    };
+    const ReadbackHeader* rh = w.host_out.as<ReadbackHeader>();
+    const G1xyzz* T = reinterpret_cast<const G1xyzz*>(rh + 1);
+    for (size_t k = 0; k < count; ++k) {
+      // the slot's entry and task counts first: they bound the copies below
+      uint32_t ends[2] = {0, 0};
+      PLK_HIP_TRY(hipMemcpy(&ends[0], w.offsets.as<uint32_t>() + k * (B + 1) + B, 4, hipMemcpyDeviceToHost));
+      PLK_HIP_TRY(hipMemcpy(&ends[1], w.task_off.as<uint32_t>() + k * (B + 1) + B, 4, hipMemcpyDeviceToHost));
+      const size_t n_ent = ends[0], n_task = ends[1];
+      if (n_ent + 1 > w.sorted_stride || n_task > w.task_stride) return PLK_E_DEVICE;
+      if ((snap->sorted && n_ent > snap->cap_sorted) ||
+          ((snap->tasks || snap->partials) && n_task > snap->cap_tasks))
+        return PLK_E_ARG;
+      snap->n_tasks[k] = (uint32_t)n_task;
+      PLK_HIP_TRY(d2h(snap->offsets ? snap->offsets + k * (B + 1) : nullptr, w.offsets.ptr, k * (B + 1) * 4, (B + 1) * 4));
+      PLK_HIP_TRY(d2h(snap->task_off ? snap->task_off + k * (B + 1) : nullptr, w.task_off.ptr, k * (B + 1) * 4, (B + 1) * 4));
+      PLK_HIP_TRY(d2h(snap->sorted ? snap->sorted + k * snap->cap_sorted : nullptr, w.sorted.ptr,
+                      k * w.sorted_stride * 4, n_ent * 4));
+      PLK_HIP_TRY(d2h(snap->tasks ? snap->tasks + 2 * k * snap->cap_tasks : nullptr, w.tasks.ptr,
+                      k * w.task_stride * sizeof(uint2), n_task * sizeof(uint2)));
+      PLK_HIP_TRY(d2h(snap->partials ? snap->partials + 48 * k * snap->cap_tasks : nullptr, w.partials.ptr,
+                      k * w.task_stride * row, n_task * row));
+      if (d.wide) {
+        PLK_HIP_TRY(d2h(snap->rsum ? snap->rsum + 48 * k * B : nullptr, w.rsum.ptr, k * B * row, B * row));
+        PLK_HIP_TRY(d2h(snap->ys ? snap->ys + 48 * k * d.NR : nullptr, w.ys.ptr, k * d.NR * row, d.NR * row));
+        PLK_HIP_TRY(d2h(snap->zs ? snap->zs + 48 * k * d.NR : nullptr, w.zs.ptr, k * d.NR * row, d.NR * row));
+      } else {
+        PLK_HIP_TRY(d2h(snap->bsum ? snap->bsum + 48 * k * B : nullptr, w.bsum.ptr, k * B * row, B * row));
+      }
+      if (snap->bits) std::memcpy(snap->bits + 48 * k * d.nout, &T[k * d.nout], d.nout * row);
+      if (snap->readback) {
+        snap->readback[3 * k] = rh->flag[k];
+        snap->readback[3 * k + 1] = rh->entries[k];
+        snap->readback[3 * k + 2] = rh->max_count[k];
+      }
+    }
+    return r;
+  } catch (const std::bad_alloc&) {
+    return PLK_E_OOM;
   } catch (...) {
     return PLK_E_DEVICE;
   }

@@ -1579,6 +1579,8 @@ int msm_run_batch(plk_srs* s, MsmWorkspace& w, const Fr* const* d_scalars, const
   // not pay, profiles/r04_sort_one_big_ab.jsonl)
   const bool sort_one = small_batch || (!wide && B <= kSortSmallMax && max_len <= kSortOneBig);
   const bool hold = max_len <= kSortOneMax;
+  w.last = MsmDerived{B, s->windows, s->narrow, s->c, chunk, rb, fb, NC, NR, G, nbits, nout, wide,
+                      sort_one, sort_one && hold, part * B, gen, max_tasks_used};
   if (max_tail && !sort_one) {
     hipLaunchKernelGGL(k_any_nonzero, dim3(cdiv(max_tail, 256), slots), dim3(256), 0, stream,
                        batch, hdr_dev->flag, gen);

@@ -99,7 +99,16 @@ struct ReadbackHeader {
 };
 static_assert(sizeof(ReadbackHeader) % 16 == 0, "alignment of the bit sums");
 
+// What msm_run_batch derived for its most recent batch on a workspace (MsmWorkspace::last), for
+// plk_debug_msm_snapshot (debug.hip): the host's report only, no kernel reads it.
+struct MsmDerived {
+  uint32_t B = 0, W = 0, narrow = 0, c = 0, chunk = 0, rb = 0, fb = 0, NC = 0, NR = 0, G = 0;
+  uint32_t nbits = 0, nout = 0, wide = 0, sort_one = 0, hold = 0, b_lo = 0, gen = 0;
+  uint64_t max_tasks_used = 0;
+};
+
 struct MsmWorkspace {
+  MsmDerived last;
   DevBuf counts, blockhist, offsets, task_off, full_off, len_cur, sorted, tasks, partials, bsum, bits1;
   // wide bucket sets only (msm.hip: two-level sort, run-sum reduction)
   DevBuf tmp, task_rel, bin_tot, len_fill, coarse_off, rsum, ys, zs;

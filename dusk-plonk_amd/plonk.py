@@ -56,6 +56,9 @@ _KZG_SYMBOLS = ("plk_kzg_open", "plk_kzg_open_domain", "plk_kzg_last_open_ms", "
                 "plk_debug_g1_ntt", "plk_kzg_open_cosets", "plk_kzg_fold_cosets",
                 "plk_debug_g1_ntt_batch", "plk_debug_g1_colsum")
 
+# the MSM stage snapshot of csrc/debug.hip (bound only when the loaded library has it, as above)
+_MSM_DEBUG_SYMBOLS = ("plk_debug_msm_snapshot",)
+
 # Symbols declared in include/plk.h (checked by tests/test_abi.py)
 ABI_SYMBOLS = (
     "plk_abi_version", "plk_status_str", "plk_build_info", "plk_device_count", "plk_ctx_create",
@@ -107,6 +110,8 @@ ABI_SYMBOLS = (
     *_CHECK_SYMBOLS,
     # KZG openings (PlonkParams.open / open_domain, OpeningKey.fold_openings) and the G1 transform
     *_KZG_SYMBOLS,
+    # the fixed-base MSM's stage snapshot (debug_msm_snapshot here)
+    *_MSM_DEBUG_SYMBOLS,
 )
 
 # per-item status of the ingest calls (include/plk.h PLK_INGEST_*)
@@ -185,6 +190,7 @@ def _lib():
             "plk_debug_g1r_op": (i32, [vp, i32, vp, vp, vp, vp, sz]),
             "plk_debug_block_eval": (i32, [vp, vp, sz, vp, sz, C.POINTER(i32)]),
             "plk_debug_prover_stage": (i32, [vp, i32, vp, vp, sz, vp, sz, vp, sz, vp, sz]),
+            "plk_debug_msm_snapshot": (i32, [vp, vp, vp, sz, vp, vp, vp]),
             "plk_commit_batch_dev": (i32, [vp, vp, vp, sz, vp, vp, vp]),
             "plk_commit_batch_dev_part": (i32, [vp, vp, vp, sz, u32, u32, vp, vp, vp]),
             "plk_srs_setup_range": (i32, [vp, vp, u64, sz, vp, pp]),
@@ -240,7 +246,7 @@ def _lib():
         }
         for name, (res, args) in sig.items():
             if (name in _SRS_IO_SYMBOLS + _SRS_UPDATE_SYMBOLS + _CHECK_SYMBOLS + _KZG_SYMBOLS
-                    and not hasattr(lib, name)):
+                    + _MSM_DEBUG_SYMBOLS and not hasattr(lib, name)):
                 continue  # a PLK_LIB build from before srs_io.hip still loads; a use fails loudly
             f = getattr(lib, name)
             f.restype, f.argtypes = res, args
@@ -1433,3 +1439,81 @@ def debug_miller(p0, q0, p1=None, q1=None, ctx: "Context | None" = None) -> np.n
                                    None if c is None else _ptr(c), None if g1 is None else _ptr(g1),
                                    a.shape[0], _ptr(out)), "plk_debug_miller")
     return out
+
+
+# plk_msm_snapshot of include/plk.h and the names of its header words
+MSM_SNAPSHOT_HDR = ("B", "W", "narrow", "c", "chunk", "rb", "fb", "NC", "NR", "G", "nbits", "nout",
+                    "wide", "sort_one", "hold", "task_stride", "sorted_stride", "max_tasks_used",
+                    "b_lo", "n_srs", "gen", "part", "parts", "has_inf")
+_MSM_SNAPSHOT_BUFS = ("offsets", "task_off", "sorted", "tasks", "partials", "bsum", "rsum", "ys",
+                      "zs", "bits", "readback")
+
+
+class _MsmSnapshot(C.Structure):
+    _fields_ = ([(n, C.c_uint32) for n in ("shared_chip", "tail_quad", "part", "parts",
+                                           "guard_limit", "reserved")] +
+                [("cap_sorted", C.c_uint64), ("cap_tasks", C.c_uint64)] +
+                [(n, C.c_void_p) for n in _MSM_SNAPSHOT_BUFS] +
+                [("hdr", C.c_uint64 * len(MSM_SNAPSHOT_HDR)), ("n_tasks", C.c_uint32 * 16)])
+
+
+def debug_msm_snapshot(pp: "PlonkParams", slots, shared_chip: bool = False, tail_quad: int = 1,
+                       part: int = 0, parts: int = 1, guard_limit: int = 0, points: bool = True):
+    """Test support (plk_debug_msm_snapshot): one fixed-base MSM batch over `slots` (1..16 arrays of
+    Montgomery scalars, uint64[len, 4]) on a workspace of its own, and what the batch left there.
+    Returns (hdr, per-slot dicts): hdr maps MSM_SNAPSHOT_HDR to integers; a slot holds offsets,
+    task_off (uint32[B + 1]), sorted (uint32[entries]), tasks (uint32[n, 2]), flag, entries,
+    max_count, bits (uint32[nout, 48]), point (uint64[13]), status, and with points=True partials
+    (uint32[n, 48]) and bsum (uint32[B, 48]) or rsum, ys, zs (uint32[B | NR, 48]). The batch runs
+    twice: once for the header that sizes the buffers, once for the buffers."""
+    arrs = [_as_fr_array(s) for s in slots]
+    k = len(arrs)
+    ptrs = (C.c_void_p * max(k, 1))(*[C.c_void_p(a.ctypes.data if a.shape[0] else None) for a in arrs])
+    lens = (C.c_size_t * max(k, 1))(*[a.shape[0] for a in arrs])
+    outs = np.zeros((max(k, 1), 13), dtype=np.uint64)
+    sts = (C.c_int * max(k, 1))()
+
+    def call(snap):
+        snap.shared_chip, snap.tail_quad = int(bool(shared_chip)), tail_quad
+        snap.part, snap.parts, snap.guard_limit = part, parts, guard_limit
+        st = _lib().plk_debug_msm_snapshot(pp._h, ptrs, lens, k, C.byref(snap), _ptr(outs), sts)
+        if st not in (PLK_OK, PLK_E_DEGREE):
+            raise PlonkError(st, "plk_debug_msm_snapshot")
+        return dict(zip(MSM_SNAPSHOT_HDR, (int(v) for v in snap.hdr)))
+
+    h = call(_MsmSnapshot())
+    B, NR, nout = h["B"], h["NR"], h["nout"]
+    cap_sorted = max(1, h["W"] * max(a.shape[0] for a in arrs))
+    cap_tasks = h["max_tasks_used"] + 1
+    u32 = np.uint32
+    bufs = {"offsets": np.zeros((k, B + 1), u32), "task_off": np.zeros((k, B + 1), u32),
+            "sorted": np.zeros((k, cap_sorted), u32), "tasks": np.zeros((k, cap_tasks, 2), u32),
+            "bits": np.zeros((k, nout, 48), u32), "readback": np.zeros((k, 3), u32)}
+    if points:
+        bufs["partials"] = np.zeros((k, cap_tasks, 48), u32)
+        if h["wide"]:
+            bufs.update(rsum=np.zeros((k, B, 48), u32), ys=np.zeros((k, NR, 48), u32),
+                        zs=np.zeros((k, NR, 48), u32))
+        else:
+            bufs["bsum"] = np.zeros((k, B, 48), u32)
+    snap = _MsmSnapshot()
+    snap.cap_sorted, snap.cap_tasks = cap_sorted, cap_tasks
+    for name, a in bufs.items():
+        setattr(snap, name, a.ctypes.data)
+    h2 = call(snap)
+    assert h2 == h, (h, h2)
+    out = []
+    for i in range(k):
+        n, ent = int(snap.n_tasks[i]), int(bufs["offsets"][i, B])
+        d = {"offsets": bufs["offsets"][i], "task_off": bufs["task_off"][i],
+             "sorted": bufs["sorted"][i, :ent], "tasks": bufs["tasks"][i, :n],
+             "bits": bufs["bits"][i], "flag": int(bufs["readback"][i, 0]),
+             "entries": int(bufs["readback"][i, 1]), "max_count": int(bufs["readback"][i, 2]),
+             "point": outs[i].copy(), "status": int(sts[i])}
+        if points:
+            d["partials"] = bufs["partials"][i, :n]
+            for name in ("bsum", "rsum", "ys", "zs"):
+                if name in bufs:
+                    d[name] = bufs[name][i]
+        out.append(d)
+    return h, out

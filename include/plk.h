@@ -1018,6 +1018,50 @@ int plk_debug_f12_op(plk_ctx* ctx, int op, const uint64_t* a, const uint64_t* b,
 int plk_debug_miller(plk_ctx* ctx, const plk_g1* p0, const plk_g2* q0, const plk_g1* p1,
                      const plk_g2* q1, size_t n, uint64_t* out);
 
+/* What one batch of the fixed-base MSM leaves in its workspace, stage by stage (test support). The
+ * call makes a workspace of its own, sets its accumulation form (shared_chip: the prover lanes'
+ * grouped k_accumulate instead of the lone form) and the reduction trees' form (tail_quad 0 / 1 /
+ * 2, as PLK_TAIL_QUAD), runs the library's own batch on `count` <= 16 slots of host scalars
+ * exactly as plk_commit_batch_dev_part does (slot k: lens[k] Montgomery scalars, the first
+ * min(lens[k], SRS length) of them committed, the rest required to be zero), and copies the
+ * workspace out. No kernel and no launch differs from plk_commit_batch_dev_part's.
+ *
+ * hdr (PLK_MSM_SNAPSHOT_HDR words): B W narrow c chunk rb fb NC NR G nbits nout wide sort_one hold
+ * task_stride sorted_stride max_tasks_used b_lo n_srs gen part parts has_inf — the bucket count of
+ * the call (a part's range for parts > 1), the window count and the number of narrow top windows,
+ * the window size, the task length, the run, fine-bin, coarse-bin and group figures of the
+ * reduction, the number of bit sums (nbits) and of readback rows (nout), which sort ran, the
+ * workspace strides, the bound on a slot's tasks, the part's first bucket, the SRS length, and the
+ * batch's generation number (a degree-check flag equal to it is set).
+ *
+ * Per slot k, each buffer optional (NULL: not copied); 32-bit words:
+ *   offsets, task_off   [k (B + 1) ..]: B + 1 words each
+ *   sorted              [k cap_sorted ..]: the offsets[B] entry codes, w n_srs + i | sign << 31
+ *   tasks               [2 k cap_tasks ..]: n_tasks[k] = task_off[B] records {first entry, partial
+ *                       index | (length - 1) << 26}: full tasks in bucket order, then tails grouped
+ *                       by length, longest first
+ *   partials            [48 k cap_tasks ..]: n_tasks[k] packed R'-domain XYZZ rows of 48 words
+ *   bsum                [48 k B ..]: B rows (narrow bucket sets, B <= 32768; untouched otherwise)
+ *   rsum                [48 k B ..]: B rows; ys, zs [48 k NR ..]: NR rows (wide sets only)
+ *   bits                [48 k nout ..]: the nout readback rows T_j
+ *   readback            [3 k ..]: flag, entries, max_count (max_count only with guard_limit)
+ * then outs[k] and statuses[k] as plk_commit_batch_dev_part gives them.
+ * PLK_E_ARG: a NULL srs / lens / hdr / outs / statuses, count = 0 or > 16, a slot with scalars NULL
+ * and a length, tail_quad outside 0..2, parts the SRS does not take, a sorted or tasks capacity
+ * too small for a slot (nothing is written past a capacity). Otherwise the batch's status:
+ * PLK_OK, or PLK_E_DEGREE when a slot failed its degree check (the buffers are still filled). */
+#define PLK_MSM_SNAPSHOT_HDR 24
+typedef struct plk_msm_snapshot {
+  uint32_t shared_chip, tail_quad, part, parts, guard_limit, reserved;
+  uint64_t cap_sorted, cap_tasks; /* per-slot capacities: entries, task records */
+  uint32_t *offsets, *task_off, *sorted, *tasks, *partials, *bsum, *rsum, *ys, *zs, *bits;
+  uint32_t* readback;
+  uint64_t hdr[PLK_MSM_SNAPSHOT_HDR];
+  uint32_t n_tasks[16];
+} plk_msm_snapshot;
+int plk_debug_msm_snapshot(plk_srs* s, const plk_fr* const* scalars, const size_t* lens,
+                           size_t count, plk_msm_snapshot* snap, plk_g1* outs, int* statuses);
+
 #ifdef __cplusplus
 }
 #endif
