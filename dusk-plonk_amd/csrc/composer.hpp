@@ -6,9 +6,6 @@
 
 #include "internal.hpp"
 
-// a function shared by translation units of the library and not part of what it exports
-#define PLK_LOCAL __attribute__((visibility("hidden")))
-
 namespace plk {
 
 PLK_LOCAL inline Fr fr_u64(uint64_t v) {

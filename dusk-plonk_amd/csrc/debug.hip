@@ -717,7 +717,7 @@ extern "C" int plk_debug_prover_round3(plk_prover* p, uint64_t* out, size_t out_
 
 // One batch of the fixed-base MSM on a workspace of this call's own, then the workspace's buffers
 // as the batch left them (include/plk.h). msm_run_batch is the library's, unchanged: it reports
-// what it derived in MsmWorkspace::last.
+// the batch's plan in MsmWorkspace::last.
 extern "C" int plk_debug_msm_snapshot(plk_srs* s, const plk_fr* const* scalars, const size_t* lens,
                                       size_t count, plk_msm_snapshot* snap, plk_g1* outs,
                                       int* statuses) {
@@ -752,7 +752,7 @@ extern "C" int plk_debug_msm_snapshot(plk_srs* s, const plk_fr* const* scalars, 
     r = msm_run_batch(s, w, ptrs, use, chk, count, outs, statuses, st, snap->part, snap->parts,
                       snap->guard_limit);
     if (r != PLK_OK && r != PLK_E_DEGREE) return r;
-    const MsmDerived& d = w.last;
+    const MsmPlan& d = w.last;
     const uint64_t hdr[PLK_MSM_SNAPSHOT_HDR] = {
         d.B, d.W, d.narrow, d.c, d.chunk, d.rb, d.fb, d.NC, d.NR, d.G, d.nbits, d.nout, d.wide,
         d.sort_one, d.hold, w.task_stride, w.sorted_stride, d.max_tasks_used, d.b_lo, s->n, d.gen,

@@ -37,6 +37,9 @@ namespace plk {
 
 hipError_t& last_hip_error();
 
+// a function shared by translation units of the library and not part of what it exports
+#define PLK_LOCAL __attribute__((visibility("hidden")))
+
 // blocks of b threads for a items
 inline uint32_t cdiv(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
 
@@ -188,7 +191,7 @@ struct plk_srs {
   uint32_t windows = 16;     // ceil(256 / c)
   // balanced windows (round 5): when c does not divide 255, the top `narrow` windows are
   // c - 1 bits wide (narrow = c W - 255) and their digits come scaled by 2, their table rows
-  // pre-divided by 2 (msm_prepare_srs, msm.hip digit_at): every window spreads over the whole
+  // pre-divided by 2 (msm_prepare_srs, msm_digits.hpp digit_at): every window spreads over the whole
   // bucket range, without the short top window whose few digit values piled extra entries
   // onto a few hot buckets
   uint32_t narrow = 0;
@@ -353,7 +356,7 @@ int msm_run(plk_srs* s, const Fr* d_scalars, size_t len, size_t check_len, plk_g
 // parts' outputs sum to the whole MSM's (one large MSM split over GPUs by bucket
 // range, each GPU's reduction over its own buckets only).
 // guard_limit > 0: a slot whose largest bucket holds more than guard_limit entries is not
-// accumulated or reduced (msm.hip k_guard); info[k].hot reports it and outs[k] is void. info
+// accumulated or reduced (msm_sort.hip k_guard); info[k].hot reports it and outs[k] is void. info
 // (optional, `count` records): each slot's entry count and, for a guarded batch, its largest
 // bucket count.
 struct MsmSlotInfo {

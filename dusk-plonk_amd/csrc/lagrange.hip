@@ -3,7 +3,7 @@
 // A polynomial given by its values v_i = w(omega^i) commits to sum_i v_i [L_i(tau)]_1, and
 //   P_i = [L_i(tau)]_1 = n^-1 sum_j omega^(-ij) [tau^j]_1,
 // the inverse DFT of the first n SRS points taken over G1. A column that is zero (or sparse) in
-// the evaluation basis then costs the MSM nothing (msm.hip emits no entry for a zero digit),
+// the evaluation basis then costs the MSM nothing (msm_sort.hip emits no entry for a zero digit),
 // where its n dense coefficients cost a full MSM. Three more points carry a blinder
 // b(X)(X^n - 1), b of degree <= 2, in the same MSM:
 //   Z_t = [tau^(n+t)]_1 - [tau^t]_1  (t < 3),   commit = sum_i v_i P_i + sum_t b_t Z_t

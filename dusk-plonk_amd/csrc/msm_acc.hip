@@ -1,6 +1,7 @@
 // msm_acc.hip — the MSM's bucket accumulation (k_accumulate), the dominant kernel of a
-// proof (≈ 56 % of a 2^20 proof's GPU time). Its own translation unit: msm.hip's sort and
-// reduction kernels take minutes to compile, and this kernel is the one tuned most often.
+// proof (≈ 56 % of a 2^20 proof's GPU time). Its own translation unit, like the sort (msm_sort.hip)
+// and the reduction (msm_reduce.hip, the one that takes minutes to compile): this kernel is the
+// one tuned most often. The driver and the design are in msm.hip.
 //
 // One thread per task of <= 64 same-bucket entries of the sorted digit list (full tasks
 // first, tails grouped by length, longest first: the lanes of a wave finish together),
@@ -79,8 +80,8 @@ __global__ void __launch_bounds__(kAccThreads)
   const uint32_t lane = threadIdx.x & 63;
   if (t >= task_off[(size_t)slot * (B + 1) + B]) return;
   const uint2 tk = tasks[(size_t)slot * task_stride + t];
-  const uint2 task = make_uint2(tk.x, (tk.y >> kTaskShift) + 1);  // first entry, length (>= 1)
-  const uint32_t pidx = tk.y & ((1u << kTaskShift) - 1);
+  const uint2 task = make_uint2(tk.x, task_len(tk));  // first entry, length (>= 1)
+  const uint32_t pidx = task_partial(tk);
   sorted += (size_t)slot * sorted_stride;
   // The first entry initialises the accumulator; exceptional additions (accumulator at
   // infinity, equal x) show up as ZZ3 == 0 after the straight-line formula and are
@@ -89,9 +90,9 @@ __global__ void __launch_bounds__(kAccThreads)
   G1R acc = g1r_infinity();
   {
     const uint32_t c0 = sorted[task.x];
-    if (!HAS_INF || !table_inf[c0 & 0x7fffffffu]) {
-      ld_g1r_aff(&table[c0 & 0x7fffffffu], acc.X, acc.Y);
-      if (c0 & 0x80000000u) acc.Y = rx_neg(acc.Y);
+    if (!HAS_INF || !table_inf[entry_row(c0)]) {
+      ld_g1r_aff(&table[entry_row(c0)], acc.X, acc.Y);
+      if (entry_neg(c0)) acc.Y = rx_neg(acc.Y);
       acc.ZZ = rx_one<FpCfg>();
       acc.ZZZ = rx_one<FpCfg>();
     }
@@ -102,8 +103,8 @@ __global__ void __launch_bounds__(kAccThreads)
   // with the index so that no ordinary load result is consumed while a DMA is in flight
   // (hipcc would wait vmcnt(0) there and drain it)
   uint32_t code = task.x + 1 < end ? sorted[task.x + 1] : 0u;
-  bool inf = HAS_INF && task.x + 1 < end && table_inf[code & 0x7fffffffu];
-  if (task.x + 1 < end) stage_point(&table[code & 0x7fffffffu], stage);
+  bool inf = HAS_INF && task.x + 1 < end && table_inf[entry_row(code)];
+  if (task.x + 1 < end) stage_point(&table[entry_row(code)], stage);
   uint32_t next = task.x + 2 < end ? sorted[task.x + 2] : 0u;
   for (uint32_t e = task.x + 1; e < end; ++e) {
     const uint32_t cur = code;
@@ -114,18 +115,18 @@ __global__ void __launch_bounds__(kAccThreads)
     __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     if (e + 1 < end) {
       code = next;
-      if (HAS_INF) inf = table_inf[code & 0x7fffffffu];
-      stage_point(&table[code & 0x7fffffffu], stage);
+      if (HAS_INF) inf = table_inf[entry_row(code)];
+      stage_point(&table[entry_row(code)], stage);
       if (e + 2 < end) next = sorted[e + 2];
     }
     if (HAS_INF && cur_inf) continue;
-    if (cur & 0x80000000u) y = rx_neg_lazy(y);
+    if (entry_neg(cur)) y = rx_neg_lazy(y);
     const bool was_inf = g1r_is_inf(acc);
     G1R r = g1r_madd_lazy_sl<true, true, LONE>(acc, x, y);
     if (rx_is_zero(r.ZZ)) {  // rare: reload the point rather than keep it live
       RFp xr, yr;
-      ld_g1r_aff(&table[cur & 0x7fffffffu], xr, yr);
-      if (cur & 0x80000000u) yr = rx_neg(yr);
+      ld_g1r_aff(&table[entry_row(cur)], xr, yr);
+      if (entry_neg(cur)) yr = rx_neg(yr);
       r = g1r_madd_lazy_fix(was_inf, r, xr, yr);
     }
     acc = r;

@@ -1,5 +1,8 @@
-// msm_common.hpp — device load/store helpers and the per-SRS MSM workspace.
+// msm_common.hpp — what the MSM's translation units share: device load/store helpers, the
+// sort / accumulate contract, the shape constants and the batch plan, the per-SRS workspace
+// and the stage launchers (msm_sort.hip, msm_acc.hip, msm_reduce.hip) the driver (msm.hip) calls.
 #pragma once
+#include <algorithm>
 #include <cstdlib>
 
 #include "ffr.hpp"
@@ -25,6 +28,20 @@ constexpr uint32_t kChunkMax = PLK_CHUNK_MAX;
 // task record .y = partial index | (length - 1) << kTaskShift
 constexpr uint32_t kTaskShift = 32 - (kChunkMax <= 64 ? 6 : 7);
 static_assert(kChunkMax <= 128, "task length field");
+// The contract between the sorts (msm_sort.hip, msm_var.hip) and k_accumulate (msm_acc.hip),
+// stated once. An entry of the sorted digit list is a table row with the digit's sign on top;
+// a task is {first entry, partial index | (length - 1) << kTaskShift}: 1 .. kChunkMax
+// same-bucket entries whose sum goes to partials[partial index] (< kTaskIndexEnd).
+constexpr uint32_t kEntryNeg = 0x80000000u;  // the entry's point is subtracted
+constexpr uint32_t kTaskIndexEnd = 1u << kTaskShift;
+__device__ __forceinline__ uint32_t entry_code(uint32_t row, bool neg) { return row | (neg ? kEntryNeg : 0u); }
+__device__ __forceinline__ uint32_t entry_row(uint32_t code) { return code & ~kEntryNeg; }
+__device__ __forceinline__ bool entry_neg(uint32_t code) { return code & kEntryNeg; }
+__device__ __forceinline__ uint2 task_record(uint32_t first, uint32_t partial, uint32_t len) {
+  return make_uint2(first, partial | ((len - 1) << kTaskShift));
+}
+__device__ __forceinline__ uint32_t task_len(const uint2& t) { return (t.y >> kTaskShift) + 1; }
+__device__ __forceinline__ uint32_t task_partial(const uint2& t) { return t.y & (kTaskIndexEnd - 1); }
 constexpr uint32_t kBatchAff = 32;  // points per batch-inversion chunk
 constexpr uint32_t kMaxSlots = 16;  // independent MSMs per batch
 
@@ -99,18 +116,113 @@ struct ReadbackHeader {
 };
 static_assert(sizeof(ReadbackHeader) % 16 == 0, "alignment of the bit sums");
 
-// What msm_run_batch derived for its most recent batch on a workspace (MsmWorkspace::last), for
-// plk_debug_msm_snapshot (debug.hip): the host's report only, no kernel reads it.
-struct MsmDerived {
-  uint32_t B = 0, W = 0, narrow = 0, c = 0, chunk = 0, rb = 0, fb = 0, NC = 0, NR = 0, G = 0;
-  uint32_t nbits = 0, nout = 0, wide = 0, sort_one = 0, hold = 0, b_lo = 0, gen = 0;
-  uint64_t max_tasks_used = 0;
+// ---- the constants the plan (msm.hip) and the kernels (msm_sort.hip, msm_reduce.hip) share
+#ifndef PLK_LANE_PARTIALS
+#define PLK_LANE_PARTIALS 4  // bucket partials per k_bucket_sum lane aimed at (only c <= 15, SRS < 2^16: 8 -> 4 gave 2^12 3.74 -> 3.93 M constraints/s, tools/gpu_ab_quick.sh)
+#endif
+#ifndef PLK_CHUNK_TARGET
+#define PLK_CHUNK_TARGET 262144  // accumulation tasks aimed at per batch (chunk = entries / this)
+#endif
+constexpr uint32_t kHistBlocksMax = 256;  // histogram / scatter workgroups per slot
+// LDS histograms cover at most kLdsBuckets buckets (128 KiB); larger bucket sets (c = 17)
+// are processed in bucket windows, each a fresh pass over the workgroup's scalars.
+constexpr uint32_t kLdsBuckets = 32768;
+// small bucket sets (the 2^12-size commits, c <= 13): k_sort_small / k_sort_one hold the
+// bucket counts in LDS (msm_sort.hip)
+constexpr uint32_t kSortSmallMax = 4096;
+constexpr uint32_t kSortOneMax = 8192;  // scalars per slot held in registers
+// workgroups per slot, each taking 1/kSortOneParts of the buckets (round 5, three interleaved
+// runs against one workgroup, profiles/r05_sort_one_parts_ab.jsonl: lone 2^12 MSM 0.394 ->
+// 0.347 ms, 2^12 proofs 8.81 -> 9.10 M, 2^13 within noise; 8 workgroups the same as 4)
+constexpr uint32_t kSortOneParts = 4;
+// HOLD: the slot's scalars (<= kSortOneMax) stay in registers between the histogram and the
+// scatter; otherwise (<= kSortOneBig, the 2^14-size commits at c = 13) both passes read them
+// from memory, 4 ahead per thread (for_scalars)
+constexpr uint32_t kSortOneBig = 32768;
+constexpr uint32_t kFineBits = 10;  // 2^10 buckets per coarse bin = threads of k_fine
+// A bucket-range part (parts > 1) of 2^(c-1) / parts buckets keeps >= 256 coarse bins (k_fine
+// / k_make_tasks_wide workgroups) with bins of 2^FB buckets, FB = max(8, 10 - log2 parts)
+constexpr uint32_t kFineBitsMin = 8;
+constexpr uint32_t kCoarseMax = 4096;        // coarse bins (B <= 2^22, c <= 23)
+// bucket reduction: runs of K = 2^rb buckets per lane. Batches of several MSMs (the
+// prover's commit groups, with other proofs' kernels beside them) take 16. A lone MSM's
+// run-sum chains are latency-bound with the chip otherwise idle, so its rb is the largest
+// rb <= kRunBits that still gives kRunLanes run lanes: K = 8 at 2^20, 2 at 2^16 (lone
+// 2^16 MSM 1.14 -> 1.01 ms in round 2). Applied to batches too it cost the 2^16 proof
+// 22 -> 18 M constraints/s (more bit-sum groups, NR / 256, in every commit group).
+constexpr uint32_t kRunBits = 4, kRunBitsMin = 1;
+// run lanes aimed at: 65536 (one wave per SIMD) — with the 4-lane k_bitsum1 a lone 2^20
+// MSM then runs rb = 3, 256 bit-sum groups: 3.44 -> 3.34 ms (131072: rb = 2, 512 groups)
+constexpr size_t kRunLanes = 65536;
+constexpr uint32_t kBitsumOut = 10;  // k_bitsum1's records per group of 256 (msm_reduce.hip)
+// k_bitsum1 folds k_bitsum2 in when a slot has at most this many bit-sum groups (msm_reduce.hip)
+constexpr uint32_t kFoldMaxGroups = 16;
+// kRunLanes, or PLK_RUN_LANES from the environment (sweeps)
+PLK_LOCAL inline size_t run_lanes() {
+  static const size_t v = [] {
+    const char* e = getenv("PLK_RUN_LANES");
+    const long long x = e ? atoll(e) : 0;
+    return x > 0 ? (size_t)x : kRunLanes;
+  }();
+  return v;
+}
+// a batch's rb: kRunBits, or PLK_RUN_BITS_BATCH from the environment (sweeps; 1 .. 8)
+PLK_LOCAL inline uint32_t batch_run_bits() {
+  static const uint32_t v = [] {
+    const char* e = getenv("PLK_RUN_BITS_BATCH");
+    const int x = e ? atoi(e) : 0;
+    return x >= 1 && x <= 8 ? (uint32_t)x : kRunBits;
+  }();
+  return v;
+}
+PLK_LOCAL inline uint32_t run_bits(uint32_t B, uint32_t slots) {
+  if (slots > 1) return std::min<uint32_t>(batch_run_bits(), 31 - __builtin_clz(B));
+  uint32_t rb = kRunBits;
+  while (rb > kRunBitsMin && (size_t)(B >> rb) < run_lanes()) --rb;
+  return rb;
+}
+// wide bucket sets (2^(c-1) > kLdsBuckets, c >= 17): two-level sort and run-sum reduction
+PLK_LOCAL inline bool is_wide(uint32_t c) { return (1u << (c - 1)) > kLdsBuckets; }
+// small shapes (the 2^12-size proofs' commits: k_sort_one with the scalars held in registers)
+// may run tasks of kChunkSmall points; ws_reserve sizes the task buffers for them
+PLK_LOCAL inline bool is_small_shape(uint32_t c, size_t len) {
+  return !is_wide(c) && (1u << (c - 1)) <= kSortSmallMax && len <= kSortOneMax;
+}
+
+// Everything one batch's launches follow from, derived once by msm_plan (msm.hip) from the SRS
+// shape, the slots' lengths, part / parts and the workspace's policy, before any kernel runs.
+// msm_sort, launch_accumulate and msm_reduce read it, and MsmWorkspace::last keeps the most
+// recent one for plk_debug_msm_snapshot (debug.hip).
+struct MsmPlan {
+  uint32_t slots = 0, part = 0, parts = 1;
+  uint32_t c = 0, W = 0, narrow = 0;  // the SRS's windows (plk_srs)
+  uint64_t n_srs = 0;
+  bool has_inf = false;
+  uint32_t B = 0, b_lo = 0;  // the buckets this call reduces: all 2^(c-1), or a part's range
+  bool wide = false;         // is_wide(c)
+  size_t max_len = 0, max_tail = 0, total_entries = 0;  // over the slots
+  bool sort_one = false, hold = false;  // k_sort_one, with the scalars held in registers
+  bool small_sort = false;              // k_sort_small after k_hist (B <= kSortSmallMax)
+  uint32_t hist_blocks = 0;             // histogram / scatter workgroups per slot
+  uint32_t fb = 0, NC = 0;              // wide sets: bins of 2^fb buckets, NC of them
+  uint32_t chunk = 0;                   // points per accumulation task
+  uint64_t max_tasks_used = 0;          // bound on a slot's tasks
+  uint32_t acc_blocks = 0;              // k_accumulate's grid.x (256 task lanes each)
+  bool lone = false;                    // k_accumulate's LONE form (!shared_chip)
+  uint32_t rb = 0, NR = 0;              // runs of 2^rb buckets, NR of them per slot
+  uint32_t lp = 0;                      // narrow sets: 2^lp k_bucket_sum lanes per bucket
+  uint32_t G = 0, nbits = 0, nout = 0;  // bit-sum groups (a power of two), T_j count, outputs
+  bool fold = false;                    // k_bitsum2 folded into k_bitsum1 (G <= kFoldMaxGroups)
+  int tail_quad = 0;                    // MsmWorkspace::tail_quad
+  uint32_t guard_limit = 0;             // hot-bucket guard (k_guard), 0: off
+  uint32_t gen = 0;                     // the batch's generation stamp (set by msm_run_batch)
+  MsmCfg cfg() const { return MsmCfg{c, W, B, narrow, b_lo}; }
 };
 
 struct MsmWorkspace {
-  MsmDerived last;
+  MsmPlan last;
   DevBuf counts, blockhist, offsets, task_off, full_off, len_cur, sorted, tasks, partials, bsum, bits1;
-  // wide bucket sets only (msm.hip: two-level sort, run-sum reduction)
+  // wide bucket sets only (msm_sort.hip: two-level sort; msm_reduce.hip: run-sum reduction)
   DevBuf tmp, task_rel, bin_tot, len_fill, coarse_off, rsum, ys, zs;
   DevBuf done;  // k_bitsum1's per-slot arrival counters (its fold of k_bitsum2)
   DevBuf guard;  // k_guard's per-slot running maxima and arrival counters (2 kMaxSlots words)
@@ -192,6 +304,16 @@ PLK_HD Fp fp_rx_to_r(const Fp& x) {
   k.v[11] = 1u << (32 - SH);  // 2^(384 - SH) (< p)
   return fe_mul(x, k);
 }
+
+// The batch's sort (msm_sort.hip): the commit degree check, the path the plan chose (one
+// dispatch, LDS histogram or two-level wide) and the hot-bucket guard, leaving offsets, sorted,
+// task_off and tasks in the workspace. The launches only, stream-ordered.
+PLK_LOCAL int msm_sort(const MsmPlan& p, const MsmBatch& batch, MsmWorkspace& w, hipStream_t stream);
+// The sort kernels' dynamic-LDS limits for window size c, once per workspace shape (ws_reserve)
+PLK_LOCAL int msm_sort_prepare(uint32_t c);
+// The batch's bucket reduction (msm_reduce.hip): bucket sums or run sums, then the bit sums and
+// the entry counts into the workspace's readback record. The launches only, stream-ordered.
+PLK_LOCAL void msm_reduce(const MsmPlan& p, MsmWorkspace& w, hipStream_t stream);
 
 // k_accumulate (msm_acc.hip) over grid.x * 256 task lanes per slot (grid.y = slots), stamped
 // with the start / stop events ev0 / ev1 by the dispatch itself

@@ -68,7 +68,7 @@ __global__ void __launch_bounds__(256) k_var_prepare(const plk_g1* __restrict__ 
   inf[i] = keep ? 0 : 1;
 }
 
-// Canonical scalar in [0, (r-1)/2]: s, or r - s with the digit signs flipped (msm.hip
+// Canonical scalar in [0, (r-1)/2]: s, or r - s with the digit signs flipped (msm_digits.hpp
 // scalar_half_v: the same recoding, s < 2^254 needs W = ceil(255 / c) windows)
 __device__ __forceinline__ Fr var_scalar_half(const Fr& raw, bool& neg) {
   const Fr s = fe_from_mont(raw);
@@ -85,7 +85,7 @@ __device__ __forceinline__ Fr var_scalar_half(const Fr& raw, bool& neg) {
   return lt ? t : s;
 }
 
-// f(w, d) for the W signed c-bit digits of s (msm.hip each_digit's recoding with plain c-bit
+// f(w, d) for the W signed c-bit digits of s (msm_digits.hpp each_digit's recoding with plain c-bit
 // windows: d in [-2^(c-1) + 1, 2^(c-1)], the carry threaded upwards). The scalar is shifted
 // down by c bits per window, so no word of it is indexed at run time (no scratch).
 template <class F>
@@ -131,7 +131,7 @@ __global__ void __launch_bounds__(256) k_var_count(VarBatch batch, const Fr* __r
 
 // One workgroup per output: offsets[b] = entries before bucket b (offsets[NB] = all), cursor = a
 // copy for the scatter, task_off[b] = tasks before bucket b, and the task records of
-// k_accumulate (msm_acc.hip): .x = first entry, .y = partial index | (length - 1) << kTaskShift,
+// k_accumulate (msm_acc.hip): task_record(first entry, partial index, length) of msm_common.hpp,
 // bucket b's tasks at task_off[b] .. task_off[b + 1], each of <= chunk entries.
 __global__ void __launch_bounds__(1024) k_var_scan(const uint32_t* __restrict__ counts, uint32_t NB,
                                                    uint32_t chunk, uint32_t* __restrict__ offsets,
@@ -171,7 +171,7 @@ __global__ void __launch_bounds__(1024) k_var_scan(const uint32_t* __restrict__ 
     task_off[b] = to;
     for (uint32_t done = 0; done < n; done += chunk) {
       const uint32_t len = min(chunk, n - done);
-      if (to < task_stride) tasks[to] = make_uint2(eo + done, to | ((len - 1) << kTaskShift));
+      if (to < task_stride) tasks[to] = task_record(eo + done, to, len);
       ++to;
     }
     eo += n;
@@ -203,7 +203,7 @@ __global__ void __launch_bounds__(256) k_var_scatter(VarBatch batch, const Fr* _
     const uint32_t a = (uint32_t)(d < 0 ? -d : d);
     const uint32_t pos = atomicAdd(&cur[w * Bw + a - 1], 1u);
     // the same digits as k_var_count counted, so pos stays inside the bucket's range
-    if (pos < sorted_stride) out[pos] = i | (((d < 0) != neg) ? 0x80000000u : 0u);
+    if (pos < sorted_stride) out[pos] = entry_code(i, (d < 0) != neg);
   });
 }
 
@@ -308,7 +308,7 @@ int msm_var_run(plk_ctx* ctx, const plk_g1* d_points, const Fr* d_scalars, size_
   if (E >= (1ull << 31)) return PLK_E_ARG;
   const uint32_t chunk = E < (1u << 20) ? kChunkMin : kChunkMax;
   const size_t task_stride = std::min<size_t>(E, E / chunk + NB) + 1;
-  if (task_stride >= (1ull << kTaskShift)) return PLK_E_ARG;
+  if (task_stride >= kTaskIndexEnd) return PLK_E_ARG;
   int st;
   if ((st = w.pts.alloc(n * sizeof(G1Affine)))) return st;
   if ((st = w.inf.alloc(n))) return st;

@@ -102,7 +102,7 @@ static uint32_t choose_c(size_t n) {
   }
   // 2^20 points and up: c = 20, 13 windows (16 at c = 16). Entries N * W fall 19 %; the
   // 2^19 buckets (~26 entries each) go through the wide-set sort and the run-sum
-  // reduction (msm.hip), ~2.2 additions per bucket. Per MSM: N * ceil(255 / c) mixed
+  // reduction (msm_reduce.hip), ~2.2 additions per bucket. Per MSM: N * ceil(255 / c) mixed
   // additions + ~2.2 * 2^(c-1) full ones is smallest at c = 20 for N = 2^20.
 #ifndef PLK_C_HUGE
 #define PLK_C_HUGE 20
@@ -153,7 +153,7 @@ int msm_prepare_srs(plk_srs* s, hipStream_t stream, uint32_t force_c, bool own_w
   if (!force_c && (s->c - 1) * ((255 + s->c - 1) / s->c) == 255) s->c -= 1;
   s->windows = (255 + s->c - 1) / s->c;  // scalars recoded from [0, (r-1)/2] (< 2^254)
   // balanced windows (round 5): the W windows cover exactly 255 bits, the top `narrow` = c W -
-  // 255 of them c - 1 bits wide with digits scaled by 2 (msm.hip digit_at) and table rows
+  // 255 of them c - 1 bits wide with digits scaled by 2 (msm_digits.hpp digit_at) and table rows
   // pre-divided by 2, so every window spreads over all 2^(c-1) buckets: even buckets hold the
   // wide windows' entries, odd ones also the narrow windows' (c = 20: 8 x 20 + 5 x 19 bits,
   // 16 / 36 entries per 2^20 scalars, every run of >= 2 buckets the same load). Round 4's

@@ -350,7 +350,7 @@ def window_bits(n_points: int) -> int:
 
 def bucket_parts_ok(n_points: int, parts: int) -> bool:
     """Whether plk_commit_batch_dev_part accepts `parts` bucket ranges on an SRS of n_points
-    (msm.hip msm_commit_batch_part): a power of two, a wide bucket set (2^(c-1) above the
+    (msm.hip msm_parts_ok): a power of two, a wide bucket set (2^(c-1) above the
     32 K LDS buckets, c >= 17) and >= 2^14 buckets per part."""
     c = window_bits(n_points)
     return (parts >= 1 and parts & (parts - 1) == 0

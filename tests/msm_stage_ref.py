@@ -1,4 +1,4 @@
-"""Integer model of the fixed-base MSM pipeline (csrc/msm.hip, csrc/msm_acc.hip), stage by stage,
+"""Integer model of the fixed-base MSM pipeline (csrc/msm.hip, msm_sort.hip, msm_acc.hip, msm_reduce.hip), stage by stage,
 for the snapshots of plk_debug_msm_snapshot (tests/test_msm_stage_gpu.py) and its own CPU test
 (tests/test_msm_stage_ref_cpu.py).
 
@@ -48,7 +48,7 @@ import rx_ref
 
 R = P.R_MOD
 HALF = (R - 1) // 2
-TASK_SHIFT = 26            # msm_common.hpp kTaskShift (kChunkMax <= 64)
+TASK_SHIFT = 26            # msm_common.hpp kTaskShift, task_record() (kChunkMax <= 64)
 SIGN = 0x80000000
 INV2 = pow(2, -1, R)
 

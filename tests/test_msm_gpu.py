@@ -57,7 +57,7 @@ def test_msm_vs_oracle(plk, gpu_ctx, oracle, logn):
     pp = plk.PlonkParams.setup(logn, tau, gpu_ctx, n_points=n + 8)
     pts = pp.points()
     # logn = 16, 18: c = 17 (15 windows, 2^16 buckets: the wide-set sort and run-sum
-    # reduction of msm.hip); below 2^16 the LDS-histogram path (srs.hip choose_c)
+    # reduction of msm_sort.hip / msm_reduce.hip); below 2^16 the LDS-histogram path (srs.hip choose_c)
     if logn <= 12:  # the SRS itself against the oracle's setup
         assert np.array_equal(pts, oracle.srs(tau, n + 8))
     sc = random_fr(n, seed=1000 + logn)
@@ -69,7 +69,7 @@ def test_msm_vs_oracle(plk, gpu_ctx, oracle, logn):
         "tiny": P.fr_vec_to_np([i % 5 for i in range(n)]),
         "sparse": np.where((np.arange(n) % 17 == 0)[:, None], sc, 0).astype(np.uint64),
         "minus_one": np.tile(fr_int(P.R_MOD - 1), (n, 1)),
-        # around the half-range recoding boundary (msm.hip scalar_half: s > (r-1)/2 -> r - s)
+        # around the half-range recoding boundary (msm_digits.hpp scalar_half: s > (r-1)/2 -> r - s)
         "half_boundary": P.fr_vec_to_np([
             [(P.R_MOD - 1) // 2, (P.R_MOD + 1) // 2, (P.R_MOD - 1) // 2 - 1, (P.R_MOD + 3) // 2,
              1 << 253, P.R_MOD - (1 << 253), (1 << 254) - 1, P.R_MOD - 2][i % 8] for i in range(n)]),
@@ -201,7 +201,7 @@ def test_commit_batch_dev(plk, gpu_ctx, oracle):
 @pytest.mark.parametrize("c,logn", [(17, 10), (20, 12), (18, 14), (19, 14), (20, 16)])
 def test_msm_wide_buckets_vs_oracle(plk, gpu_ctx, oracle, monkeypatch, c, logn):
     """Wide bucket sets (2^(c-1) > 32 K buckets: the two-level radix sort, the per-bin
-    counting sort and the run-sum bucket reduction of msm.hip) at small sizes, forced with
+    counting sort and the run-sum bucket reduction of msm_sort.hip / msm_reduce.hip) at small sizes, forced with
     PLK_MSM_C: most buckets empty or single, skewed and adversarial scalar sets, batches."""
     import torch
     monkeypatch.setenv("PLK_MSM_C", str(c))
@@ -286,7 +286,7 @@ def test_msm_wide_buckets_repeated_points(plk, gpu_ctx, oracle, monkeypatch, tau
 @pytest.mark.parametrize("quad", ["0", "1", "2"])
 @pytest.mark.parametrize("c,logn", [(None, 10), (None, 12), (17, 10), (20, 12)])
 def test_msm_tail_forms(plk, gpu_ctx, oracle, monkeypatch, quad, c, logn):
-    """The forms of the reduction trees (k_bucket_sum / k_bitsum1 / k_bitsum2, msm.hip):
+    """The forms of the reduction trees (k_bucket_sum / k_bitsum1 / k_bitsum2, msm_reduce.hip):
     one lane per addition, the quad-cooperative g1r_add_quad, and quads in k_bitsum2 only
     (PLK_TAIL_QUAD = 0 / 1 / 2),
     on the narrow (default c) and wide (forced c) bucket paths. tau = 1 makes every SRS point

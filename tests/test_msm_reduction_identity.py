@@ -1,4 +1,4 @@
-"""CPU check of the bucket-reduction identities the MSM kernels rely on (msm.hip), with
+"""CPU check of the bucket-reduction identities the MSM kernels rely on (msm_reduce.hip, msm_digits.hpp), with
 integers standing in for the bucket sums (the identities are linear, so any abelian group
 behaves the same):
 
@@ -8,7 +8,7 @@ behaves the same):
 * bit-sum form (k_bitsum1/2): sum_u (u+1) S_u = sum_j 2^j T_j with b = 256 g + 16 a + c,
   T_j(g) from row / column sums and the group term (256 g + 1) A_g spread over T_(8+i);
 * the top-window-free recoding: signed c-bit digits of a scalar below 2^254 reconstruct it
-  with W = ceil(255 / c) windows and never exceed 2^(c-1) (msm.hip digit_at).
+  with W = ceil(255 / c) windows and never exceed 2^(c-1) (msm_digits.hpp digit_at).
 """
 import random
 
@@ -61,7 +61,7 @@ def test_bitsum_identity(B):
 
 
 def digits(s, c, W):
-    """msm.hip digit_at over all windows (carry threaded)."""
+    """msm_digits.hpp digit_at over all windows (carry threaded)."""
     out, carry = [], 0
     for w in range(W):
         val = (s >> (w * c)) & ((1 << c) - 1) if w * c < 256 else 0
@@ -88,7 +88,7 @@ def test_signed_recoding(c):
 
 
 def run_bits_lone(B, run_lanes=65536, kmax=4, kmin=1):
-    """msm.hip run_bits for a lone MSM: the largest rb <= 4 with B >> rb >= 2^16 run lanes."""
+    """msm_common.hpp run_bits for a lone MSM: the largest rb <= 4 with B >> rb >= 2^16 run lanes."""
     rb = kmax
     while rb > kmin and (B >> rb) < run_lanes:
         rb -= 1
