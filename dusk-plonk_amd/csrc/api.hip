@@ -520,6 +520,26 @@ int plk_srs_last_msm_stats(const plk_srs* s, float* accumulate_ms, uint64_t* poi
   return PLK_OK;
 }
 
+int plk_srs_table_layout(const plk_srs* s, uint32_t* naf, uint32_t* rows, uint64_t* table_bytes) {
+  if (!s) return PLK_E_ARG;
+  if (naf) *naf = s->naf ? 1u : 0u;
+  if (rows) *rows = s->rows;
+  if (table_bytes) *table_bytes = (uint64_t)s->table.bytes + s->table_inf.bytes;
+  return PLK_OK;
+}
+
+int plk_msm_table_policy(uint64_t n_points, uint32_t window_bits, int c_from_env, uint32_t* naf,
+                         uint64_t* table_bytes) {
+  if (!n_points || window_bits < 8 || window_bits > 22) return PLK_E_ARG;
+  const uint64_t row_bytes = 255 * n_points * (sizeof(G1Affine) + 1);
+  const bool want = msm_naf_policy((size_t)n_points, window_bits, c_from_env != 0) &&
+                    255 * n_points < kEntryNeg && msm_naf_table_allowed(255 * n_points * sizeof(G1Affine));
+  if (naf) *naf = want ? 1u : 0u;
+  if (table_bytes)
+    *table_bytes = want ? row_bytes : (uint64_t)((255 + window_bits - 1) / window_bits) * n_points * (sizeof(G1Affine) + 1);
+  return PLK_OK;
+}
+
 }  // extern "C"
 
 // the SRS loaders' two ends, for loaders in other units (srs_io.hip)

@@ -39,7 +39,9 @@ namespace {
 // that is what the coefficient commit, the alternative, runs at anyway (n = 2^12 at c = 10:
 // 208 per bucket).
 uint32_t lagrange_bucket_max(const plk_srs* s, size_t len) {
-  const size_t dense = (size_t)s->windows * len >> (s->c - 1);
+  // (row-table layout: a random scalar gives 255 / (c + 2) + ~0.4 digits, not `windows`)
+  const size_t per = s->naf ? 255 / (s->c + 2) + 1 : s->windows;
+  const size_t dense = per * len >> (s->c - 1);
   return (uint32_t)std::max<size_t>(4 * kChunkMax, 4 * dense);
 }
 

@@ -195,7 +195,13 @@ struct plk_srs {
   // bucket range, without the short top window whose few digit values piled extra entries
   // onto a few hot buckets
   uint32_t narrow = 0;
-  plk::DevBuf points;        // affine, plk::G1Affine (96 B), n entries; inf flags separate
+  // row-table layout (msm_prepare_srs, msm_digits.hpp naf_walk): the table holds a row 2^p P for
+  // every bit position p < rows = 255 instead of one per window (rows = windows otherwise), and a
+  // scalar is recoded as a signed sliding window, <= windows odd digits. c and windows keep their
+  // meaning: 2^(c-1) buckets, at most `windows` entries per scalar
+  bool naf = false;
+  uint32_t rows = 16;
+  plk::DevBuf points;       // affine, plk::G1Affine (96 B), n entries; inf flags separate
   plk::DevBuf inf;           // uint8 per point
   plk::DevBuf table;         // precomputed 2^(c*w) * P_i, affine, windows * n entries
   plk::DevBuf table_inf;     // uint8, windows * n
@@ -342,7 +348,14 @@ int ntt_run(plk_domain* d, const Fr* in, Fr* out, size_t len_in, int dir, int co
 // loader ends with once they are filled: the has_inf scan and the MSM table (srs_finish).
 int srs_new(plk_ctx* ctx, size_t n, std::unique_ptr<plk_srs>& s);
 int srs_complete(plk_srs* s);
-int msm_prepare_srs(plk_srs* s, hipStream_t stream, uint32_t force_c = 0, bool own_ws = true);
+// force_naf (with force_c): the table layout of the SRS whose c is taken, 1 row table, 0 window table
+int msm_prepare_srs(plk_srs* s, hipStream_t stream, uint32_t force_c = 0, bool own_ws = true,
+                    int force_naf = -1);
+// The table layout msm_prepare_srs gives an SRS of n points at window size c (PLK_MSM_NAF, the
+// default for large SRSs, wide sets only) before it tries the allocation, and whether a table of
+// `bytes` may be tried at all (PLK_MSM_TABLE_CAP, bytes: a cap on the row table, 0 = none)
+bool msm_naf_policy(size_t n, uint32_t c, bool c_from_env);
+bool msm_naf_table_allowed(size_t bytes);
 // The Lagrange-basis SRS of `dom` from the first dom->n + 3 points of `src` (lagrange.hip):
 // [L_i(tau)]_1 for i < n, then [tau^(n+t)]_1 - [tau^t]_1 for t < 3; an ordinary SRS with src's
 // window size. PLK_E_ARG when src has fewer than n + 3 points.

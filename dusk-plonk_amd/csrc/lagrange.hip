@@ -121,8 +121,8 @@ int srs_lagrange_build(plk_srs* src, plk_domain* dom, bool own_ws, plk_srs** out
   a = DevBuf();
   b = DevBuf();
   pref = DevBuf();
-  // the key SRS's window size: one workspace shape serves both bases
-  if ((st = msm_prepare_srs(s.get(), stream, src->c, own_ws))) return st;
+  // the key SRS's window size and table layout: one workspace shape serves both bases
+  if ((st = msm_prepare_srs(s.get(), stream, src->c, own_ws, src->naf ? 1 : 0))) return st;
   *out = s.release();
   return PLK_OK;
 }

@@ -65,6 +65,7 @@ static int msm_plan(const plk_srs* s, const MsmWorkspace& w, const MsmBatch& bat
   p.c = s->c;
   p.W = s->windows;
   p.narrow = s->narrow;
+  p.naf = s->naf;
   p.n_srs = s->n;
   p.has_inf = s->has_inf;
   p.guard_limit = guard_limit;
@@ -127,7 +128,8 @@ static int msm_plan(const plk_srs* s, const MsmWorkspace& w, const MsmBatch& bat
 }
 
 int ws_reserve(plk_srs* s, MsmWorkspace& w, size_t len, uint32_t slots, hipStream_t stream) {
-  const bool same_shape = w.cap_c == s->c && w.cap_windows == s->windows;
+  // (a workspace sized on a window table meets a row table: the digit words are still to come)
+  const bool same_shape = w.cap_c == s->c && w.cap_windows == s->windows && (!s->naf || w.naf.ptr);
   if (same_shape && len <= w.cap_len && slots <= w.cap_slots && w.cap_len) return PLK_OK;
   // buffers only ever grow (DevBuf::alloc), so re-sizing for another shape keeps the larger
   // of the old and new needs; the strides below always match the current shape
@@ -160,6 +162,7 @@ int ws_reserve(plk_srs* s, MsmWorkspace& w, size_t len, uint32_t slots, hipStrea
   if ((st = w.partials.alloc(slots * max_tasks * sizeof(G1xyzz)))) return st;
   if (wide) {
     if ((st = w.tmp.alloc(slots * entries * sizeof(uint2)))) return st;
+    if (s->naf && (st = w.naf.alloc(slots * entries * 4))) return st;
     if ((st = w.task_rel.alloc(slots * B * 4))) return st;
     if ((st = w.bin_tot.alloc(slots * 2 * NC * 4))) return st;
     if ((st = w.len_fill.alloc(slots * kChunkMax * 4))) return st;
@@ -204,6 +207,7 @@ int ws_reserve(plk_srs* s, MsmWorkspace& w, size_t len, uint32_t slots, hipStrea
   w.cap_windows = s->windows;
   w.task_stride = max_tasks;
   w.sorted_stride = entries + 1;
+  w.naf_stride = entries;
   return PLK_OK;
 }
 
@@ -233,6 +237,13 @@ static void host_tail(const MsmPlan& p, const G1xyzz* T, plk_g1* out) {
     acc = xyzz_add(acc, a);
     for (uint32_t i = 0; i < p.rb; ++i) acc = xyzz_dbl(acc);
     acc = xyzz_add(acc, rx_to_r_domain(T[nbits]));
+  }
+  // row-table layout (wide sets only): bucket k holds the digits +-(2 k + 1), so the sum is
+  // sum_k (2 (k + 1) - 1) B_k = 2 acc - sum_r Y_r, for a part over its own buckets alike
+  if (p.naf) {
+    G1xyzz y = rx_to_r_domain(T[nbits + 1]);
+    y.Y = fe_neg(y.Y);
+    acc = xyzz_add(xyzz_dbl(acc), y);
   }
   Fp x, y;
   const bool fin = xyzz_to_affine(acc, x, y);

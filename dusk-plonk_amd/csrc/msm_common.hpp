@@ -196,6 +196,7 @@ PLK_LOCAL inline bool is_small_shape(uint32_t c, size_t len) {
 struct MsmPlan {
   uint32_t slots = 0, part = 0, parts = 1;
   uint32_t c = 0, W = 0, narrow = 0;  // the SRS's windows (plk_srs)
+  bool naf = false;                   // the SRS's row-table layout (plk_srs::naf, msm_digits.hpp)
   uint64_t n_srs = 0;
   bool has_inf = false;
   uint32_t B = 0, b_lo = 0;  // the buckets this call reduces: all 2^(c-1), or a part's range
@@ -224,6 +225,7 @@ struct MsmWorkspace {
   DevBuf counts, blockhist, offsets, task_off, full_off, len_cur, sorted, tasks, partials, bsum, bits1;
   // wide bucket sets only (msm_sort.hip: two-level sort; msm_reduce.hip: run-sum reduction)
   DevBuf tmp, task_rel, bin_tot, len_fill, coarse_off, rsum, ys, zs;
+  DevBuf naf;   // row-table layout: the scalars' digit words, W per scalar (k_chist_naf)
   DevBuf done;  // k_bitsum1's per-slot arrival counters (its fold of k_bitsum2)
   DevBuf guard;  // k_guard's per-slot running maxima and arrival counters (2 kMaxSlots words)
   // the readback record (ReadbackHeader + bit sums): coherent host memory mapped into the
@@ -231,7 +233,7 @@ struct MsmWorkspace {
   PinnedBuf host_out;
   void* out_dev = nullptr;  // host_out's device address
   uint32_t gen = 0;    // generation number of the last batch (degree-check flag stamps)
-  size_t cap_len = 0, task_stride = 0, sorted_stride = 0;
+  size_t cap_len = 0, task_stride = 0, sorted_stride = 0, naf_stride = 0;
   uint32_t cap_slots = 0;
   // the SRS shape the buffers and strides were sized for: a workspace moves between SRSs
   // (a prover's key SRS, then a shard slice with another window size), and every size

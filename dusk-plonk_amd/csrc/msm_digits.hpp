@@ -78,6 +78,105 @@ __device__ __forceinline__ void each_digit(const Fr& s, const MsmCfg& cfg, F&& f
   }
 }
 
+// ---- row-table layout (plk_srs::naf): a signed sliding window over the canonical half --------
+// The table has a row 2^p P for every bit position p, so a digit may start at any bit: a window
+// starts at a set bit of the running value (its digit is odd), the zeros after it cost nothing,
+// and with windows of up to c + 1 bits the odd digits |d| < 2^c fill the same 2^(c-1) buckets,
+// bucket (|d| - 1) / 2 weighing |d|. A uniform 254-bit half gives 255 / (c + 2) + ~0.4 digits
+// (c = 20: 11.98) instead of the fixed grid's W = 13, never more than ceil(255 / (c + 1)) <= W.
+//
+// The half stays in its registers: the walk keeps a bit position and a borrow (the running
+// value is (s >> pos) + borrow), and a window starts at the first bit >= pos that differs from
+// the borrow. Pass 1 is the greedy walk, all windows c + 1 bits, counting its digits m. Greedy's
+// top digit takes the few bits left over, whose values crowd the lowest buckets (9 % of all
+// scalars in bucket 0), so pass 2 spreads the bits over the same m digits: with rho bits still
+// to cover (one more for the borrow) and k digits to emit, a window is
+// min(c + 1, max(ceil(rho / k) - 1, rho - (c + 1)(k - 1), 2)) bits; the middle term keeps the
+// rest coverable. tests/msm_naf_ref.py states both forms, tests/test_msm_naf_cpu.py the conditions.
+
+// bits [o, o + 33) of s at least (64 taken, sh <= 31 shifted out), zero from bit 256 on
+__device__ __forceinline__ uint64_t bits_at(const Fr& s, uint32_t o) {
+  if (o >= 256) return 0;
+  const uint32_t wd = o >> 5, sh = o & 31;
+  const bool b0 = wd & 1, b1 = wd & 2, b2 = wd & 4;
+  uint64_t p[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {  // pair (2k + b0, 2k + b0 + 1), as digit_at
+    const uint32_t lo = b0 ? s.v[2 * k + 1] : s.v[2 * k];
+    const uint32_t hi = b0 ? (k < 3 ? s.v[2 * k + 2] : 0u) : s.v[2 * k + 1];
+    p[k] = ((uint64_t)hi << 32) | lo;
+  }
+  const uint64_t q0 = b1 ? p[1] : p[0], q1 = b1 ? p[3] : p[2];
+  return (b2 ? q1 : q0) >> sh;
+}
+
+__device__ __forceinline__ uint32_t fr_bit_length(const Fr& s) {
+  uint32_t len = 0;
+#pragma unroll
+  for (int k = 0; k < 8; ++k)
+    if (s.v[k]) len = 32u * k + 32u - (uint32_t)__builtin_clz(s.v[k]);
+  return len;
+}
+
+// One walk over s (bit length len): EMIT = false counts the greedy digits, EMIT = true emits
+// f(pos, d) for the k digits of pass 2. Returns the digit count. At most `cap` windows whatever
+// the input (the callers' buffers hold cap words per scalar).
+template <bool EMIT, class F>
+__device__ __forceinline__ uint32_t naf_pass(const Fr& s, uint32_t len, uint32_t c, uint32_t k,
+                                             uint32_t cap, F&& f) {
+  const uint32_t w = c + 1;
+  // a window read from one bits_at: its start at most `skip` bits in, skip + w <= 33
+  const uint32_t skip = 33 - w;
+  uint32_t pos = 0, carry = 0, n = 0;
+  while (n < cap) {
+    if (!carry && pos >= len) break;
+    const uint64_t x = bits_at(s, pos);
+    const uint32_t differ = (uint32_t)x ^ (0u - carry);  // bits that differ from the borrow
+    const uint32_t tz = (uint32_t)__builtin_ctz(differ | (1u << skip));
+    if (tz == skip && !((differ >> skip) & 1u)) {  // a longer run: look again from its end
+      pos += skip;
+      continue;
+    }
+    pos += tz;
+    uint32_t wd = w;
+    if (EMIT && k > 1) {
+      const uint32_t rho = (len > pos ? len - pos : 1u) + 1u;
+      const uint32_t even = (rho + k - 1) / k - 1, rest = w * (k - 1);
+      wd = min(w, max(max(even, rho > rest ? rho - rest : 0u), 2u));
+    }
+    const uint32_t val = ((uint32_t)(x >> tz) & ((1u << wd) - 1u)) + carry;
+    carry = val >> (wd - 1) ? 1u : 0u;  // val odd: never 2^(wd-1) itself
+    if (EMIT) f(pos, (int)val - (int)(carry << wd));
+    pos += wd;
+    --k;
+    ++n;
+  }
+  return n;
+}
+
+// A scalar's digits as words: bucket (|d| - 1) / 2 | position << 22 | (d < 0) << 31. Positions
+// stop at 254, so kNafNone (position 255) marks a word that holds no digit.
+constexpr uint32_t kNafNone = 0xFFFFFFFFu;
+constexpr uint32_t kNafMaxW = 15;  // digits per scalar at most: W of the wide sets (c >= 17)
+constexpr uint32_t kNafPosShift = 22;
+__device__ __forceinline__ uint32_t naf_word(uint32_t pos, int d) {
+  const uint32_t a = (uint32_t)(d < 0 ? -d : d);
+  return ((a - 1u) >> 1) | (pos << kNafPosShift) | (d < 0 ? 0x80000000u : 0u);
+}
+__device__ __forceinline__ uint32_t naf_bucket(uint32_t word) { return word & ((1u << kNafPosShift) - 1u); }
+__device__ __forceinline__ uint32_t naf_pos(uint32_t word) { return (word >> kNafPosShift) & 255u; }
+__device__ __forceinline__ bool naf_neg(uint32_t word) { return word >> 31; }
+
+// Both passes: f(j, word) for j = 0 .. digits - 1 in order of position. Returns the count (<= W).
+template <class F>
+__device__ __forceinline__ uint32_t naf_walk(const Fr& s, const MsmCfg& cfg, F&& f) {
+  const uint32_t len = fr_bit_length(s);
+  const uint32_t m = naf_pass<false>(s, len, cfg.c, 0, cfg.W, [](uint32_t, int) {});
+  uint32_t j = 0;
+  naf_pass<true>(s, len, cfg.c, m, cfg.W, [&](uint32_t pos, int d) { f(j++, naf_word(pos, d)); });
+  return m;
+}
+
 __device__ __forceinline__ void slot_range(uint32_t len, uint32_t& i0, uint32_t& i1) {
   const uint32_t per = (len + gridDim.x - 1) / gridDim.x;
   i0 = blockIdx.x * per;

@@ -588,6 +588,90 @@ __global__ void __launch_bounds__(kHistThreads) k_cscatter(MsmBatch batch, MsmCf
   });
 }
 
+// Wide pass 1 and 2 of the row-table layout (MsmPlan::naf; msm_digits.hpp naf_walk). Each scalar
+// is recoded ONCE: k_chist_naf walks it, counts its digits' bins and leaves the digit words in
+// naf[j * len + i] (W words per scalar, kNafNone after the last digit); k_cscatter_naf reads them
+// back (the scalars not at all) and scatters (pos * n_srs + i | sign, bucket). A part keeps the
+// digits of its bucket range, as the window layout's kernels do.
+__global__ void __launch_bounds__(kHistThreads) k_chist_naf(MsmBatch batch, MsmCfg cfg, uint32_t NC,
+                                                            uint32_t fb, uint32_t* __restrict__ blockhist,
+                                                            uint32_t* __restrict__ naf, uint64_t naf_stride) {
+  __shared__ uint32_t hist[kCoarseMax];
+  const uint32_t slot = blockIdx.y, len = batch.len[slot];
+  uint32_t i0, i1;
+  slot_range(len, i0, i1);
+  const Fr* sc = batch.scalars[slot];
+  uint32_t* words = naf + (size_t)slot * naf_stride;
+  for (uint32_t b = threadIdx.x; b < NC; b += blockDim.x) hist[b] = 0;
+  __syncthreads();
+  for_scalars(sc, i0, i1, threadIdx.x, blockDim.x, [&](uint32_t i, const Fr& s, bool neg) {
+    const uint32_t m = naf_walk(s, cfg, [&](uint32_t j, uint32_t word) {
+      words[(size_t)j * len + i] = neg ? word ^ 0x80000000u : word;
+      const uint32_t b = naf_bucket(word) - cfg.b_lo;  // below the part's range: wraps past B
+      if (b < cfg.B) atomicAdd(&hist[b >> fb], 1u);
+    });
+    for (uint32_t j = m; j < cfg.W; ++j) words[(size_t)j * len + i] = kNafNone;
+  });
+  __syncthreads();
+  uint32_t* out = blockhist + ((size_t)slot * gridDim.x + blockIdx.x) * NC;
+  for (uint32_t b = threadIdx.x; b < NC; b += blockDim.x) out[b] = hist[b];
+}
+
+__global__ void __launch_bounds__(kHistThreads) k_cscatter_naf(MsmBatch batch, MsmCfg cfg, uint32_t NC,
+                                                               uint32_t fb, uint64_t n_srs,
+                                                               const uint32_t* __restrict__ ccounts,
+                                                               const uint32_t* __restrict__ blockhist,
+                                                               uint32_t* __restrict__ coarse_off,
+                                                               uint2* __restrict__ tmp, uint64_t tmp_stride,
+                                                               const uint32_t* __restrict__ naf,
+                                                               uint64_t naf_stride) {
+  __shared__ uint32_t hist[kCoarseMax];
+  __shared__ uint32_t sh[32];
+  const uint32_t slot = blockIdx.y, tid = threadIdx.x, len = batch.len[slot];
+  const uint32_t* cc = ccounts + (size_t)slot * NC;
+  const uint32_t* bh = blockhist + ((size_t)slot * gridDim.x + blockIdx.x) * NC;
+  uint32_t* co = coarse_off + (size_t)slot * (NC + 1);
+  uint32_t loc[4], v[1], tot[1];
+  v[0] = 0;
+#pragma unroll
+  for (uint32_t q = 0; q < 4; ++q) {  // the bin offsets, as k_cscatter
+    const uint32_t b = 4 * tid + q;
+    loc[q] = b < NC ? cc[b] : 0u;
+    v[0] += loc[q];
+  }
+  block_scan_excl<1>(v, tot, sh);
+  uint32_t run = v[0];
+#pragma unroll
+  for (uint32_t q = 0; q < 4; ++q) {
+    const uint32_t b = 4 * tid + q;
+    if (b < NC) {
+      if (blockIdx.x == 0) co[b] = run;
+      hist[b] = run + bh[b];
+    }
+    run += loc[q];
+  }
+  if (blockIdx.x == 0 && tid == 0) co[NC] = tot[0];
+  __syncthreads();
+  uint32_t i0, i1;
+  slot_range(len, i0, i1);
+  const uint32_t* words = naf + (size_t)slot * naf_stride;
+  uint2* out = tmp + (size_t)slot * tmp_stride;
+  for (uint32_t i = i0 + tid; i < i1; i += blockDim.x) {
+    uint32_t wv[kNafMaxW];  // every load in flight before the first atomic
+#pragma unroll
+    for (uint32_t j = 0; j < kNafMaxW; ++j) wv[j] = j < cfg.W ? words[(size_t)j * len + i] : kNafNone;
+#pragma unroll
+    for (uint32_t j = 0; j < kNafMaxW; ++j) {
+      const uint32_t word = wv[j];
+      const uint32_t b = naf_bucket(word) - cfg.b_lo;
+      if (word != kNafNone && b < cfg.B) {
+        const uint32_t pos = atomicAdd(&hist[b >> fb], 1u);
+        out[pos] = make_uint2(entry_code((uint32_t)(naf_pos(word) * n_srs + i), naf_neg(word)), b);
+      }
+    }
+  }
+}
+
 // Wide pass 3: one workgroup per (bin, slot), one thread per bucket of the bin. Counting sort
 // of the bin's entries by bucket into its own region of `sorted`; bucket offsets (global),
 // per-bucket task and full-task offsets relative to the bin, the bin's totals and the
@@ -867,7 +951,11 @@ void sort_fine(const MsmPlan& p, MsmWorkspace& w, hipStream_t stream) {
 int sort_wide(const MsmPlan& p, const MsmBatch& batch, MsmWorkspace& w, hipStream_t stream) {
   const uint32_t NC = p.NC, fb = p.fb, slots = p.slots, hist_blocks = p.hist_blocks;
   const MsmCfg cfg = p.cfg();
-  if (p.max_len) {
+  if (p.max_len && p.naf) {
+    hipLaunchKernelGGL(k_chist_naf, dim3(hist_blocks, slots), dim3(kHistThreads), 0, stream, batch,
+                       cfg, NC, fb, w.blockhist.as<uint32_t>(), w.naf.as<uint32_t>(),
+                       (uint64_t)w.naf_stride);
+  } else if (p.max_len) {
     by_c(CWide{}, p.c, [&](auto cc) {
       hipLaunchKernelGGL(k_chist<decltype(cc)::value>, dim3(hist_blocks, slots), dim3(kHistThreads), 0,
                          stream, batch, cfg, NC, fb, w.blockhist.as<uint32_t>());
@@ -878,7 +966,13 @@ int sort_wide(const MsmPlan& p, const MsmBatch& batch, MsmWorkspace& w, hipStrea
   hipLaunchKernelGGL(k_block_scan, dim3(cdiv(NC, 256), slots), dim3(256), 0, stream,
                      w.blockhist.as<uint32_t>(), hist_blocks, NC, w.counts.as<uint32_t>(),
                      w.len_cur.as<uint32_t>(), w.len_fill.as<uint32_t>());
-  by_c(CWide{}, p.c, [&](auto cc) {
+  if (p.naf) {
+    hipLaunchKernelGGL(k_cscatter_naf, dim3(hist_blocks, slots), dim3(kHistThreads), 0, stream, batch,
+                       cfg, NC, fb, p.n_srs, (const uint32_t*)w.counts.as<uint32_t>(),
+                       (const uint32_t*)w.blockhist.as<uint32_t>(), w.coarse_off.as<uint32_t>(),
+                       w.tmp.as<uint2>(), (uint64_t)(w.sorted_stride - 1),
+                       (const uint32_t*)w.naf.as<uint32_t>(), (uint64_t)w.naf_stride);
+  } else by_c(CWide{}, p.c, [&](auto cc) {
     hipLaunchKernelGGL(k_cscatter<decltype(cc)::value>, dim3(hist_blocks, slots), dim3(kHistThreads),
                        0, stream, batch, cfg, NC, fb, p.n_srs,
                        (const uint32_t*)w.counts.as<uint32_t>(),

@@ -147,7 +147,32 @@ int srs_batch_affine(const G1xyzz* temp, uint64_t n, Fp* pref, G1Affine* out, ui
 // force_c: another SRS's (final) window size instead of choose_c's (the Lagrange-basis SRS of a
 // key, lagrange.hip, shares its provers' workspaces with the key's SRS). own_ws = false: no
 // workspace of its own (an SRS that only msm_run_batch callers with their own workspace use).
-int msm_prepare_srs(plk_srs* s, hipStream_t stream, uint32_t force_c, bool own_ws) {
+// Row-table layout (plk_srs::naf): PLK_MSM_NAF = 1 asks for it, 0 forbids it; otherwise it is
+// the default for an SRS of 2^20 points and up whose window size choose_c picked itself
+// (PLK_MSM_C alone keeps the window table). Wide bucket sets only: the host tail needs their
+// sum_r Y_r (msm.hip host_tail). 2^20 proofs, 12 lanes, against the window table on one box:
+// 39.2-39.4 -> 40.2-40.3 M constraints/s (profiles/msm_naf_ab.jsonl); SRSs below
+// 2^20 points (c = 17) are not measured and keep the window table. PLK_NAF_DEFAULT 0: opt-in only.
+#ifndef PLK_NAF_DEFAULT
+#define PLK_NAF_DEFAULT 1
+#endif
+bool msm_naf_policy(size_t n, uint32_t c, bool c_from_env) {
+  if (!is_wide(c)) return false;
+  if (const char* e = getenv("PLK_MSM_NAF")) return atoi(e) == 1;
+  return PLK_NAF_DEFAULT && !c_from_env && n >= ((size_t)1 << 20);
+}
+
+// PLK_MSM_TABLE_CAP (bytes; tests): a row table above it counts as one that could not be allocated
+bool msm_naf_table_allowed(size_t bytes) {
+  const char* e = getenv("PLK_MSM_TABLE_CAP");
+  const unsigned long long cap = e ? strtoull(e, nullptr, 10) : 0;
+  return cap == 0 || bytes <= cap;
+}
+
+constexpr uint32_t kNafRows = 255;  // bit positions 0 .. 254 of a half below 2^254 and its borrow
+
+int msm_prepare_srs(plk_srs* s, hipStream_t stream, uint32_t force_c, bool own_ws, int force_naf) {
+  const bool c_from_env = !force_c && getenv("PLK_MSM_C") != nullptr;
   s->c = force_c ? force_c : choose_c(s->n);
   // every window would be c - 1 bits (c = 18: 15 x 17 = 255): that is the c - 1 layout
   if (!force_c && (s->c - 1) * ((255 + s->c - 1) / s->c) == 255) s->c -= 1;
@@ -163,8 +188,24 @@ int msm_prepare_srs(plk_srs* s, hipStream_t stream, uint32_t force_c, bool own_w
   s->narrow = s->c * s->windows - 255;
   const size_t n = s->n;
   int st;
-  if ((st = s->table.alloc((size_t)s->windows * n * sizeof(G1Affine)))) return st;
-  if ((st = s->table_inf.alloc((size_t)s->windows * n))) return st;
+  // the layout: the row table where the policy (or the SRS whose shape this one takes) asks for
+  // it, its entry codes fit (row n + i below the sign bit) and its memory can be had; the
+  // window table otherwise, never a failed setup for the row table's sake
+  s->naf = is_wide(s->c) && (force_c && force_naf >= 0 ? force_naf == 1 : msm_naf_policy(n, s->c, c_from_env));
+  if (s->naf && (uint64_t)kNafRows * n >= kEntryNeg) s->naf = false;
+  if (s->naf) {
+    const size_t bytes = (size_t)kNafRows * n * sizeof(G1Affine);
+    if (!msm_naf_table_allowed(bytes) || s->table.alloc(bytes) != PLK_OK ||
+        s->table_inf.alloc((size_t)kNafRows * n) != PLK_OK) {
+      (void)hipGetLastError();  // a refused allocation is not this setup's error
+      s->table = DevBuf();
+      s->table_inf = DevBuf();
+      s->naf = false;
+    }
+  }
+  s->rows = s->naf ? kNafRows : s->windows;
+  if ((st = s->table.alloc((size_t)s->rows * n * sizeof(G1Affine)))) return st;
+  if ((st = s->table_inf.alloc((size_t)s->rows * n))) return st;
   PLK_HIP_TRY(hipMemcpyAsync(s->table.ptr, s->points.ptr, n * sizeof(G1Affine),
                              hipMemcpyDeviceToDevice, stream));
   PLK_HIP_TRY(hipMemcpyAsync(s->table_inf.ptr, s->inf.ptr, n, hipMemcpyDeviceToDevice, stream));
@@ -175,18 +216,19 @@ int msm_prepare_srs(plk_srs* s, hipStream_t stream, uint32_t force_c, bool own_w
   uint8_t* tinf = s->table_inf.as<uint8_t>();
   // row w = 2^(o_w - s_w) P (o_w the window's bit offset, s_w = 1 for narrow windows): from
   // row w - 1 by c doublings while both are wide, c - 1 from the first narrow one on
-  for (uint32_t w = 1; w < s->windows; ++w) {
-    hipLaunchKernelGGL(k_double_c, dim3(cdiv(n, 256)), dim3(256), 0, stream, tab + (w - 1) * n,
-                       tinf + (w - 1) * n, (uint64_t)n,
-                       w < s->windows - s->narrow ? s->c : s->c - 1, temp.as<G1xyzz>());
+  // (row table: row p = 2^p P, one doubling from row p - 1)
+  for (uint32_t w = 1; w < s->rows; ++w) {
+    hipLaunchKernelGGL(k_double_c, dim3(cdiv(n, 256)), dim3(256), 0, stream, tab + (size_t)(w - 1) * n,
+                       tinf + (size_t)(w - 1) * n, (uint64_t)n,
+                       s->naf ? 1u : w < s->windows - s->narrow ? s->c : s->c - 1, temp.as<G1xyzz>());
     hipLaunchKernelGGL(k_batch_affine, dim3(cdiv(cdiv(n, kBatchAff), 128)), dim3(128), 0, stream,
                        temp.as<G1xyzz>(), (uint64_t)n, pref.as<Fp>(), tab + w * n, tinf + w * n);
     PLK_HIP_TRY(hipGetLastError());
   }
   // table holds R-domain points up to here (each window doubles the previous one); the
   // MSM reads it in the R' domain
-  hipLaunchKernelGGL(k_table_to_rx, dim3(cdiv((uint64_t)s->windows * n, 256)), dim3(256), 0, stream,
-                     tab, (uint64_t)s->windows * n);
+  hipLaunchKernelGGL(k_table_to_rx, dim3(cdiv((uint64_t)s->rows * n, 256)), dim3(256), 0, stream,
+                     tab, (uint64_t)s->rows * n);
   PLK_HIP_TRY(hipGetLastError());
   PLK_HIP_TRY(stream_wait(stream));
   if (!own_ws) return PLK_OK;

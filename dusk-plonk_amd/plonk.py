@@ -58,6 +58,8 @@ _KZG_SYMBOLS = ("plk_kzg_open", "plk_kzg_open_domain", "plk_kzg_last_open_ms", "
 
 # the MSM stage snapshot of csrc/debug.hip (bound only when the loaded library has it, as above)
 _MSM_DEBUG_SYMBOLS = ("plk_debug_msm_snapshot",)
+# the MSM table's layout report and policy (csrc/api.hip; optional in the same way)
+_MSM_LAYOUT_SYMBOLS = ("plk_srs_table_layout", "plk_msm_table_policy")
 
 # Symbols declared in include/plk.h (checked by tests/test_abi.py)
 ABI_SYMBOLS = (
@@ -112,6 +114,7 @@ ABI_SYMBOLS = (
     *_KZG_SYMBOLS,
     # the fixed-base MSM's stage snapshot (debug_msm_snapshot here)
     *_MSM_DEBUG_SYMBOLS,
+    *_MSM_LAYOUT_SYMBOLS,
 )
 
 # per-item status of the ingest calls (include/plk.h PLK_INGEST_*)
@@ -243,10 +246,12 @@ def _lib():
             "plk_kzg_fold_cosets": (i32, [vp, u32, vp, vp, vp, vp, sz, vp, vp]),
             "plk_debug_g1_ntt_batch": (i32, [vp, vp, u32, sz, i32, vp]),
             "plk_debug_g1_colsum": (i32, [vp, vp, sz, sz, vp]),
+            "plk_srs_table_layout": (i32, [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u64)]),
+            "plk_msm_table_policy": (i32, [u64, u32, i32, C.POINTER(u32), C.POINTER(u64)]),
         }
         for name, (res, args) in sig.items():
             if (name in _SRS_IO_SYMBOLS + _SRS_UPDATE_SYMBOLS + _CHECK_SYMBOLS + _KZG_SYMBOLS
-                    + _MSM_DEBUG_SYMBOLS and not hasattr(lib, name)):
+                    + _MSM_DEBUG_SYMBOLS + _MSM_LAYOUT_SYMBOLS and not hasattr(lib, name)):
                 continue  # a PLK_LIB build from before srs_io.hip still loads; a use fails loudly
             f = getattr(lib, name)
             f.restype, f.argtypes = res, args
@@ -1181,6 +1186,14 @@ class PlonkParams:
         _check(_lib().plk_srs_last_msm_stats(self._h, C.byref(ms), C.byref(adds), C.byref(c)),
                "plk_srs_last_msm_stats")
         return ms.value, adds.value, c.value
+
+    def table_layout(self) -> dict:
+        """The MSM table this SRS got: {"naf": row table (True) or window table, "rows",
+        "table_bytes"} (plk_srs_table_layout)."""
+        naf, rows, nbytes = C.c_uint32(), C.c_uint32(), C.c_uint64()
+        _check(_lib().plk_srs_table_layout(self._h, C.byref(naf), C.byref(rows), C.byref(nbytes)),
+               "plk_srs_table_layout")
+        return {"naf": bool(naf.value), "rows": rows.value, "table_bytes": nbytes.value}
 
     def __del__(self):
         try:

@@ -223,6 +223,17 @@ int plk_srs_last_msm_stats(const plk_srs* srs, float* accumulate_ms, uint64_t* p
 int plk_srs_msm_stats_reset(plk_srs* srs);
 int plk_srs_cum_msm_stats(const plk_srs* srs, double* accumulate_ms, uint64_t* launches,
                           uint64_t* point_adds, uint64_t* points);
+/* The layout of this SRS's MSM table: naf = 1 for the row table (a row 2^p P for every bit position
+ * p < rows = 255, scalars recoded as a signed sliding window), 0 for the window table (rows = the
+ * window count); table_bytes = device memory of the table and its infinity flags. */
+int plk_srs_table_layout(const plk_srs* srs, uint32_t* naf, uint32_t* rows, uint64_t* table_bytes);
+/* The layout an SRS of n_points at window_bits would be set up with, before the allocation is
+ * tried (no GPU needed): PLK_MSM_NAF = 1 / 0 asks for / forbids the row table, which only bucket
+ * sets of window_bits >= 17 support; c_from_env: the window size came from PLK_MSM_C. A row table
+ * above PLK_MSM_TABLE_CAP bytes (when set) counts as one that cannot be allocated: the window
+ * table then, as after a failed allocation. */
+int plk_msm_table_policy(uint64_t n_points, uint32_t window_bits, int c_from_env, uint32_t* naf,
+                         uint64_t* table_bytes);
 
 /* ---- prover: Plonk composer, PlonkKey::compile, Prover::create_proof --------------------
  * The callers of the hot path, restated on the C++ host with every O(n) step
